@@ -13,17 +13,26 @@ reference's deployment mode), refine_iter=3, use_positivity=True, ONE stereo pai
 across ranks with no data-path collective; for N>1 each step ends with the RCCL gather of the three output maps to rank 0).
 Inputs are synthetic uint8-valued images already resident in HBM; weights are the seeded random init (no checkpoints ship).
 
-The JSON line carries, next to the contract's fields:
+A plain run sets up, warms up, times the ``--steps`` forwards and prints the line.  The JSON line carries, next to the contract's fields
+(``ms_per_step`` = milliseconds of one timed step, max over ranks):
 * ``roofline``            K1 = LayerNorm + correlation kernel, HBM bound: a start / stop HIP event pair attached to each of its
                           dispatches inside the timed region (hipExtLaunchKernel: the kernel's own execution time, the quantity
                           a rocprofv3 kernel trace reports);
+
+``--full`` adds everything that takes launches, runs or host work of its own after the timed region:
+* ``roofline.both_variants`` / ``roofline.ln_inside_k1_in_forward``  the two K1 forms measured back to back and in a second module;
+* ``gpu_state``           power cap / clocks read before and after the timed region (hwmon, rocm-smi);
 * ``roofline_attention``  K4 attention kernels, MFMA bound: one instrumented eager forward AFTER the timed region with HIP events
                           around every K4 launch, analytic FLOPs 4*N^2*d*heads*batch -> fraction of the dense
                           fp16 MFMA peak (north_star: "MFMA utilisation on the attention GEMMs");
 * ``forward``             multiply-accumulate work of one forward as executed (counted per launch) / time per pair;
 * ``cpu_baseline``        the reference's own CPU forward (oracle/_ref = the unmodified reference model byte-compiled by
                           oracle/make_ref.py; kind "reference") on this box's host cores: thread-count sweep, 1 warm-up + 3 timed
-                          runs at the best count.
+                          runs at the best count;
+* ``secondary*``          the 640x480 size, a batch of 2, two streams in flight, the L / M / XL models (``--no-secondary`` drops them).
+
+``--dump-outputs DIR`` writes the (disp, occ, conf) maps the timed path returned in its last step as ``DIR/<name>.npy`` (float32; above
+64 MB in all, a fixed seeded sample of each).  Inputs and weights are seeded: two builds run with the same arguments compare output for output.
 
 ``--dry`` (CPU, gloo, no model): exercises launcher, rendezvous, gather and max-over-ranks timing without a GPU (tests).
 """
@@ -56,11 +65,39 @@ def parse():
     ap.add_argument("--pairs-per-gpu", type=int, default=1)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
     ap.add_argument("--refine-iter", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 640x480 block measured after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary sizes and models")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--dry", action="store_true", help="CPU/gloo plumbing check of the multi-rank path: no GPU, no model")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure the K1 variants, attention / forward rooflines, "
+                                                        "GPU state, secondary sizes and models and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64_000_000                      # --dump-outputs: every file together, headers included
+OUTPUT_NAMES = ("disp", "occ", "conf")
+
+
+def dump_outputs(out, dirname, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays a caller received from the last timed step -> ``dirname/<name>.npy`` in float32.  When they hold more
+    than ``limit`` bytes together, each is replaced by the same fraction of its elements, taken at sorted flat positions drawn by a
+    fixed-seed generator: the same positions in every run with the same arguments.  -> {name: stored shape}"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = [o.detach().float().cpu().numpy() if hasattr(o, "detach") else np.asarray(o, dtype=np.float32) for o in out]
+    room = limit - 4096 * len(arrs)                                # room for the .npy headers
+    total = sum(4 * x.size for x in arrs)
+    shapes = {}
+    for k, (name, x) in enumerate(zip(OUTPUT_NAMES, arrs)):
+        if total > room:
+            flat = x.reshape(-1)
+            n = int(flat.size * (room / total))
+            x = flat[np.sort(np.random.default_rng(k).choice(flat.size, n, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+        shapes[name] = list(x.shape)
+    sys.stderr.write(f"bench.py: outputs of the last timed step -> {dirname}: {shapes}{' (seeded sample)' if total > room else ''}\n")
+    return shapes
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -500,10 +537,11 @@ def dry_run(a, rank, world):
     right = torch.rand(a.pairs_per_gpu, 3, 32, 64, generator=g)
     pending = [None]
     got = []
+    last = [None]
 
     def step():
         d = (left - right).mean(dim=1, keepdim=True)
-        out = (d, d * 0.5, d.abs())
+        out = last[0] = (d, d * 0.5, d.abs())
         if world > 1:
             if pending[0] is not None:
                 got.append(pending[0].wait())
@@ -525,6 +563,8 @@ def dry_run(a, rank, world):
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(got[-1] if world > 1 else last[0], a.dump_outputs)
     if rank == 0:
         ok = world == 1 or all(x is not None and tuple(x[0].shape) == (world * a.pairs_per_gpu, 1, 32, 64) for x in got)
         pairs = a.steps * a.pairs_per_gpu * world
@@ -560,9 +600,8 @@ def main():
         import torch.distributed as dist
         _quiet_init(dist, "nccl", rank, world, dev)
 
-    from s2m2_amd import hip
     from s2m2_amd.model import build_model
-    from s2m2_amd.shard import gather_outputs_async
+    from s2m2_amd.shard import gather_outputs, gather_outputs_async
     from s2m2_amd.weights import noise_pair
 
     model = build_model(a.model, use_positivity=True, refine_iter=a.refine_iter).to(dev).eval()
@@ -600,17 +639,18 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     eng.k1_events.clear()                             # keep only the launches of the timed region
-    state_before = gpu_state(local_rank) if rank == 0 else None
+    state_before = gpu_state(local_rank) if rank == 0 and a.full else None
     t0 = time.perf_counter()
+    out = None
     for _ in range(a.steps):
-        step()
+        out = step()
     drain()                                           # the last gather belongs to the timed region
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    state_after = gpu_state(local_rank) if rank == 0 else None
+    state_after = gpu_state(local_rank) if rank == 0 and a.full else None
     k1_ms = [t.elapsed_us() * 1e-3 for t in eng.k1_events]
     own_elapsed = elapsed
     per_rank_ms = [1e3 * elapsed / a.steps]
@@ -629,6 +669,12 @@ def main():
         devices = [None] * world
         dist.all_gather_object(devices, me)
 
+    if a.dump_outputs:
+        # what a caller of the timed path receives: on N > 1 the gathered maps of every rank (the last step's gather once more, all ranks)
+        res = gather_outputs(out, dist, dst=0) if gather else out
+        if rank == 0:
+            dump_outputs(res, a.dump_outputs)
+
     if rank == 0:
         h, w, C = a.height // 4, a.width // 4, model.feature_channels
         e = 2 if use_fp16 else 4
@@ -646,34 +692,6 @@ def main():
         pairs = a.steps * B * world
         ms_per_pair_gpu = 1e3 * elapsed / (a.steps * B)             # one GPU's time per pair
         traffic, traffic_src = pmc_traffic(a.model, a.height, a.width, use_fp16, B) if eng.cv_band < 0 else (None, None)
-        # the OTHER variant of the judged kernel in the same process, same dispatch-attached events: K1 with the LayerNorm inside (s2m2_ln_corr)
-        # on the very tokens of the last forward (back to back: the tokens sit in L2 / Infinity Cache, the in-forward figure above does not have
-        # that luxury), and the shipped variant measured the same way for comparison.  Same-box end-to-end A/B of the two:
-        # profiles/r04/ab_k1_fold.txt (5 alternating runs: 8.819 vs 8.815 ms per pair -- the choice does not move the forward)
-        k1_both = None
-        try:
-            runner = next(iter(model._graphs.values()), None)
-            tok = runner.state[0] if runner is not None and getattr(runner, "split", False) else None
-            if tok is not None and eng.cv_band < 0:
-                def k1_loop(fn):
-                    ts = []
-                    for _ in range(25):
-                        t = hip.KernelTimer()
-                        fn(t)
-                        ts.append(t)
-                    torch.cuda.synchronize()
-                    us = sorted(t.elapsed_us() for t in ts[5:])
-                    return us[len(us) // 2]
-                own = k1_loop(lambda t: hip.ln_corr(tok, eng.ln_w, eng.ln_b, out=runner.cv, timer=t))
-                k1_both = {"ln_inside_k1_us_back_to_back": own, "ln_inside_k1_frac": k1_bytes / (own * 1e-6) / 1e9 / HBM_PEAK_GBS}
-                if runner.normed is not None:
-                    shp = k1_loop(lambda t: hip.corr(runner.normed, out=runner.cv, timer=t))
-                    k1_both.update({"shipped_us_back_to_back": shp, "shipped_frac_back_to_back": k1_bytes / (shp * 1e-6) / 1e9 / HBM_PEAK_GBS})
-        except Exception as e:  # noqa: BLE001  (an extra, never the line)
-            k1_both = {"error": str(e)[:200]}
-        # ---- after the timed region: one instrumented eager forward (work meter + HIP events around every K4 launch)
-        attn_block, fwd_block = attention_and_work(eng, left, right, use_fp16, B, ms_per_pair_gpu)
-        eng.k1_events = None
         line = {
             "metric": "stereo pairs/sec, S-model 1216x1024 fp16 refine_iter=3 (ms/pair = 1000*n_gpus/value)",
             "value": pairs / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -686,44 +704,84 @@ def main():
             "roofline": {"kernel": "ln_corr_kernel (K1: all-pairs correlation of the LayerNorm'ed tokens -> cost volume)", "bound": "hbm", "variant": k1_variant,
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes_per_launch": k1_bytes, "avg_launch_us": k1_us,
-                         "launches_timed": len(k1_ms), "store_policy": "sc1 write-through (S2M2_K1_NT=%s)" % os.environ.get("S2M2_K1_NT", "2"),
-                         "both_variants": k1_both},
-            "roofline_attention": attn_block,
-            "forward": fwd_block,
+                         "launches_timed": len(k1_ms), "store_policy": "sc1 write-through (S2M2_K1_NT=%s)" % os.environ.get("S2M2_K1_NT", "2")},
         }
         line["per_rank_ms_per_step"] = [round(x, 4) for x in per_rank_ms]
-        line["gpu_state"] = {"before_timed_region": state_before, "after_timed_region": state_after,
-                             "note": "board power cap / average power / clocks read by rank 0 outside the timed region (hwmon, rocm-smi); boxes of "
-                                     "the pool differ by 2 - 5 % end to end on the same build"}
-        if not a.no_secondary and (a.height, a.width) != (480, 640):
-            line["secondary"] = secondary_640x480(model, eng, dev, use_fp16, a.refine_iter, a.model)
-            if B == 1:
-                line["secondary_batched"] = secondary_batched(model, dev, use_fp16, a, pairs=2)
-                if world == 1:
-                    try:
-                        line["secondary_two_streams"] = secondary_two_streams(model, dev, use_fp16, a)
-                    except Exception as e:  # noqa: BLE001  (an extra, never the line)
-                        line["secondary_two_streams"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
         if devices is not None:
             line["rccl_ranks"], line["distinct_gpus"], line["gpu_uuids"] = world, len(set(devices)), devices
-        if not a.no_secondary and world == 1 and (a.model, a.height, a.width, B) == ("S", 1024, 1216, 1) and use_fp16:
-            # the judged kernel's other form inside a forward, and the other BASELINE configurations (driver-run record of c4 / c5 / M)
-            try:
-                line["roofline"]["ln_inside_k1_in_forward"] = k1_ln_inside_in_forward(a, dev, use_fp16)
-            except Exception as e:  # noqa: BLE001  (an extra, never the line)
-                line["roofline"]["ln_inside_k1_in_forward"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
-            for key, (tag, mt, H2, W2, pos, st) in (("secondary_L", ("c4", "L", 1024, 1216, True, 10)), ("secondary_M", ("M", "M", 1024, 1216, True, 10)),
-                                                    ("secondary_XL", ("c5", "XL", 2048, 2432, False, 3))):
-                try:
-                    line[key] = secondary_config(tag, mt, H2, W2, pos, dev, use_fp16, a.refine_iter, st)
-                except Exception as e:  # noqa: BLE001
-                    line[key] = {"config": tag, "error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if world == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(a.model, a.height, a.width, a.refine_iter)
+        if a.full:
+            full_extras(line, a, model, eng, left, right, dev, use_fp16, B, world, k1_bytes, ms_per_pair_gpu, state_before, state_after)
+        eng.k1_events = None
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def k1_both_variants(model, eng, k1_bytes):
+    """--full: K1 back to back on the tokens of the last timed forward, both forms"""
+    import torch
+    from s2m2_amd import hip
+    # the OTHER variant of the judged kernel in the same process, same dispatch-attached events: K1 with the LayerNorm inside (s2m2_ln_corr)
+    # on the very tokens of the last forward (back to back: the tokens sit in L2 / Infinity Cache, the in-forward figure above does not have
+    # that luxury), and the shipped variant measured the same way for comparison.  Same-box end-to-end A/B of the two:
+    # profiles/r04/ab_k1_fold.txt (5 alternating runs: 8.819 vs 8.815 ms per pair -- the choice does not move the forward)
+    k1_both = None
+    try:
+        runner = next(iter(model._graphs.values()), None)
+        tok = runner.state[0] if runner is not None and getattr(runner, "split", False) else None
+        if tok is not None and eng.cv_band < 0:
+            def k1_loop(fn):
+                ts = []
+                for _ in range(25):
+                    t = hip.KernelTimer()
+                    fn(t)
+                    ts.append(t)
+                torch.cuda.synchronize()
+                us = sorted(t.elapsed_us() for t in ts[5:])
+                return us[len(us) // 2]
+            own = k1_loop(lambda t: hip.ln_corr(tok, eng.ln_w, eng.ln_b, out=runner.cv, timer=t))
+            k1_both = {"ln_inside_k1_us_back_to_back": own, "ln_inside_k1_frac": k1_bytes / (own * 1e-6) / 1e9 / HBM_PEAK_GBS}
+            if runner.normed is not None:
+                shp = k1_loop(lambda t: hip.corr(runner.normed, out=runner.cv, timer=t))
+                k1_both.update({"shipped_us_back_to_back": shp, "shipped_frac_back_to_back": k1_bytes / (shp * 1e-6) / 1e9 / HBM_PEAK_GBS})
+    except Exception as e:  # noqa: BLE001  (an extra, never the line)
+        k1_both = {"error": str(e)[:200]}
+    return k1_both
+
+
+def full_extras(line, a, model, eng, left, right, dev, use_fp16, B, world, k1_bytes, ms_per_pair_gpu, state_before, state_after):
+    """--full: rank 0's measurements after the timed region, each with launches or runs of its own (none of them part of `value`)"""
+    line["roofline"]["both_variants"] = k1_both_variants(model, eng, k1_bytes)
+    # one instrumented eager forward (work meter + HIP events around every K4 launch)
+    line["roofline_attention"], line["forward"] = attention_and_work(eng, left, right, use_fp16, B, ms_per_pair_gpu)
+    eng.k1_events = None
+    line["gpu_state"] = {"before_timed_region": state_before, "after_timed_region": state_after,
+                         "note": "board power cap / average power / clocks read by rank 0 outside the timed region (hwmon, rocm-smi); boxes of "
+                                 "the pool differ by 2 - 5 % end to end on the same build"}
+    if not a.no_secondary and (a.height, a.width) != (480, 640):
+        line["secondary"] = secondary_640x480(model, eng, dev, use_fp16, a.refine_iter, a.model)
+        if B == 1:
+            line["secondary_batched"] = secondary_batched(model, dev, use_fp16, a, pairs=2)
+            if world == 1:
+                try:
+                    line["secondary_two_streams"] = secondary_two_streams(model, dev, use_fp16, a)
+                except Exception as e:  # noqa: BLE001  (an extra, never the line)
+                    line["secondary_two_streams"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
+    if not a.no_secondary and world == 1 and (a.model, a.height, a.width, B) == ("S", 1024, 1216, 1) and use_fp16:
+        # the judged kernel's other form inside a forward, and the other BASELINE configurations (driver-run record of c4 / c5 / M)
+        try:
+            line["roofline"]["ln_inside_k1_in_forward"] = k1_ln_inside_in_forward(a, dev, use_fp16)
+        except Exception as e:  # noqa: BLE001  (an extra, never the line)
+            line["roofline"]["ln_inside_k1_in_forward"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
+        for key, (tag, mt, H2, W2, pos, st) in (("secondary_L", ("c4", "L", 1024, 1216, True, 10)), ("secondary_M", ("M", "M", 1024, 1216, True, 10)),
+                                                ("secondary_XL", ("c5", "XL", 2048, 2432, False, 3))):
+            try:
+                line[key] = secondary_config(tag, mt, H2, W2, pos, dev, use_fp16, a.refine_iter, st)
+            except Exception as e:  # noqa: BLE001
+                line[key] = {"config": tag, "error": f"{type(e).__name__}: {str(e)[:300]}"}
+    if world == 1 and not a.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(a.model, a.height, a.width, a.refine_iter)
 
 
 if __name__ == "__main__":

@@ -78,12 +78,70 @@ def test_one_gpu_rank_through_rccl_gather_and_graph_replay():
     assert "RCCL gather" in d["config"]["parallelism"]
 
 
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_times_its_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain run (no --full): the contract's fields, no extra measurement after the timed region, and --dump-outputs writes the three
+    maps of the last timed step as float32 .npy files of the caller's shapes."""
+    r = _run(["--gpus", "1", "--steps", "4", "--warmup", "2", "--height", "256", "--width", "320", "--dump-outputs", str(tmp_path)], timeout=540)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["roofline"]["launches_timed"] == 4 and d["dtype"] == "f16" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "secondary", "roofline_attention", "forward", "gpu_state"):
+        assert k not in d, k
+    import numpy as np
+    for name in ("disp", "occ", "conf"):
+        x = np.load(tmp_path / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == (1, 1, 256, 320) and np.isfinite(x).all(), name
+
+
 @pytest.mark.timeout(120)
 def test_dry_single_rank_line():
     r = _run(["--dry", "--steps", "3", "--warmup", "0"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip())
     assert d["n_gpus"] == 1 and d["steps"] == 3
+
+
+@pytest.mark.timeout(300)
+def test_dry_dump_outputs_single_and_two_ranks(tmp_path):
+    """--dump-outputs on the CPU plumbing path: rank 0 writes what a caller receives -- its own maps, or on N > 1 the gathered maps of every
+    rank -- as float32 .npy files, and the same arguments write the same arrays."""
+    import numpy as np
+    for args, nb in ((["--steps", "3", "--warmup", "1"], 1), (["--gpus", "2", "--steps", "2", "--warmup", "1"], 2)):
+        got = []
+        for k in range(2):
+            out = tmp_path / f"{nb}_{k}"
+            r = _run(["--dry", *args, "--full", "--dump-outputs", str(out)])
+            assert r.returncode == 0, r.stderr[-2000:]
+            assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["steps"] == int(args[args.index("--steps") + 1])
+            got.append({n: np.load(out / f"{n}.npy") for n in ("disp", "occ", "conf")})
+        for n, x in got[0].items():
+            assert x.dtype == np.float32 and x.shape == (nb, 1, 32, 64) and np.array_equal(x, got[1][n]), n
+
+
+def test_dump_outputs_samples_above_the_size_limit(tmp_path):
+    """Outputs larger than the limit are stored as the same fixed, seeded sample of each array: within the limit, float32, identical from
+    run to run, and every stored value is an element of the full array."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    maps = [torch.randn(2, 1, 64, 96) for _ in range(3)]
+    small = bench.dump_outputs(maps, str(tmp_path / "all"))
+    assert small == {n: [2, 1, 64, 96] for n in ("disp", "occ", "conf")}
+    assert np.array_equal(np.load(tmp_path / "all" / "occ.npy"), maps[1].numpy())
+    limit = 40_000 + 3 * 4096
+    shapes = [bench.dump_outputs(maps, str(tmp_path / f"s{k}"), limit=limit) for k in range(2)]
+    assert shapes[0] == shapes[1] and all(len(s) == 1 and 0 < s[0] < 2 * 64 * 96 for s in shapes[0].values())
+    assert sum(os.path.getsize(tmp_path / "s0" / f"{n}.npy") for n in ("disp", "occ", "conf")) <= limit
+    for n, m in zip(("disp", "occ", "conf"), maps):
+        a, b = np.load(tmp_path / "s0" / f"{n}.npy"), np.load(tmp_path / "s1" / f"{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b) and np.isin(a, m.numpy().reshape(-1)).all()
 
 
 @pytest.mark.timeout(120)

@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 from oracle import s2m2_oracle as O
 from s2m2_amd.weights import seeded_state_dict, synthetic_pair
 
@@ -41,7 +42,7 @@ MARGIN = 1.5
 
 
 def _load(name):
-    g = np.load(os.path.join(HERE, "golden", FILES[name]))
+    g = golden_io.load(FILES[name])
     C, ntr, H, W, B, pos, ri, disparity, seed = [int(v) for v in g["cfg"]]
     return g, dict(C=C, ntr=ntr, H=H, W=W, B=B, pos=bool(pos), ri=ri, disparity=disparity, seed=seed, gain=float(g["gain"]), sub=int(g["sub"]),
                    sub0=int(g["sub0"]), cvsub=int(g["cvsub"]), shifts=tuple(int(v) for v in g["shifts"]), tok_seed=int(g["tok_seed"]))
@@ -303,7 +304,7 @@ def test_web0025_full_size_fp16_against_the_references_cpu_autocast_run():
     golden of the reference's CPU-autocast run of the same body, with the reference's fp32 run as the yardstick (tests/golden/make_golden_web_fp16.py)."""
     from s2m2_amd import utils
     from s2m2_amd.model import S2M2
-    g = np.load(os.path.join(HERE, "golden", "e2e_S_web0025_full_fp16_r3.npz"))
+    g = golden_io.load("e2e_S_web0025_full_fp16_r3.npz")
     C, ntr, H, W, _, pos, ri, _, seed = [int(v) for v in g["cfg"]]
     left = torch.from_numpy(g["left"]).permute(2, 0, 1)[None].cuda()
     right = torch.from_numpy(g["right"]).permute(2, 0, 1)[None].cuda()
@@ -333,7 +334,7 @@ def test_c5_fp32_refine_iter_3_against_the_reference():
     """BASELINE configs[4] at its own refine_iter (the r1 golden of make_golden_big.py covers DispInit; same weights and pair): the HIP fp32
     forward continued from the reference's disp0 / conf0 / occ0 vs the reference's fp32 maps after three refinement iterations."""
     g, c = _load("c5")
-    g1 = np.load(os.path.join(HERE, "golden", "e2e_XL_2432x2048_fp32_r1_neg_sub.npz"))
+    g1 = golden_io.load("e2e_XL_2432x2048_fp32_r1_neg_sub.npz")
     assert [int(v) for v in g1["cfg"]][:6] == [c["C"], c["ntr"], c["H"], c["W"], 1, 0] and [int(v) for v in g1["cfg"]][7:] == [c["disparity"], c["seed"]]
     assert float(g1["gain"]) == c["gain"]
     left, right = synthetic_pair(c["H"], c["W"], 1, c["disparity"], c["seed"])

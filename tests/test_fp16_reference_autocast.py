@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 from oracle import s2m2_oracle as O
 from s2m2_amd.weights import seeded_state_dict, synthetic_pair
 
@@ -34,7 +35,7 @@ def _stats(a, b):
 
 
 def _setup():
-    g = np.load(GOLD)
+    g = golden_io.load(GOLD)
     C, ntr, H, W, B, pos, ri, disparity, seed = [int(v) for v in g["cfg"]]
     sd = seeded_state_dict(C, 1, ntr, seed)
     left, right = synthetic_pair(H, W, B, disparity, seed)

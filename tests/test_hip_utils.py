@@ -74,9 +74,8 @@ def test_stem_mlp_matches_the_two_conv_layers(dtype):
 # ---- pinned to the reference's REAL functions (tests/golden/make_golden_utils.py imports image_pad / image_crop from the reference with a
 # stubbed cv2 and runs the body of run_stereo_matching on a window of the reference's own sample pair) ---------------------------------
 def _gold(name):
-    import os
-    import numpy as np
-    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name))
+    import golden_io
+    return golden_io.load(name)
 
 
 def test_image_pad_matches_the_reference_function():

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 from oracle import s2m2_oracle as O
 from s2m2_amd.weights import seeded_state_dict, synthetic_pair
 
@@ -28,7 +29,7 @@ ATOL, RTOL = 1e-3, 1e-4
 
 
 def _load(name):
-    g = np.load(os.path.join(HERE, "golden", FILES[name]))
+    g = golden_io.load(FILES[name])
     C, ntr, H, W, B, pos, ri, disparity, seed = [int(v) for v in g["cfg"]]
     return g, dict(C=C, ntr=ntr, H=H, W=W, B=B, pos=bool(pos), ri=ri, disparity=disparity, seed=seed, gain=float(g["gain"]),
                    sub=int(g["sub"]), fsub=int(g["fsub"]), cvsub=int(g["cvsub"]), gsub=int(g["gsub"]))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 from oracle import s2m2_oracle as O
 from s2m2_amd.weights import seeded_state_dict, synthetic_pair
 
@@ -16,7 +17,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "e2e_S
 
 
 def _setup():
-    g = np.load(GOLD)
+    g = golden_io.load(GOLD)
     C, ntr, H, W, B, pos, ri, disparity, seed = [int(v) for v in g["cfg"]]
     return g, seeded_state_dict(C, 1, ntr, seed), C, ntr, ri, bool(pos), synthetic_pair(H, W, B, disparity, seed), int(g["sub"])
 

@@ -19,7 +19,7 @@ if has smoke; then
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; echo "smoke rc=$?" >> $OUT/smoke.txt; tail -3 $OUT/smoke.txt
 fi
 if has bench; then
-  timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_N1.json 2> $OUT/bench_N1.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_N1.json 2> $OUT/bench_N1.err; echo "bench rc=$?"
   python - <<PY
 import json
 try:
@@ -68,7 +68,7 @@ if has configs; then
 fi
 if has prof; then
   cd /tmp
-  timeout 900 rocprofv3 --kernel-trace --stats -T -f csv -d $OUT/prof_bench -o bench -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/prof_bench.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -T -f csv -d $OUT/prof_bench -o bench -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/prof_bench.log 2>&1
   echo "rocprof bench rc=$?"
   timeout 300 rocprofv3 --kernel-trace --stats -T -f csv -d $OUT/prof_k1_c3 -o k1 -- python $R/tools/k1_only.py --case c3 > $OUT/prof_k1_c3.log 2>&1
   cd $R

@@ -9,6 +9,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import golden_io  # noqa: E402
 from s2m2_amd import hip  # noqa: E402
 
 
@@ -40,7 +42,7 @@ def main():
     total = 0
     gdir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
     for name in ("op_dispinit_pos", "op_dispinit_neg"):
-        g = np.load(os.path.join(gdir, name + ".npz"))
+        g = golden_io.load(os.path.join(gdir, name + ".npz"))
         cv = torch.from_numpy(g["cv"]).cuda()
         total += check(f"{name} {tuple(cv.shape)}", cv, bool(g["cfg"][4]), a.runs)
     gen = torch.Generator(device="cuda").manual_seed(0)
