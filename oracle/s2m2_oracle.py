@@ -17,6 +17,7 @@ vectors of its own).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
@@ -43,6 +44,23 @@ SD = Mapping[str, Tensor]
 # --------------------------------------------------------------------------------------------------
 class _Prec:
     half = False
+
+
+@contextlib.contextmanager
+def precision(mode: str):
+    """Run the module functions of this file in ``mode`` ("fp32" or "fp16", see above) inside the block; restores the previous mode.
+    ``forward(precision=...)`` does the same for a whole forward; this is for the module-level checks (tests/module_parity.py)."""
+    if mode not in ("fp32", "fp16"):
+        raise ValueError(mode)
+    old = _Prec.half
+    _Prec.half = mode == "fp16"
+    try:
+        yield
+    finally:
+        _Prec.half = old
+
+
+_precision = precision          # (forward()'s argument of the same name shadows it there)
 
 
 def _q(x: Tensor) -> Tensor:
@@ -510,14 +528,8 @@ def forward(sd: SD, img0: Tensor, img1: Tensor, use_positivity: bool = False, re
     reference's autocast deployment mode, see the precision note at the top of this file).  ``inject`` (parity tests only):
     {"feature_tr_4x": (2B,C,h,w)} replaces the transformer output before DispInit, like the product's Engine ``inject`` hook -- used to
     run both sides from synthetic features with sharp, unambiguous matches."""
-    if precision not in ("fp32", "fp16"):
-        raise ValueError(precision)
-    old = _Prec.half
-    _Prec.half = precision == "fp16"
-    try:
+    with _precision(precision):
         return _forward(sd, img0, img1, use_positivity, refine_iter, output_upsample, capture, inject)
-    finally:
-        _Prec.half = old
 
 
 def _forward(sd: SD, img0: Tensor, img1: Tensor, use_positivity: bool, refine_iter: int, output_upsample: bool,

@@ -751,14 +751,9 @@ class Engine:
         return self.cconv(s2, [y])
 
     # ---- whole forward, in three stages (bench.py brackets the middle one, K1, with HIP events) ----------
-    @torch.no_grad()
-    def features(self, img0: Tensor, img1: Tensor, x8: Optional[Tensor] = None):
-        """normalise -> CNN backbone -> feature pyramid -> multi-resolution transformer (s2m2.py:140-150).  ``x8``: the normalised 8-channel
-        image tensor when the caller has already run hip.image_prep (GraphRunner: eagerly, straight from the caller's images)."""
-        B = img0.shape[0]
-        if x8 is None:
-            x8 = hip.image_prep(img0, img1, self.dtype)                         # (2B,H,W,8): channels 1..3 = normalised RGB, 0 free
-        p = "cnn_backbone"                                                      # CNNEncoder (submodules.py:63-93)
+    def cnn_encoder(self, x8: Tensor) -> Tuple[Tensor, Tensor]:
+        """CNNEncoder (submodules.py:63-93) on the (2B,H,W,8) normalised image tensor -> (1/4 features f4, 1/2 features f2)."""
+        p = "cnn_backbone"
         c0, c2 = self._conv0(), self.std(p + ".conv0.2")
         if tuple(c0[0].shape) == (16, 8) and tuple(c2[0].shape) == (16, 16) and c0[2] == 1 and c2[2] == 1:
             st = self._packed.get("stem|fp32")                                  # conv0 = 1x1 - GELU - 1x1 per pixel on the VALU (K8)
@@ -774,6 +769,16 @@ class Engine:
         t = self.cconv(self.std(p + ".conv2.0"), [f2], act=hip.ACT_GELU)
         f2 = self.cconv(self.std(p + ".conv2.2"), [t], epi=hip.EPI_ADD, aux0=f2)
         f4 = self.cconv(self.std(p + ".conv2_down.0", frag=False), [f2], stride=2)
+        return f4, f2
+
+    @torch.no_grad()
+    def features(self, img0: Tensor, img1: Tensor, x8: Optional[Tensor] = None):
+        """normalise -> CNN backbone -> feature pyramid -> multi-resolution transformer (s2m2.py:140-150).  ``x8``: the normalised 8-channel
+        image tensor when the caller has already run hip.image_prep (GraphRunner: eagerly, straight from the caller's images)."""
+        B = img0.shape[0]
+        if x8 is None:
+            x8 = hip.image_prep(img0, img1, self.dtype)                         # (2B,H,W,8): channels 1..3 = normalised RGB, 0 free
+        f4, f2 = self.cnn_encoder(x8)
         py = self.unet("feat_pyramid", f4)
         z = py
         # DispInit's LayerNorm (submodules.py:165,216) is folded into the launch that writes feature_tr_4x -- the last K9 chain of the

@@ -34,6 +34,11 @@ def test_ln_corr_vs_reference_golden(hip, name, dtype):
     assert err < (3e-4 if dtype == torch.float32 else 0.35), err
 
 
+# pixels of each fixture that the tie exclusion below leaves out: (not 'sure', of them exact ties top1 == top2).  Pinned so that a
+# regenerated fixture or a looser gap cannot quietly exclude more pixels than the committed ones do.
+NOT_SURE = {"op_dispinit_pos": (17, 5), "op_dispinit_neg": (1, 1), "e2e_S_64x96_pos_r2": (0, 0), "e2e_S_96x160_neg_r1_b2": (0, 0)}
+
+
 @pytest.mark.parametrize("name", ["op_dispinit_pos", "op_dispinit_neg", "e2e_S_64x96_pos_r2", "e2e_S_96x160_neg_r1_b2"])
 def test_sinkhorn_regress_vs_reference_golden(hip, name):
     g = load_golden(name + ".npz")
@@ -47,6 +52,7 @@ def test_sinkhorn_regress_vs_reference_golden(hip, name):
     # 1.4 -- a coincidence of its rounding, which any other summation order resolves either way; ties between identical scores are pinned by
     # test_sinkhorn_first_maximum_wins_on_exact_ties)
     sure = T((top1 - top2) > 1e-4 * top1)
+    assert (int((~sure).sum()), int((top1 == top2).sum())) == NOT_SURE[name], (int((~sure).sum()), int((top1 == top2).sum()), sure.numel())
     same = am == T(g["argmax"])
     assert bool(same[sure].all()), f"{int((~same[sure]).sum())} argmax mismatches on well separated pixels"
     assert float(sure.float().mean()) > 0.97

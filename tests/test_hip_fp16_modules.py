@@ -1,0 +1,488 @@
+"""Every fp16 module form of the engine against the oracle, teacher-forced at the module's own boundary (tests/module_parity.py).
+
+The benchmarked mode is fp16, and in fp16 the engine runs kernel forms that the fp32 every-stage tests never dispatch: the direct K9 / K10
+forms, the fragment-stream K5, K13 row attention, K14 ConvBlock, the merged GRU gates, the pooled / fan-out K9 launches, the coarse-level
+fusions and the fusion_up tails.  Here each engine module method -- conv_block, fusion, fusion_up, attn_block (1-D and 2-D, with and without
+PE), unet, mrt (with the LayerNorm output of the last one), gru, cnn_encoder -- runs on fp16 inputs and fp16-rounded weights and is judged
+against the oracle in fp32 with the oracle's fp16 autocast emulation as the yardstick (``judge``).  Module instances come from the
+state_dict keys; configurations:
+
+* S (C = 128) at the widths of 1216 x 1024 (304 .. 38), inputs = the oracle's own tensors at each module boundary of a forward on
+  ``synthetic_pair`` (regime a), plus peaked attention (b) and offset tokens (c) on the 1-D and 2-D blocks, and a w = 300 row;
+* S at the widths of 640 x 480 (160 .. 20), seeded inputs, peaked attention and offset tokens;
+* M (C = 192) at the widths of 640 x 480, natural inputs;
+* L (C = 256) at the 1216 x 1024 widths and XL (C = 384) at the 2432 x 2048 widths, seeded inputs;
+  every configuration at full row width and a cropped height (CONFIGS).
+
+test_dispatch_coverage_* then records every (entry point, form signature) of one eager fp16 forward per configuration and asserts that the
+module cases reach each one that is not listed in EXCLUDED; test_switch_* re-runs the affected cases with each A/B switch flipped.
+Measured errors per case: profiles/r07/fp16_modules.txt (S2M2_FP16_MODULES_TABLE=<path> writes the table).
+"""
+import collections
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import module_parity as MP
+from oracle import s2m2_oracle as O
+from s2m2_amd import hip as hip_mod
+from s2m2_amd.spec import MODEL_CONFIGS
+from s2m2_amd.weights import seeded_state_dict, synthetic_pair
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# name: (model, image H, W, rows kept at the 1/4 grid, natural inputs).  The full row width of every level is kept (it drives the tiling);
+# the height is cropped to what the CPU oracle affords (the natural inputs come from a forward on a 4 * rows tall image).  S1216 keeps 72
+# rows so that its 1/4-level ConvBlocks stay above K14's 40 000-pixel limit, as in the full-size forward (the three-launch form).
+CONFIGS = {
+    "S1216": ("S", 1024, 1216, 72, True),
+    "S640": ("S", 480, 640, 64, False),
+    "M640": ("M", 480, 640, 32, True),
+    "L1216": ("L", 1024, 1216, 16, False),
+    "XL2432": ("XL", 2048, 2432, 16, False),
+}
+
+
+# ---- dispatch recording ----------------------------------------------------------------------------------------------------------------
+# Module scopes: a launch made (directly or not) from one of these Engine methods belongs to a module case.  Every other launch of the
+# forward is made from one of the scopes of EXCLUDED, each covered by the test file named there.
+MODULE_SCOPES = {"cnn_encoder", "conv_block", "fusion", "fusion_up", "attn_block", "unet", "mrt", "gru"}
+EXCLUDED = {
+    "features": "tests/test_hip_e2e.py, test_hip_pw.py (image_prep)",
+    "cost_volume": "tests/test_hip_dispinit.py (corr / ln_corr)",
+    "_normed_like_the_forward": "tests/test_hip_parity_baseline.py (injected feature_tr_4x)",
+    "finish": "tests/test_hip_dispinit.py (sinkhorn_regress), test_hip_norm_upsample.py (convex_upsample, tanh), test_hip_parity_baseline.py (ctx_feat, feat_fusion_layer is a module case)",
+    "global_refiner": "tests/test_hip_parity_baseline.py, test_fp16_headline.py (refine_prep, init_feat, out_feat, global_update)",
+    "local_refiner": "tests/test_hip_dispinit.py (cv_lookup_into), test_hip_conv_narrow.py, test_hip_pw.py, test_fp16_headline.py (corr / disp / update heads, refine_prep, refine_update)",
+    "mask4x": "tests/test_hip_norm_upsample.py, test_hip_parity_baseline.py (UpsampleMask4x)",
+    "mask1x": "tests/test_hip_conv_narrow.py, test_hip_parity_baseline.py (UpsampleMask1x, K12 head)",
+}
+
+
+def _c(t):
+    return int(t.shape[-1]) if torch.is_tensor(t) else None
+
+
+def signature(name, a, k):
+    """(entry point, channel widths, form flags): no spatial size, so a cropped case reaches the same signature as the full forward"""
+    g = lambda i, key, d=None: a[i] if len(a) > i else k.get(key, d)          # noqa: E731
+    if name == "conv2d":
+        srcs = a[0] if isinstance(a[0], (list, tuple)) else [a[0]]
+        return (name, tuple(_c(s) for s in srcs), g(5, "Cout"), (g(3, "KH"), g(4, "KW")), k.get("stride", 1), k.get("act", 0),
+                k.get("epi", 0), k.get("korder", 0), bool(k.get("pool2")), k.get("ln_wsum") is not None, bool(k.get("shuffle2")),
+                bool(k.get("epi_cout0")), bool(k.get("ksplit")))
+    if name == "mlp_chain":
+        st = a[1]
+        return (name, _c(a[0]), tuple((s[2], s[1] is not None, s[3] is not None) for s in st), k.get("res_stage", -1), bool(k.get("carry")),
+                k.get("ln_out") is not None, (k["fan"][0].shape[0] // _c(a[0]), k["fan"][2] is not None) if k.get("fan") else None,
+                bool(k.get("frag")), bool(k.get("pool2")))
+    if name == "mlp_fan":
+        return (name, _c(a[0]), a[1].shape[0] // _c(a[0]), g(3, "ln_wsum") is not None, bool(k.get("pool2")))
+    if name == "row_attn":
+        return (name, _c(a[0]), a[1], bool(a[2]), k.get("ln_out_eps") is not None)
+    if name == "feature_fusion":
+        return (name, _c(a[0]), bool(k.get("z1_coarse")), bool(k.get("frag")))
+    if name == "attention":
+        return (name, _c(a[0]), a[3], bool(k.get("swap_halves")), k.get("pe") is not None)
+    if name in ("pw_direct", "conv_narrow"):
+        srcs = a[0] if isinstance(a[0], (list, tuple)) else [a[0]]
+        return (name, tuple(_c(s) for s in srcs), a[3] if name == "pw_direct" else (a[3], a[4], a[5]), k.get("act", 0), k.get("stride", 1),
+                bool(k.get("shuffle2")), k.get("head") is not None)
+    return (name,) + tuple(_c(t) for t in a if torch.is_tensor(t)) + tuple(sorted((kk, v) for kk, v in k.items() if isinstance(v, (int, bool))))
+
+
+class Recorder:
+    """engine.hip proxy (in the style of tools/layer_trace.py's Tracer): records (scope, signature) of every launch"""
+    SKIP = {"load"}
+
+    def __init__(self, real):
+        self.real, self.log = real, collections.Counter()
+
+    def __getattr__(self, name):
+        f = getattr(self.real, name)
+        if not callable(f) or name.startswith("_") or name[0].isupper() or name in self.SKIP or name.endswith("_supported"):
+            return f
+
+        def wrapped(*a, **k):
+            self.log[(_scope(), signature(name, a, k))] += 1
+            return f(*a, **k)
+        return wrapped
+
+
+def _scope():
+    """'module' if an Engine module method is on the stack, else the innermost EXCLUDED scope on it (else the innermost Engine method)"""
+    inner = first = None
+    fr = sys._getframe(2)
+    while fr is not None:
+        if os.path.basename(fr.f_code.co_filename) == "engine.py":
+            name = fr.f_code.co_name
+            if name in MODULE_SCOPES:
+                return "module"
+            first = first or name
+            if name in EXCLUDED:
+                inner = inner or name
+        fr = fr.f_back
+    return inner or first or "?"
+
+
+@pytest.fixture
+def recorder(monkeypatch):
+    import s2m2_amd.engine as engine_mod
+    rec = Recorder(hip_mod)
+    monkeypatch.setattr(engine_mod, "hip", rec)
+    return rec
+
+
+# ---- models, engines, inputs -----------------------------------------------------------------------------------------------------------
+_SD, _NAT, _ORACLE = {}, {}, {}
+TABLE = []
+
+
+def _threads():
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+
+
+def state(cfg):
+    model = CONFIGS[cfg][0]
+    if model not in _SD:
+        c, ntr = MODEL_CONFIGS[model]
+        _SD[model] = MP.sd16(seeded_state_dict(c, 1, ntr, 0))
+    return _SD[model]
+
+
+def engine(cfg, sd=None):
+    from s2m2_amd.engine import Engine
+    from s2m2_amd.model import S2M2
+    c, ntr = MODEL_CONFIGS[CONFIGS[cfg][0]]
+    m = S2M2(c, 1, ntr, use_positivity=True, refine_iter=1)
+    m.load_state_dict(sd if sd is not None else state(cfg), strict=True)
+    return Engine(m.cuda().eval(), torch.float16)
+
+
+def images(cfg):
+    _, H, W, rows, _ = CONFIGS[cfg]
+    if rows is not None:
+        H = 4 * rows
+    left, right = synthetic_pair(H, W, 1, 32, 0)
+    return torch.cat([(left / 255.0 - 0.5) * 2, (right / 255.0 - 0.5) * 2], 0)
+
+
+def natural(cfg):
+    """the oracle's fp32 module inputs of a trunk forward (regime a), rounded to fp16"""
+    if cfg not in _NAT:
+        _threads()
+        c, ntr = MODEL_CONFIGS[CONFIGS[cfg][0]]
+        got = MP.capture_boundaries(state(cfg), MP.round16(images(cfg)), ntr)
+        _NAT[cfg] = {p: tuple(MP.round16(t) for t in a) for p, a in got.items()}
+    return _NAT[cfg]
+
+
+def level_grid(cfg, lvl):
+    _, H, W, rows, _ = CONFIGS[cfg]
+    h, w = H // 4 >> lvl, W // 4 >> lvl
+    if rows is not None:
+        h = max(2, rows >> lvl)
+    return h, w
+
+
+# ---- cases -----------------------------------------------------------------------------------------------------------------------------
+class Case:
+    """one module instance on one input: ``oracle(sd, *x)`` -> NCHW tuple, ``run(eng, *x_nhwc_fp16)`` -> NHWC tuple"""
+
+    def __init__(self, cfg, kind, prefix, shapes, oracle, run, regime="seeded", nat_key=None, sd_edit=None, seed=0, form=None):
+        self.cfg, self.kind, self.prefix, self.shapes, self.oracle, self.run = cfg, kind, prefix, shapes, oracle, run
+        self.regime, self.nat_key, self.sd_edit, self.seed, self.form = regime, nat_key, sd_edit, seed, form
+
+    @property
+    def id(self):
+        return f"{self.cfg}-{self.kind}-{self.prefix}-{self.regime}" + ("-w%d" % self.shapes[0][3] if self.kind == "basic" else "")
+
+    def inputs(self):
+        if self.regime == "natural":
+            if isinstance(self.nat_key, list):                       # [(module prefix, argument index), ...]
+                return tuple(natural(self.cfg)[k][i] for k, i in self.nat_key)
+            return natural(self.cfg)[self.nat_key]
+        if self.regime == "image":
+            return (MP.round16(images(self.cfg)),)
+        out = []
+        for i, s in enumerate(self.shapes):
+            if self.regime == "offset":
+                out.append(MP.offset_tokens(s, self.seed + i))
+            elif self.regime == "peaked":
+                out.append(MP.peaked_pair(s, self.seed + i, s[3] // 2))
+            elif self.regime == "tanh":
+                out.append(MP.round16(torch.tanh(MP.seeded(s, self.seed + i))))
+            else:
+                out.append(MP.seeded(s, self.seed + i))
+        return tuple(out)
+
+    def sd(self):
+        sd = state(self.cfg)
+        return self.sd_edit(sd) if self.sd_edit else sd
+
+
+def _ln_pair(y32, y16e, sd):
+    g, b = sd["disp_init.layer_norm.weight"], sd["disp_init.layer_norm.bias"]
+    ln = lambda t: torch.nn.functional.layer_norm(MP.nhwc(t), (t.shape[1],), g, b, 1e-5)     # noqa: E731
+    return MP.nchw(ln(y32)), MP.nchw(MP.round16(ln(y16e)))
+
+
+def cases(cfg):
+    model, H, W, rows, nat = CONFIGS[cfg]
+    sd = state(cfg)
+    c, ntr = MODEL_CONFIGS[model]
+    keys = set(sd)
+    nb = 2
+    out = []
+    lvl = lambda p: int(p[-1])                                                   # noqa: E731
+    tr0, trl = "transformer.uformer_list.0", f"transformer.uformer_list.{ntr - 1}"
+    unets = {"feat_pyramid": 2, "global_refiner.refine_unet": 1, "refiner.refine_unet": 1}
+
+    def reg(p):
+        return "natural" if nat and p in natural_keys else "seeded"
+    natural_keys = set(natural(cfg)) if nat else set()
+
+    # CNN encoder
+    x = images(cfg)
+    out.append(Case(cfg, "encoder", "cnn_backbone", [tuple(x.shape)],
+                    lambda sd_, x_: O.cnn_encoder(sd_, "cnn_backbone", x_),
+                    lambda e, x_: e.cnn_encoder(torch.nn.functional.pad(x_, (1, 4)).contiguous()),          # RGB in channels 1..3 of 8
+                    regime="natural" if nat else "image", nat_key="cnn_backbone"))
+    # ConvBlock2D
+    for u, n in unets.items():
+        for e_d in ("enc", "dec"):
+            for i in range(3):
+                p = f"{u}.{e_d}{i}"
+                cin = sd[p + ".convs.0.weight"].shape[1]
+                h, w = level_grid(cfg, i)
+                out.append(Case(cfg, "convblock", p, [(n, cin, h, w)], lambda sd_, z, p=p: (O.conv_block(sd_, p, z),),
+                                lambda e, z, p=p: (e.conv_block(p, z),), regime=reg(p) if u == "feat_pyramid" else "seeded", nat_key=p))
+    # FeatureFusion: fusion, and fusion_up for the decoders
+    fus = [(f"feat_pyramid.concat_conv{i}", i, 2) for i in range(3)] + [(f"{u}.concat_conv{i}", i, 1) for u in list(unets)[1:] for i in range(3)]
+    fus += [(f"{tr0}.down_concat{i}", i, 2) for i in (1, 2, 3)] + [(f"{tr0}.up_concat{i}", i, 2) for i in range(3)] + [("feat_fusion_layer", 0, 1)]
+    for p, lv, n in fus:
+        cc = sd[p + ".feature_gate.0.weight"].shape[0]
+        h, w = level_grid(cfg, min(lv, 3))
+        out.append(Case(cfg, "fusion", p, [(n, cc, h, w), (n, cc, h, w)], lambda sd_, a, b, p=p: (O.feature_fusion(sd_, p, a, b),),
+                        lambda e, a, b, p=p: (e.fusion(p, a, b),), regime=reg(p), nat_key=p, seed=lv))
+        if "concat_conv" in p or "up_concat" in p:
+            pu = p.replace("concat_conv", "up_conv").replace("up_concat", "up_conv")
+            cx = sd[pu + ".1.weight"].shape[1]
+            hc, wc = level_grid(cfg, lv + 1)
+            out.append(Case(cfg, "fusion_up", p, [(n, cc, 2 * hc, 2 * wc), (n, cx, hc, wc)],
+                            lambda sd_, a, b, p=p, pu=pu: (O.feature_fusion(sd_, p, a, O._up(sd_, pu, b)),),
+                            lambda e, a, b, p=p, pu=pu: (e.fusion_up(p, a, pu, b),), seed=lv,
+                            regime="natural" if (p in natural_keys and pu in natural_keys) else "seeded", nat_key=[(p, 0), (pu, 0)]))
+    # BasicAttnBlock (1-D): natural / seeded, peaked, offset
+    for e_d in ("enc", "dec"):
+        for i in range(3):
+            p = f"{tr0}.{e_d}_attn{i}"
+            nh = 2 ** i
+            cc = sd[p + ".ffn.ffn.0.weight"].shape[1]
+            h, w = level_grid(cfg, i)
+            o = lambda sd_, z, p=p, nh=nh: (O.basic_attn_block(sd_, p, z, nh),)             # noqa: E731
+            r = lambda e, z, p=p, nh=nh: (e.attn_block(p, z, nh, False)[0],)                 # noqa: E731
+            out.append(Case(cfg, "basic", p, [(nb, cc, h, w)], o, r, regime=reg(p), nat_key=p))
+            if e_d == "enc" and c == 128:
+                hs = min(h, 8)
+                out.append(Case(cfg, "basic", p, [(nb, cc, hs, w)], o, r, regime="offset", seed=10 + i))
+                out.append(Case(cfg, "basic", p, [(nb, cc, hs, w)], o, r, regime="peaked", seed=20 + i,
+                                sd_edit=lambda s, p=p: MP.peaked_sd(s, p)))
+    if c == 128 and W // 4 >= 304:
+        p = f"{tr0}.enc_attn0"                                        # K13's last partial 32-token tile and second key chunk
+        out.append(Case(cfg, "basic", p, [(nb, c, 4, 300)], lambda sd_, z, p=p: (O.basic_attn_block(sd_, p, z, 1),),
+                        lambda e, z, p=p: (e.attn_block(p, z, 1, False)[0],), seed=30))
+    # GlobalAttnBlock (2-D), 8 heads
+    glob = [(f"feat_pyramid.{s}.{i}", 2) for s in ("enc3s", "dec3s") for i in range(2) if f"feat_pyramid.{s}.{i}.ffn.ffn.0.weight" in keys]
+    glob += [(f"{u}.{s}.0", 1) for u in list(unets)[1:] for s in ("enc3s", "dec3s")]
+    glob += [(f"{tr0}.{s}.{i}", 2) for s in ("enc_attn3s", "dec_attn3s") for i in range(2)]
+    for p, n in glob:
+        cc = sd[p + ".ffn.ffn.0.weight"].shape[1]
+        h, w = level_grid(cfg, 3)
+        pe = (p + ".self_attn.attn.pe_proj.weight") in keys
+        out.append(Case(cfg, "global", p, [(n, cc, h, w)],
+                        lambda sd_, z, p=p, pe=pe: (O.global_attn_block(sd_, p, z, 8, O.dense_pe(z.shape[2], z.shape[3]) if pe else None),),
+                        lambda e, z, p=p, pe=pe: (e.attn_block(p, z, 8, True, pe)[0],), regime=reg(p) if n == 2 else "seeded", nat_key=p))
+        if c == 128 and (p.endswith("enc3s.0") or p.endswith("enc_attn3s.0")):
+            out.append(Case(cfg, "global", p, [(n, cc, h, w)], out[-1].oracle, out[-1].run, regime="offset", seed=40))
+    # whole U-Nets and MRTs (the chained forms: qkv_in / next_block / tail, COARSE_FUSE's pooled fan-out, fusion_up's up_pre)
+    for u, n in unets.items():
+        cin = sd[u + ".enc0.convs.0.weight"].shape[1]
+        h, w = level_grid(cfg, 0)
+        out.append(Case(cfg, "unet", u, [(n, cin, h, w)], lambda sd_, z, u=u: O.unet(sd_, u, z), lambda e, z, u=u: e.unet(u, z),
+                        regime=reg(u) if u == "feat_pyramid" else "seeded", nat_key=u))
+    shp = [(nb, sd[f"{trl}.enc_attn{i}.ffn.ffn.0.weight"].shape[1]) + level_grid(cfg, i) for i in range(3)]
+    shp.append((nb, shp[2][1]) + level_grid(cfg, 3))
+
+    out.append(Case(cfg, "mrt", trl, shp, lambda sd_, *z: O.mrt(sd_, trl, *z), lambda e, *z: _mrt_ln(e, trl, z), regime=reg(trl), nat_key=trl))
+    # ConvGRU: h = tanh(ctx) in (-1, 1), x = the refiner U-Net's output
+    h, w = level_grid(cfg, 0)
+    out.append(Case(cfg, "gru", "refiner.gru", [(1, c, h, w), (1, c, h, w)], lambda sd_, hh, xx: (O.conv_gru(sd_, "refiner.gru", hh, xx),),
+                    lambda e, hh, xx: (e.gru("refiner.gru", hh, xx),), regime="tanh", seed=50))
+    return out
+
+
+def _mrt_ln(e, p, z):
+    r = e.mrt(p, *z, ln_out=(e.ln_w, e.ln_b, 1e-5))
+    return tuple(r) + ((e._tokens_normed,) if e._tokens_normed is not None else ())
+
+
+SWITCH_KINDS = set()            # (cfg, kind) re-run by test_switch: their oracle outputs are kept
+
+
+def oracle_outputs(case, xs):
+    key = case.id
+    if key not in _ORACLE:
+        _threads()
+        sd = case.sd()
+        y32, y16e = MP.oracle_pair(lambda: case.oracle(sd, *xs))
+        y32, y16e = tuple(y32) if isinstance(y32, (tuple, list)) else (y32,), tuple(y16e) if isinstance(y16e, (tuple, list)) else (y16e,)
+        if case.kind == "mrt":                                           # + DispInit's LayerNorm of the last transformer's output
+            a, b = _ln_pair(y32[0], y16e[0], sd)
+            y32, y16e = y32 + (a,), y16e + (b,)
+        if (case.cfg, case.kind) not in SWITCH_KINDS:
+            return y32, y16e
+        _ORACLE[key] = (y32, y16e)
+    return _ORACLE[key]
+
+
+def run_case(case, eng, table=True):
+    xs = case.inputs()
+    y32, y16e = oracle_outputs(case, xs)
+    xh = [MP.nhwc(x).to("cuda", torch.float16) for x in xs]
+    with torch.no_grad():
+        yh = case.run(eng, *xh)
+    torch.cuda.synchronize()
+    assert len(yh) == len(y32), (case.id, len(yh), len(y32))
+    msgs = []
+    for k, (a, b, d) in enumerate(zip(yh, y32, y16e)):
+        v = MP.judge(a, MP.nhwc(b), MP.nhwc(d), f"{case.id}[{k}]")
+        if table:
+            TABLE.append(f"{case.id}[{k}]  {v.row()}  {'ok' if v.ok else 'FAIL'}")
+        if not v.ok:
+            msgs.append(v.msg)
+    return msgs
+
+
+_ENG = {}
+
+
+def _engine_for(case):
+    if case.sd_edit is not None:
+        return engine(case.cfg, case.sd())
+    if case.cfg not in _ENG:
+        _ENG.clear()
+        _ENG[case.cfg] = engine(case.cfg)
+    return _ENG[case.cfg]
+
+
+@pytest.mark.parametrize("cfg", list(CONFIGS))
+def test_fp16_modules(cfg):
+    """every module case of one configuration; all failures of the configuration are reported together"""
+    fails = []
+    for case in cases(cfg):
+        fails += run_case(case, _engine_for(case))
+    _write_table()
+    assert not fails, "\n".join(fails)
+
+
+def _write_table():
+    path = os.environ.get("S2M2_FP16_MODULES_TABLE")
+    if path:
+        with open(path, "w") as f:
+            f.write("# |yh - y32| (hip) and |y16e - y32| (emu) per module case; ulp>4: fraction beyond 4 fp16 ulps of |y32|\n")
+            f.write("\n".join(TABLE) + "\n")
+
+
+# ---- dispatch coverage -----------------------------------------------------------------------------------------------------------------
+def _forward_signatures(cfg, recorder, monkeypatch):
+    monkeypatch.setenv("S2M2_REFINE_NATIVE", "0")
+    _, H, W, _, _ = CONFIGS[cfg]
+    eng = engine(cfg)
+    left, right = synthetic_pair(H, W, 1, 32, 0)
+    recorder.log.clear()
+    eng.run(left.cuda(), right.cuda())
+    torch.cuda.synchronize()
+    return collections.Counter(recorder.log)
+
+
+def _case_signatures(cfg, recorder, kinds=None):
+    eng = engine(cfg)
+    recorder.log.clear()
+    for case in cases(cfg):
+        if kinds is not None and case.kind not in kinds:
+            continue
+        xh = [torch.randn([s[0], s[2], s[3], s[1]], device="cuda").half() for s in case.shapes]
+        with torch.no_grad():
+            case.run(eng, *xh)
+    torch.cuda.synchronize()
+    return {sig for (scope, sig) in recorder.log}
+
+
+def uncovered(cfg, recorder, monkeypatch, kinds=None):
+    fwd = _forward_signatures(cfg, recorder, monkeypatch)
+    reached = _case_signatures(cfg, recorder, kinds)
+    missing, unknown = set(), set()
+    for scope, sig in fwd:
+        if scope == "module":
+            if sig not in reached:
+                missing.add(sig)
+        elif scope not in EXCLUDED:
+            unknown.add((scope, sig))
+    return missing, unknown
+
+
+@pytest.mark.parametrize("cfg", list(CONFIGS))
+def test_dispatch_coverage(cfg, recorder, monkeypatch):
+    """every (entry point, form) that a module of the eager fp16 forward launches is launched by this configuration's module cases; every
+    other launch comes from a scope of EXCLUDED"""
+    missing, unknown = uncovered(cfg, recorder, monkeypatch)
+    assert not unknown, f"launches from scopes neither module nor EXCLUDED: {sorted(unknown, key=str)}"
+    assert not missing, f"forms of the forward no module case reaches: {sorted(missing, key=str)}"
+
+
+def test_dispatch_coverage_notices_a_missing_kind(recorder, monkeypatch):
+    """the coverage check has teeth: without the BasicAttnBlock cases, K13 (row_attn) is reported"""
+    kinds = {"encoder", "convblock", "fusion", "fusion_up", "global", "unet", "gru"}
+    missing, _ = uncovered("S640", recorder, monkeypatch, kinds)
+    assert any(sig[0] == "row_attn" for sig in missing), missing
+
+
+# ---- A/B switches ----------------------------------------------------------------------------------------------------------------------
+SWITCHES = [
+    ("S2M2_ROWFUSE", "0", "S1216", {"basic"}),
+    ("S2M2_CONVBLOCK", "0", "S1216", {"convblock"}),
+    ("S2M2_CONVBLOCK_C256", "1", "L1216", {"convblock"}),
+    ("S2M2_COARSE_FUSE", "0", "S640", {"unet", "mrt"}),
+    ("S2M2_GRU_FRAG", "1", "S640", {"gru"}),
+    ("S2M2_K12", "0", "S640", {"encoder"}),
+]
+
+
+SWITCH_KINDS.update((cfg, k) for _, _, cfg, kinds in SWITCHES for k in kinds)
+
+
+@pytest.mark.parametrize("var,val,cfg,kinds", SWITCHES, ids=[f"{v}={x}" for v, x, _, _ in SWITCHES])
+def test_switch(var, val, cfg, kinds, monkeypatch):
+    monkeypatch.setenv(var, val)
+    eng = engine(cfg)
+    fails = []
+    for case in cases(cfg):
+        if case.kind in kinds:
+            fails += run_case(case, engine(cfg, case.sd()) if case.sd_edit else eng, table=False)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("var", ["S2M2_CHAIN_FRAG512", "S2M2_FUSION_FRAG512"])
+def test_switch_frag512_in_a_child(var):
+    """read once per process by the library (static const): the L cases at C = 512 in a fresh child process"""
+    env = dict(os.environ, **{var: "0"})
+    env.pop("S2M2_FP16_MODULES_TABLE", None)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-p", "no:cacheprovider",
+                        "-k", "test_fp16_modules and L1216"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
