@@ -37,8 +37,9 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * points s2m2_corr_tiled / s2m2_corr_hybrid / s2m2_debug_store_pattern and the ln_out_tile* fields of s2m2_chain_desc removed;
  * head_* appended to s2m2_narrow_desc without a bump -- the reason for the exact comparison since 500); 500 = round 5; 600 = round 6
  * (s2m2_row_attn and s2m2_conv_block added; the five ABI-400 entry points of K1 -- s2m2_ln_corr, _timed, _banded, _pitched, s2m2_corr -- removed: every form of
- * K1 is s2m2_cost_volume). */
-#define S2M2_ABI_VERSION 600
+ * K1 is s2m2_cost_volume); 700 (engine files: s2m2_plan_save, s2m2_engine_*, s2m2_engine_region, s2m2_engine_info added; nothing changed
+ * in place). */
+#define S2M2_ABI_VERSION 700
 int s2m2_version(void);
 const char* s2m2_last_error(void);
 /* test aid (not part of the path): fills the LDS of every CU with quiet-NaN patterns, so that a kernel launched next that reads an LDS word it
@@ -148,6 +149,53 @@ int s2m2_plan_run(const s2m2_plan* plan, const void* const* ext_ptrs, int next, 
 int s2m2_plan_destroy(s2m2_plan* plan);
 int s2m2_refine_step(const s2m2_plan* step, const void* hidden, const void* ctx, const void* disp, const void* conf, const void* occ,
                      const void* cv, const void* side_input, void* stream);
+
+/*
+ * Engine files (ABI 700): one whole forward as a self-contained file, loaded and run with nothing but this library and the HIP runtime.
+ *
+ * s2m2_plan_save writes a sealed plan (recorded with next = 0) together with the device memory its calls point to.  The caller describes that
+ * memory as `nregions` disjoint ranges [base, base + bytes):
+ *   S2M2_REGION_CONTENT   the bytes are stored (read from the device here: the caller synchronises first); an all-zero range is stored as its
+ *                         size only, a range no recorded call points into as its size only and is never allocated by the loader
+ *   S2M2_REGION_SCRATCH   only the size is stored; the loader allocates it zero-filled
+ *   S2M2_REGION_EXTERNAL  an input slot: the first external is the left image, the second the right one, (B,3,H,W) of meta->image_dtype.
+ *                         Only the first call (s2m2_image_prep) may point into an external
+ * Every pointer word of every call (the pointer mask of the plan) is stored as (region, offset) or as null; a non-null pointer word that falls
+ * in no region fails the save with the call, its entry point and the word.  The impl pointer of a call is stored as its entry point's name and
+ * mapped back by the loader through the library's table of recordable entry points (name, blob size).  meta->out_region / out_offset name the
+ * (3, B, 1, out_h, out_w) fp32 result (disp, occ, conf).
+ *
+ * s2m2_engine_load validates the whole file on the host before any device call (magic, format version, S2M2_ABI_VERSION equal to the
+ * library's, entry names and blob sizes, every pointer inside its region, region sizes against the file length), then checks that the
+ * current device is a gfx950, allocates the regions (every region 4096-byte aligned) on it, uploads the content and zeroes the scratch.
+ * s2m2_engine_run: left / right (B,3,H,W) in meta.image_dtype, disp / occ / conf (B,1,out_h,out_w) fp32, all device buffers of the caller
+ * on the engine's device.  The first call (image prep) is issued eagerly from the caller's images; the rest runs eagerly on the first run,
+ * is captured as a hipGraph on the second and replayed from then on (S2M2_GRAPH=0: every run eager); the maps are copied out with three
+ * device-to-device copies on `stream`.  ONE RUN AT A TIME PER ENGINE (the intermediates belong to the engine; a concurrent run fails);
+ * any number of engines may coexist, one per device and configuration or several on one device.
+ */
+enum { S2M2_REGION_CONTENT = 0, S2M2_REGION_SCRATCH = 1, S2M2_REGION_EXTERNAL = 2 };
+typedef struct s2m2_engine_region {
+    const void* base;
+    unsigned long long bytes;
+    int kind;
+} s2m2_engine_region;
+typedef struct s2m2_engine_info {
+    int B, H, W;
+    int dtype;                 /* compute dtype: S2M2_F32 / S2M2_F16 */
+    int image_dtype;           /* S2M2_F32 / S2M2_F16 / 2 (uint8) */
+    int feature_channels, dim_expansion, num_transformer;
+    int use_positivity, output_upsample, refine_iter;
+    int out_h, out_w;          /* (H, W), or (2H, 2W) with output_upsample */
+    int out_region;
+    long long out_offset;
+} s2m2_engine_info;
+typedef struct s2m2_engine s2m2_engine;
+int s2m2_plan_save(const s2m2_plan* plan, const s2m2_engine_region* regions, int nregions, const s2m2_engine_info* meta, const char* path);
+int s2m2_engine_load(const char* path, s2m2_engine** engine);
+int s2m2_engine_meta(const s2m2_engine* engine, s2m2_engine_info* meta);
+int s2m2_engine_run(s2m2_engine* engine, const void* left, const void* right, float* disp, float* occ, float* conf, void* stream);
+int s2m2_engine_destroy(s2m2_engine* engine);
 
 int s2m2_event_create(void** event);
 int s2m2_event_destroy(void* event);

@@ -2,6 +2,9 @@
 
     python -m s2m2_amd.build [--force]
 
+Next to the library it links ``lib/s2m2_run_engine`` (app/run_engine.cpp): the stand-alone runner of engine files, which uses nothing but the
+library and the HIP runtime (rpath to both).
+
 hipcc cross-compiles for gfx950 without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  Objects are cached per source file (mtime based) under s2m2_amd/csrc/_obj.
 """
@@ -112,7 +115,29 @@ def build(force: bool = False, verbose: bool = True, extra_defines=()) -> str:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
     if verbose:
         print(f"[s2m2_amd.build] {LIB} ({os.path.getsize(LIB) / 1024:.0f} KiB) from {len(srcs)} sources")
+    if not SUFFIX:                                                 # experiment builds (suffixed libraries) have no runner of their own
+        build_runner(force, verbose)
     return LIB
+
+
+RUNNER_SRC = os.path.join(HERE, "app", "run_engine.cpp")
+RUNNER = os.path.join(LIBDIR, "s2m2_run_engine")
+
+
+def build_runner(force: bool = False, verbose: bool = True) -> str:
+    """lib/s2m2_run_engine: host code only, linked against lib/libs2m2_hip.so (rpath $ORIGIN) and the HIP runtime (rpath: ROCm's lib)"""
+    include = os.path.join(os.path.dirname(HERE), "include")
+    newest = max(os.path.getmtime(RUNNER_SRC), os.path.getmtime(LIB), os.path.getmtime(os.path.join(include, "s2m2_hip.h")))
+    if force or not os.path.exists(RUNNER) or os.path.getmtime(RUNNER) < newest:
+        rocm_lib = os.path.join(os.path.dirname(os.path.dirname(HIPCC)), "lib")
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-I", include, RUNNER_SRC, "-o", RUNNER, "-L", LIBDIR,
+               "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + rocm_lib]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"building s2m2_run_engine failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+        if verbose:
+            print(f"[s2m2_amd.build] {RUNNER}")
+    return RUNNER
 
 
 if __name__ == "__main__":

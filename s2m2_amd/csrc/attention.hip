@@ -775,3 +775,6 @@ extern "C" int s2m2_attention_supported(int nb, int heads, int N, int D, int gri
     return attention_entry(nullptr, nullptr, nullptr, nullptr, 3 * c, 3 * c, 3 * c, c, nb, heads, N, N, D, 1.0f, 0, pe ? &dummy : nullptr,
                            pe ? &dummy : nullptr, pe ? const_cast<float*>(&dummy) : nullptr, heads * 32, grid_w, grid_h, dtype, nullptr, 1) == 0;
 }
+
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_ENTRY("s2m2_attention", attention_impl)

@@ -732,3 +732,5 @@ extern "C" int s2m2_mlp_chain(const s2m2_chain_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_chain_desc>("s2m2_mlp_chain", &mlp_chain_impl, d, stream);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_mlp_chain", mlp_chain_impl)

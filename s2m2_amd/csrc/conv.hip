@@ -1765,3 +1765,5 @@ extern "C" int s2m2_conv2d(const s2m2_conv_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_conv_desc>("s2m2_conv2d", &conv2d_impl, d, stream);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_conv2d", conv2d_impl)

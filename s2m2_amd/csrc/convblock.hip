@@ -328,3 +328,6 @@ static int conv_block_impl(const s2m2_convblock_desc* d, void* stream) {
 extern "C" int s2m2_conv_block(const s2m2_convblock_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_convblock_desc>("s2m2_conv_block", &conv_block_impl, d, stream);
 }
+
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_conv_block", conv_block_impl)

@@ -68,3 +68,5 @@ extern "C" int s2m2_cv_lookup(const void* cv, const float* disp, void* corr1, vo
     return s2m2::plan_dispatch("s2m2_cv_lookup", &cv_lookup_impl, stream, cv, disp, corr1, corr2, B, h, w, radius, cv_dtype, out_dtype, batch_stride, pix_stride, tap_stride, cv_pitch);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_ENTRY("s2m2_cv_lookup", cv_lookup_impl)

@@ -522,3 +522,6 @@ extern "C" int s2m2_feature_fusion(const void* z0, const void* z1, void* out, lo
     return s2m2::plan_dispatch("s2m2_feature_fusion", &feature_fusion_impl, stream, z0, z1, out, z0_stride, z1_stride, out_stride, rows, C, w1, b1, w2, bg, bf, z1_coarse_h, z1_coarse_w, dtype);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_ENTRY("s2m2_feature_fusion_frag", feature_fusion_frag_impl)
+S2M2_PLAN_ENTRY("s2m2_feature_fusion", feature_fusion_impl)

@@ -581,3 +581,6 @@ extern "C" const char* s2m2_ln_corr_kernel_name(int C, int feat_dtype, int cv_dt
     (void)C; (void)feat_dtype; (void)cv_dtype;
     return "ln_corr_kernel";
 }
+
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_cost_volume", cost_volume_impl)

@@ -239,3 +239,6 @@ extern "C" int s2m2_groupnorm_nhwc(const void* x, void* y, const float* gamma, c
     return s2m2::plan_dispatch("s2m2_groupnorm_nhwc", &groupnorm_nhwc_impl, stream, x, y, gamma, beta, workspace, N, HW, C, G, eps, dtype);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_ENTRY("s2m2_layernorm", layernorm_impl)
+S2M2_PLAN_ENTRY("s2m2_groupnorm_nhwc", groupnorm_nhwc_impl)

@@ -4,9 +4,12 @@
 // Every blob carries a mask of its POINTER words (ABI 600, round 6): s2m2_plan_end looks for pointers into the external buffers in those words
 // only -- an int pair, a stride or a size that happens to fall inside an external's address range is never rewritten.  Positional packs derive
 // the mask from the argument types; descriptors list their pointer fields below (PlanPtrFields: a descriptor without a list does not compile).
+// Every recorded entry point is also registered by name next to its definition (S2M2_PLAN_ENTRY / S2M2_PLAN_DESC_ENTRY: trampoline, impl,
+// blob size): an engine file (engine_file.hip) stores a call's impl as that name, and the loader maps it back through this table.
 #pragma once
 #include <stddef.h>
 #include <type_traits>
+#include <vector>
 #include "common.h"
 
 namespace s2m2 {
@@ -24,6 +27,31 @@ struct PlanPtrMask {
     bool test(size_t w) const { return w < 64 * kPlanMaskWords && ((bits[w / 64] >> (w % 64)) & 1ULL) != 0; }
 };
 int plan_append(int (*tramp)(const void* blob, void* stream), const void* blob, size_t bytes, const char* name, const PlanPtrMask& mask);
+
+// the table of recordable entry points (filled by static initialisers of the translation units that define them)
+struct PlanEntry {
+    const char* name;
+    int (*tramp)(const void* blob, void* stream);
+    const void* impl;
+    size_t bytes;                                                // sizeof the blob (impl pointer + arguments)
+};
+int plan_register(const char* name, int (*tramp)(const void*, void*), const void* impl, size_t bytes);
+const PlanEntry* plan_entry(const char* name);                   // nullptr: not a recordable entry point
+}  // namespace s2m2
+
+// a recording (runtime.hip) -- also read by s2m2_plan_save (engine_file.hip)
+struct s2m2_plan {
+    struct Call { int (*tramp)(const void*, void*); size_t off, words; const char* name; s2m2::PlanPtrMask mask; };
+    struct Patch { int call; int word; int slot; long long delta; };
+    std::vector<unsigned long long> arena;      // the blobs, 8-byte aligned
+    std::vector<Call> calls;
+    std::vector<Patch> patches;
+    int nslots = 0;
+    bool sealed = false, failed = false;
+    size_t max_words = 0;
+};
+
+namespace s2m2 {
 
 // positional arguments as a plain aggregate (std::tuple is not guaranteed trivially copyable; the blobs are copied and scanned as raw words)
 template <typename... A> struct ArgPack;
@@ -127,5 +155,28 @@ template <typename D> int plan_dispatch_desc(const char* name, int (*impl)(const
     }
     return rc;
 }
+
+// registration: positional entry points by the impl's signature minus the trailing stream, descriptor entry points by the descriptor type
+template <typename... T> struct TypeList {};
+template <typename Done, typename... Rest> struct DropLast;
+template <typename... D, typename L> struct DropLast<TypeList<D...>, L> { using type = TypeList<D...>; };
+template <typename... D, typename H, typename N, typename... R> struct DropLast<TypeList<D...>, H, N, R...> {
+    using type = typename DropLast<TypeList<D..., H>, N, R...>::type;
+};
+template <typename... A> int plan_register_pack(TypeList<A...>, const char* name, int (*impl)(A..., void*)) {
+    return plan_register(name, &plan_tramp<A...>, reinterpret_cast<const void*>(impl), sizeof(PlanBlob<A...>));
+}
+template <typename... P> int plan_register_positional(const char* name, int (*impl)(P...)) {
+    return plan_register_pack(typename DropLast<TypeList<>, P...>::type{}, name, impl);
+}
+template <typename D> int plan_register_desc(const char* name, int (*impl)(const D*, void*)) {
+    return plan_register(name, &plan_desc_tramp<D>, reinterpret_cast<const void*>(impl), sizeof(PlanDescBlob<D>));
+}
+#define S2M2_PLAN_CAT2(a, b) a##b
+#define S2M2_PLAN_CAT(a, b) S2M2_PLAN_CAT2(a, b)
+#define S2M2_PLAN_ENTRY(name, impl) \
+    static const int S2M2_PLAN_CAT(s2m2_plan_entry_, __LINE__) __attribute__((used)) = s2m2::plan_register_positional(name, &impl);
+#define S2M2_PLAN_DESC_ENTRY(name, impl) \
+    static const int S2M2_PLAN_CAT(s2m2_plan_entry_, __LINE__) __attribute__((used)) = s2m2::plan_register_desc(name, &impl);
 
 }  // namespace s2m2

@@ -395,3 +395,11 @@ extern "C" int s2m2_image_pad(const void* img, float* pooled, float* out, int B,
     return s2m2::plan_dispatch("s2m2_image_pad", &image_pad_impl, stream, img, pooled, out, B, C, H, W, factor, img_dtype);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_ENTRY("s2m2_image_prep", image_prep_impl)
+S2M2_PLAN_ENTRY("s2m2_refine_prep", refine_prep_impl)
+S2M2_PLAN_ENTRY("s2m2_global_update", global_update_impl)
+S2M2_PLAN_ENTRY("s2m2_refine_update_to", refine_update_to_impl)
+S2M2_PLAN_ENTRY("s2m2_stem_mlp", stem_mlp_impl)
+S2M2_PLAN_ENTRY("s2m2_tanh", tanh_impl)
+S2M2_PLAN_ENTRY("s2m2_image_pad", image_pad_impl)

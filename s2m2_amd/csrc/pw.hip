@@ -239,3 +239,5 @@ extern "C" int s2m2_pw_direct(const s2m2_pw_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_pw_desc>("s2m2_pw_direct", &pw_direct_impl, d, stream);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_pw_direct", pw_direct_impl)

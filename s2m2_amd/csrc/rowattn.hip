@@ -599,3 +599,6 @@ static int row_attn_impl(const s2m2_rowattn_desc* d, void* stream) {
 extern "C" int s2m2_row_attn(const s2m2_rowattn_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_rowattn_desc>("s2m2_row_attn", &row_attn_impl, d, stream);
 }
+
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_row_attn", row_attn_impl)

@@ -105,19 +105,25 @@ extern "C" int s2m2_debug_poison_lds(void* stream) {
 // positional pack, from the pointer-field list of a descriptor) are compared with the external ranges: a size, a stride or a pair of ints that
 // happens to fall inside a range is left alone.
 // ------------------------------------------------------------------------------------------------------------------------------------
-struct s2m2_plan {
-    struct Call { int (*tramp)(const void*, void*); size_t off, words; const char* name; s2m2::PlanPtrMask mask; };
-    struct Patch { int call; int word; int slot; long long delta; };
-    std::vector<unsigned long long> arena;      // the blobs, 8-byte aligned
-    std::vector<Call> calls;
-    std::vector<Patch> patches;
-    int nslots = 0;
-    bool sealed = false, failed = false;
-    size_t max_words = 0;
-};
-
+// (struct s2m2_plan: plan.h)
 namespace s2m2 {
 static thread_local s2m2_plan* g_plan = nullptr;
+
+static std::vector<PlanEntry>& entry_table() {                       // function-local: filled by static initialisers of other TUs
+    static std::vector<PlanEntry> t;
+    return t;
+}
+
+int plan_register(const char* name, int (*tramp)(const void*, void*), const void* impl, size_t bytes) {
+    entry_table().push_back({name, tramp, impl, bytes});
+    return (int)entry_table().size();
+}
+
+const PlanEntry* plan_entry(const char* name) {
+    for (const auto& e : entry_table())
+        if (strcmp(e.name, name) == 0) return &e;
+    return nullptr;
+}
 
 bool plan_recording() { return g_plan != nullptr; }
 

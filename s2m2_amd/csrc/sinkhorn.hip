@@ -594,3 +594,5 @@ extern "C" int s2m2_sinkhorn_regress(const void* cv, float* disp, float* conf, f
     return s2m2::plan_dispatch("s2m2_sinkhorn_regress", &sinkhorn_regress_impl, stream, cv, disp, conf, occ, argmax, B, h, w, ot_iter, use_positivity, cv_dtype, cv_pitch, workspace);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_ENTRY("s2m2_sinkhorn_regress", sinkhorn_regress_impl)

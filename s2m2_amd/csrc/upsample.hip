@@ -215,3 +215,6 @@ extern "C" int s2m2_resample2x(const void* x, void* y, int N, int H, int W, int 
     return s2m2::plan_dispatch("s2m2_resample2x", &resample2x_impl, stream, x, y, N, H, W, C, x_stride, y_stride, mode, dtype);
 }
 
+// recordable entry points of this file (plan.h: the table engine files are loaded through)
+S2M2_PLAN_DESC_ENTRY("s2m2_convex_upsample", convex_upsample_blob)
+S2M2_PLAN_ENTRY("s2m2_resample2x", resample2x_impl)

@@ -86,9 +86,23 @@ class PackDesc(ctypes.Structure):
 
 PACK_ROWS, PACK_NARROW, PACK_CONV_FRAG, PACK_FUSION, PACK_HEAD = range(5)
 
+REGION_CONTENT, REGION_SCRATCH, REGION_EXTERNAL = range(3)
+
+
+class EngineRegion(ctypes.Structure):
+    """mirror of s2m2_engine_region (include/s2m2_hip.h)"""
+    _fields_ = [("base", _vp), ("bytes", ctypes.c_ulonglong), ("kind", _i)]
+
+
+class EngineInfo(ctypes.Structure):
+    """mirror of s2m2_engine_info (include/s2m2_hip.h)"""
+    _fields_ = [("B", _i), ("H", _i), ("W", _i), ("dtype", _i), ("image_dtype", _i), ("feature_channels", _i), ("dim_expansion", _i),
+                ("num_transformer", _i), ("use_positivity", _i), ("output_upsample", _i), ("refine_iter", _i), ("out_h", _i), ("out_w", _i),
+                ("out_region", _i), ("out_offset", _ll)]
+
 
 # name -> (restype, argtypes); must list every symbol declared in include/s2m2_hip.h
-ABI_VERSION = 600                     # include/s2m2_hip.h: S2M2_ABI_VERSION (checked in load())
+ABI_VERSION = 700                     # include/s2m2_hip.h: S2M2_ABI_VERSION (checked in load())
 
 SIGNATURES = {
     "s2m2_version": (_i, []),
@@ -103,6 +117,11 @@ SIGNATURES = {
     "s2m2_plan_run": (_i, [_vp, ctypes.POINTER(_vp), _i, _vp]),
     "s2m2_plan_destroy": (_i, [_vp]),
     "s2m2_refine_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "s2m2_plan_save": (_i, [_vp, ctypes.POINTER(EngineRegion), _i, ctypes.POINTER(EngineInfo), ctypes.c_char_p]),
+    "s2m2_engine_load": (_i, [ctypes.c_char_p, ctypes.POINTER(_vp)]),
+    "s2m2_engine_meta": (_i, [_vp, ctypes.POINTER(EngineInfo)]),
+    "s2m2_engine_run": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "s2m2_engine_destroy": (_i, [_vp]),
     "s2m2_pack_frag_elems": (_ll, [ctypes.POINTER(PackDesc)]),
     "s2m2_pack_frag": (_i, [ctypes.POINTER(PackDesc), _vp]),
     "s2m2_event_create": (_i, [ctypes.POINTER(_vp)]),
