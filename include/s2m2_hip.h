@@ -38,8 +38,9 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * head_* appended to s2m2_narrow_desc without a bump -- the reason for the exact comparison since 500); 500 = round 5; 600 = round 6
  * (s2m2_row_attn and s2m2_conv_block added; the five ABI-400 entry points of K1 -- s2m2_ln_corr, _timed, _banded, _pitched, s2m2_corr -- removed: every form of
  * K1 is s2m2_cost_volume); 700 (engine files: s2m2_plan_save, s2m2_engine_*, s2m2_engine_region, s2m2_engine_info added; nothing changed
- * in place). */
-#define S2M2_ABI_VERSION 700
+ * in place); 800 (s2m2_cloud, s2m2_cloud_workspace_bytes and s2m2_cloud_desc added: the 3D output stage behind the forward; nothing changed in place,
+ * but engine files record the value and must be exported again). */
+#define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
 /* test aid (not part of the path): fills the LDS of every CU with quiet-NaN patterns, so that a kernel launched next that reads an LDS word it
@@ -650,6 +651,61 @@ int s2m2_stem_mlp(const void* x8, const float* w0, const float* b0, const float*
  *   average pooling of the zero-padded image to (H/factor, W/factor).  pooled: scratch (B,C,H/factor,W/factor) fp32.
  */
 int s2m2_image_pad(const void* img, float* pooled, float* out, int B, int C, int H, int W, int factor, int img_dtype, void* stream);
+
+/*
+ * K15 -- the 3D output stage behind the forward: validity filter, metric depth and a compacted coloured point cloud, on the device.
+ *   Replaces the host-side numpy / open3d steps of the reference's demos (demo/visualize_3d_middlebury.py:32-52,97-107: get_pointcloud and
+ *   the filtered disparity; src/s2m2/core/utils/model_utils.py:111-136; the validity mask of src/s2m2/core/utils/vis_utils.py:62; open3d's
+ *   RGBDImage.create_from_color_and_depth + PointCloud.create_from_rgbd_image by their documented behaviour).
+ *     disp, occ, conf  (B,1,Hp,Wp) fp32: the padded maps as S2M2.forward / s2m2_engine_run return them
+ *     image            (B,3,H,W) planar left image, UNPADDED, image_dtype S2M2_F32 / S2M2_F16 / 2 (uint8), values in [0,255].  The crop of
+ *                      image_crop is fused: image pixel (v,u) reads map pixel (v + (Hp-H)/2, u + (Wp-W)/2); H == Hp, W == Wp is fine
+ *   per pixel, all in fp32 (u, v: pixel indices of the unpadded image):
+ *     valid = unfiltered || (conf > conf_min && occ > occ_min);       d = valid ? disp : -1
+ *     depth = d <= 0 ? 1e9f : (float)(baseline * fx) / (d + (float)doffs)             (the product baseline * fx is formed in double here)
+ *     z = depth / depth_scale;      keep = z > 0 && z < depth_trunc                   (depth_trunc <= 0: 1e9, the reference's None)
+ *     x = (u - cx) * z / fx;        y = (v - cy) * z / fy
+ *     r, g, b = the pixel's colour as bytes (fp16 / fp32 images: clamped to [0,255], rounded to nearest even)
+ *   outputs, each optional (NULL), at least one:
+ *     depth    (B,1,H,W) fp32: z where keep, else 0
+ *     mask     (B,1,H,W) uint8: keep
+ *     count    (B) int32: the number of kept pixels of every pair -- ALWAYS the true number, also above `capacity`.  Non-NULL requests the
+ *              cloud: then image and workspace (>= s2m2_cloud_workspace_bytes(B, H, W) bytes, 4-byte aligned) are required
+ *     records  (B, capacity) records of 16 bytes { float x, y, z; uint8 r, g, b, a = 255 } (16-byte aligned; the vertex layout of a binary
+ *              little-endian PLY with x y z float, red green blue alpha uchar): the kept pixels of pair b in RASTER order (row-major over
+ *              v, u) at records + b * capacity.  Kept pixels with rank >= capacity are not stored (the caller compares count with capacity);
+ *              records beyond min(count, capacity) are left untouched.  May be NULL with capacity = 0 (count only)
+ *   Two launches, no host step between them, no atomics, no waiting between blocks: the result is bit-reproducible.  Launch A: a block takes
+ *   a fixed tile of whole image rows, writes the dense outputs and one count per tile into the workspace; launch B: a block sums the counts
+ *   of the tiles before its own, recomputes keep, ranks its pixels with wave ballots and stores the records; the last tile of a pair stores
+ *   count.  The maps are read with 16-byte loads whenever Wp % 4 == 0 and the map pointers are 16-byte aligned (any W, any crop offset).
+ *   Launch plans: s2m2_cloud is NOT recorded.  Called while the calling thread records a plan (s2m2_plan_begin .. s2m2_plan_end) it fails
+ *   with an error and launches nothing, so that it can never be silently missing from a plan or an engine file: the stage runs after
+ *   s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ *   Errors (before any device call): null descriptor / maps / missing image or workspace, no output requested, non-positive extents, H > Hp,
+ *   W > Wp, non-positive fx, fy or depth_scale, negative capacity, records NULL with capacity > 0, unknown image dtype.
+ */
+typedef struct s2m2_cloud_desc {
+    const float* disp;
+    const float* occ;
+    const float* conf;
+    const void* image;
+    float* depth;
+    unsigned char* mask;
+    void* records;
+    int32_t* count;
+    void* workspace;
+    int B, H, W, Hp, Wp;
+    int image_dtype;
+    int unfiltered;
+    long long capacity;        /* records per pair */
+    double fx, fy, cx, cy;
+    double baseline, doffs;
+    double depth_scale, depth_trunc;
+    double conf_min, occ_min;
+} s2m2_cloud_desc;
+size_t s2m2_cloud_workspace_bytes(int B, int H, int W);     /* 0: bad extents */
+int s2m2_cloud(const s2m2_cloud_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -101,8 +101,17 @@ class EngineInfo(ctypes.Structure):
                 ("out_region", _i), ("out_offset", _ll)]
 
 
+class CloudDesc(ctypes.Structure):
+    """mirror of s2m2_cloud_desc (include/s2m2_hip.h): K15, the 3D output stage"""
+    _fields_ = [("disp", _vp), ("occ", _vp), ("conf", _vp), ("image", _vp), ("depth", _vp), ("mask", _vp), ("records", _vp), ("count", _vp),
+                ("workspace", _vp), ("B", _i), ("H", _i), ("W", _i), ("Hp", _i), ("Wp", _i), ("image_dtype", _i), ("unfiltered", _i),
+                ("capacity", _ll), ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+                ("baseline", ctypes.c_double), ("doffs", ctypes.c_double), ("depth_scale", ctypes.c_double), ("depth_trunc", ctypes.c_double),
+                ("conf_min", ctypes.c_double), ("occ_min", ctypes.c_double)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/s2m2_hip.h
-ABI_VERSION = 700                     # include/s2m2_hip.h: S2M2_ABI_VERSION (checked in load())
+ABI_VERSION = 800                     # include/s2m2_hip.h: S2M2_ABI_VERSION (checked in load())
 
 SIGNATURES = {
     "s2m2_version": (_i, []),
@@ -165,6 +174,8 @@ SIGNATURES = {
     "s2m2_layernorm": (_i, [_vp, _vp, _ll, _i, _ll, _ll, _i, _vp]),
     "s2m2_groupnorm_workspace_bytes": (ctypes.c_size_t, [_i, _i]),
     "s2m2_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, ctypes.c_float, _i, _vp]),
+    "s2m2_cloud_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_cloud": (_i, [ctypes.POINTER(CloudDesc), _vp]),
 }
 
 
@@ -1088,3 +1099,57 @@ def image_pad(img: torch.Tensor, factor: int = 32) -> torch.Tensor:
     _check(load().s2m2_image_pad(img.data_ptr(), pooled.data_ptr(), out.data_ptr(), B, C, H, W, factor, _IMG_DT[img.dtype], _stream()),
            "s2m2_image_pad")
     return out
+
+
+def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, fy: float, cx: float, cy: float,
+          baseline: float, doffs: float = 0.0, depth_scale: float = 1000.0, depth_trunc: float = 0.0, conf_min: float = 0.1,
+          occ_min: float = 0.5, unfiltered: bool = False, records: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+          workspace: Optional[torch.Tensor] = None, depth: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> None:
+    """s2m2_cloud (K15): the padded maps (B,1,Hp,Wp) fp32 and the UNPADDED left image (B,3,H,W) uint8 / fp16 / fp32 -> the outputs the caller
+    allocated: ``records`` (B, capacity, 4) int32 = 16-byte point records in raster order with ``count`` (B) int32 and a ``workspace`` of
+    ``cloud_workspace_bytes`` bytes, ``depth`` (B,1,H,W) fp32, ``mask`` (B,1,H,W) uint8.  Thin: no allocation, no synchronisation."""
+    _dev(disp, occ, conf, image, records, count, workspace, depth, mask)
+    if disp.dtype != torch.float32 or occ.dtype != torch.float32 or conf.dtype != torch.float32 or disp.dim() != 4 or disp.shape[1] != 1:
+        raise ValueError("cloud: disp / occ / conf must be (B,1,Hp,Wp) fp32 tensors")
+    if occ.shape != disp.shape or conf.shape != disp.shape:
+        raise ValueError("cloud: disp, occ and conf must have one shape")
+    if image.dtype not in _IMG_DT or image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != disp.shape[0]:
+        raise ValueError("cloud: image must be a (B,3,H,W) uint8 / fp16 / fp32 tensor")
+    B, _, Hp, Wp = disp.shape
+    H, W = image.shape[-2:]
+    d = CloudDesc()
+    d.disp, d.occ, d.conf, d.image = disp.data_ptr(), occ.data_ptr(), conf.data_ptr(), image.data_ptr()
+    d.B, d.H, d.W, d.Hp, d.Wp, d.image_dtype, d.unfiltered = B, H, W, Hp, Wp, _IMG_DT[image.dtype], int(unfiltered)
+    if depth is not None:
+        if depth.dtype != torch.float32 or tuple(depth.shape) != (B, 1, H, W):
+            raise ValueError("cloud: depth must be a (B,1,H,W) fp32 tensor")
+        d.depth = depth.data_ptr()
+    if mask is not None:
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, 1, H, W):
+            raise ValueError("cloud: mask must be a (B,1,H,W) uint8 tensor")
+        d.mask = mask.data_ptr()
+    if count is not None:
+        if count.dtype != torch.int32 or count.numel() != B:
+            raise ValueError("cloud: count must hold B int32")
+        need = cloud_workspace_bytes(B, H, W)
+        if workspace is None or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"cloud: a workspace of {need} bytes is required with count")
+        d.count, d.workspace = count.data_ptr(), workspace.data_ptr()
+        if records is not None:
+            if records.dtype != torch.int32 or records.dim() != 3 or records.shape[0] != B or records.shape[2] != 4:
+                raise ValueError("cloud: records must be a (B, capacity, 4) int32 tensor")
+            d.capacity = records.shape[1]
+            d.records = records.data_ptr() if records.shape[1] > 0 else None
+    elif records is not None:
+        raise ValueError("cloud: records come with count")
+    d.fx, d.fy, d.cx, d.cy, d.baseline, d.doffs = fx, fy, cx, cy, baseline, doffs
+    d.depth_scale, d.depth_trunc, d.conf_min, d.occ_min = depth_scale, depth_trunc, conf_min, occ_min
+    with torch.cuda.device(disp.device):
+        _check(load().s2m2_cloud(ctypes.byref(d), _stream()), "s2m2_cloud")
+
+
+def cloud_workspace_bytes(B: int, H: int, W: int) -> int:
+    n = int(load().s2m2_cloud_workspace_bytes(B, H, W))
+    if n == 0:
+        raise ValueError(f"cloud: bad extents B={B} H={H} W={W}")
+    return n

@@ -6,6 +6,7 @@ image_utils.py) -- SURVEY.md section 8f rows 1-2: same names, arguments and retu
 * ``image_crop``           image_utils.py:73-103 (pure slicing)
 * ``run_stereo_matching``  model_utils.py:51-95 (pad -> autocast fp16 forward -> crop -> average confidence)
 * ``compute_confidence_score``   model_utils.py:98-101
+* ``get_pointcloud``       model_utils.py:111-136 (depth from disparity + open3d's RGBD -> point cloud conversion; HIP kernels ``s2m2_cloud``)
 * ``compute_confidence_scores``  the calibration objective (calibration/base.py:15-36 called 20 x 5 times one pair at a time by
   calibration/cem.py:66-72) for a whole population of rectified pairs at once: one batched forward, or sharded over the ranks of a
   ``torch.distributed`` group
@@ -138,3 +139,19 @@ def compute_confidence_scores(model: S2M2, lefts: torch.Tensor, rights: torch.Te
         real = shard_indices(N, r, world)
         out[real] = parts[r][:len(real)].float().cpu()
     return out
+
+
+def get_pointcloud(rgb, disp, calib, depth_trunc=None):
+    """Same arguments as the reference: ``rgb`` (H,W,3) uint8, ``disp`` (H,W) (numpy arrays or tensors), ``calib`` the dict of
+    ``cloud.read_calib_file`` -- including the reference's halving of fx, cx and cy (it is written for half-resolution Middlebury images) and
+    fx for both focal lengths.  No confidence filter, like the reference function: the caller passes the disparity already filtered (-1 where
+    invalid).  Returns a ``cloud.PointCloud`` on the device instead of an open3d object."""
+    from . import cloud
+    disp_t = torch.as_tensor(disp)
+    device = disp_t.device if disp_t.is_cuda else torch.device("cuda")
+    disp_t = disp_t.to(device=device, dtype=torch.float32).contiguous()[None, None]
+    image = torch.as_tensor(rgb).to(device).permute(2, 0, 1).contiguous()[None]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(device):
+        return cloud.reproject(disp_t, disp_t, disp_t, image, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
+                               baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False)
