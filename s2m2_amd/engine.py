@@ -813,6 +813,30 @@ class Engine:
         twoB, h, w, _ = tr.shape
         return hip.cv_alloc(twoB // 2, h, w, tr.dtype, tr.device)
 
+    # ---- the pieces of finish() around the refiners (each one a module of the fp16 module parity tests) ----------
+    def ctx_hidden(self, tr0: Tensor, py0: Tensor) -> Tuple[Tensor, Tensor]:
+        """feat_fusion_layer -> ctx_feat -> tanh (s2m2.py:163-166): the refiners' context features and the first hidden state."""
+        fus = self.fusion("feat_fusion_layer", tr0, py0)
+        c0, c2 = self.std("ctx_feat.0"), self.std("ctx_feat.2")
+        cc = fus.shape[-1]
+        if (c0[2] == 1 and c2[2] == 1 and tuple(c0[0].shape) == (cc, cc) and tuple(c2[0].shape) == (cc, cc) and not getattr(c0, "korder", 0)
+                and self.chain_frag_ok(cc)):
+            # ctx_feat = 1x1 - GELU - 1x1 (s2m2.py:59,165): ONE two-stage K9 launch (the intermediate never leaves the CU) instead of two
+            ctx = hip.mlp_chain(fus, [(self.wfrag(c0), c0[1], hip.ACT_GELU, None), (self.wfrag(c2), c2[1], hip.ACT_NONE, None)], frag=True)
+        else:
+            ctx = self.cconv(c2, [self.cconv(c0, [fus], act=hip.ACT_GELU)])
+        return ctx, hip.tanh(ctx)
+
+    def upsample4x(self, disp: Tensor, occ: Tensor, conf: Tensor, m4: Tensor, x8: Tensor):
+        """Convex upsampling 1/4 -> 1/1 of (4 * disp, occ, conf) (s2m2.py:183-185); the disparity also lands in channel 0 of ``x8``, the
+        input of UpsampleMask1x."""
+        return hip.convex_upsample([disp, occ, conf], m4, 4, scales=[4.0, 1.0, 1.0], chan_out=x8[..., 0])
+
+    def upsample1x(self, d_up: Tensor, o_up: Tensor, c_up: Tensor, m1: Tensor):
+        """The full-resolution convex filter (s2m2.py:188-197); output_upsample: onto the 2x grid, the logits upsampled inside the kernel."""
+        up = self.output_upsample
+        return tuple(hip.convex_upsample([d_up, o_up, c_up], m1, 2 if up else 1, scales=[2.0 if up else 1.0, 1.0, 1.0], logit_up2=up))
+
     @torch.no_grad()
     def finish(self, tr: Tensor, py0: Tensor, f2_left: Tensor, x8: Tensor, cv: Tensor, cap: Optional[dict] = None):
         """Sinkhorn + regression, global refiner, refinement loop, convex upsampling (s2m2.py:153-197)."""
@@ -834,16 +858,7 @@ class Engine:
             cap["disp_g"] = disp
         # (measured and dropped, profiles/r04/ab_k1_store_sc1lib_overlap.txt: this branch -- and the f2x layers of the two mask heads -- on a second stream as
         # parallel branches of the captured hipGraph: 8.95 vs 8.83 ms per pair and K1 19.4 vs 17.7 us, the side kernels evict K1's tokens)
-        fus = self.fusion("feat_fusion_layer", tr0, py0[:B])
-        c0, c2 = self.std("ctx_feat.0"), self.std("ctx_feat.2")
-        cc = fus.shape[-1]
-        if (c0[2] == 1 and c2[2] == 1 and tuple(c0[0].shape) == (cc, cc) and tuple(c2[0].shape) == (cc, cc) and not getattr(c0, "korder", 0)
-                and self.chain_frag_ok(cc)):
-            # ctx_feat = 1x1 - GELU - 1x1 (s2m2.py:59,165): ONE two-stage K9 launch (the intermediate never leaves the CU) instead of two
-            ctx = hip.mlp_chain(fus, [(self.wfrag(c0), c0[1], hip.ACT_GELU, None), (self.wfrag(c2), c2[1], hip.ACT_NONE, None)], frag=True)
-        else:
-            ctx = self.cconv(c2, [self.cconv(c0, [fus], act=hip.ACT_GELU)])
-        hidden = hip.tanh(ctx)
+        ctx, hidden = self.ctx_hidden(tr0, py0[:B])
         if cap is not None:
             cap["ctx"] = ctx.permute(0, 3, 1, 2)
         small = None
@@ -858,13 +873,12 @@ class Engine:
             if cap is not None:
                 cap[f"disp_it{it}"], cap[f"conf_it{it}"], cap[f"occ_it{it}"] = disp, conf, occ
         m4 = self.mask4x("upsample_mask_4x_refine", hidden, f2_left)
-        d_up, o_up, c_up = hip.convex_upsample([disp, occ, conf], m4, 4, scales=[4.0, 1.0, 1.0], chan_out=x8[..., 0])
-        m1 = self.mask1x("upsample_mask_1x", x8, f2_left)
+        d_up, o_up, c_up = self.upsample4x(disp, occ, conf, m4, x8)
+        m1 =self.mask1x("upsample_mask_1x", x8, f2_left)
         if cap is not None:
             cap.update(hidden=hidden.permute(0, 3, 1, 2), mask4x=m4[..., :9].permute(0, 3, 1, 2), disp_up4=d_up,
                        mask1x=m1[..., :9].permute(0, 3, 1, 2))
-        up = self.output_upsample
-        return tuple(hip.convex_upsample([d_up, o_up, c_up], m1, 2 if up else 1, scales=[2.0 if up else 1.0, 1.0, 1.0], logit_up2=up))
+        return self.upsample1x(d_up, o_up, c_up, m1)
 
     @torch.no_grad()
     def run(self, img0: Tensor, img1: Tensor, cap: Optional[dict] = None, x8: Optional[Tensor] = None):

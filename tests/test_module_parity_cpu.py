@@ -167,6 +167,171 @@ def test_judge_measured_mutations(sd, name, mutation, rejected):
     assert v.ok != rejected, v.row()
 
 
+# ---- the refinement half (module_parity.o_*): mutations the engine's packing of these modules could plausibly have -----------------------
+# S weights at w = 304, 16 rows (8 for the full-resolution heads); the disparity regime is the near one unless the name says otherwise.
+RH, RW = 16, 304
+
+
+def _conv_edit(edit):
+    """O._conv with (prefix, input) edited: edit(p, x) -> (p, x)"""
+    real = O._conv
+
+    def conv(sd, p, x, stride=1, pad=0):
+        p, x = edit(p, x)
+        return real(sd, p, x, stride, pad)
+    return lambda: MP.patched(O, "_conv", conv)
+
+
+def _lookup_edit(edit):
+    real = O.cv_lookup
+    return lambda: MP.patched(O, "cv_lookup", lambda cv, disp, radius=4: edit(*real(cv, disp, radius)))
+
+
+def _swap(a, b):
+    def edit(p, x):
+        return (p.replace(a, b) if a in p else p.replace(b, a)), x
+    return edit
+
+
+def _blend_exchanged():
+    def conv_gru(sd, p, h, x):                                          # O.conv_gru with z and 1 - z exchanged in the blend
+        for sfx, pad in (("1", (1, 0)), ("2", (0, 1))):
+            hx = torch.cat([h, x], 1)
+            z = O._q(torch.sigmoid(O._conv(sd, f"{p}.convz{sfx}", hx, 1, pad)))
+            r = O._q(torch.sigmoid(O._conv(sd, f"{p}.convr{sfx}", hx, 1, pad)))
+            q = O._q(torch.tanh(O._conv(sd, f"{p}.convq{sfx}", torch.cat([O._q(r * h), x], 1), 1, pad)))
+            h = O._q(O._q(z * h) + O._q(O._q(1 - z) * q))
+        return h
+    return MP.patched(O, "conv_gru", conv_gru)
+
+
+def _shuffle_transposed(layer):
+    real = O._convT
+
+    def convT(sd, p, x, stride=1, pad=0):
+        if p.endswith(layer):
+            sd = dict(sd)
+            sd[p + ".weight"] = sd[p + ".weight"].transpose(2, 3).contiguous()       # (dy, dx) of the 2 x 2 pixel shuffle exchanged
+        return real(sd, p, x, stride, pad)
+    return lambda: MP.patched(O, "_convT", convT)
+
+
+def _disp_in_rgb_slot():
+    real = O.upsample_mask_1x                                           # conv_disp reads the R plane, conv_rgb's first plane the disparity
+    return MP.patched(O, "upsample_mask_1x", lambda sd, p, disp, rgb, f2x: real(sd, p, rgb[:, 0:1], torch.cat([disp, rgb[:, 1:]], 1), f2x))
+
+
+def _neigh_transposed():
+    def neigh9(x):
+        B, _, h, w = x.shape
+        xp = F.pad(x, (1, 1, 1, 1), mode="replicate")
+        return torch.cat([xp[:, :, dy:dy + h, dx:dx + w] for dx in range(3) for dy in range(3)], 1)
+    return MP.patched(O, "_neigh9", neigh9)
+
+
+def _neigh_zero_padded():
+    def neigh9(x):
+        B, _, h, w = x.shape
+        xp = F.pad(x, (1, 1, 1, 1))
+        return torch.cat([xp[:, :, dy:dy + h, dx:dx + w] for dy in range(3) for dx in range(3)], 1)
+    return MP.patched(O, "_neigh9", neigh9)
+
+
+def _refine(sd, far=False, first=True):
+    xs = MP.refine_inputs(sd, 128, RH, RW, far, 100, masked_occ=not first)
+    return lambda: MP.o_refine(sd, *xs, first=first, want_side=first), xs
+
+
+def _mask4(sd):
+    xs = [MP.round16(torch.tanh(MP.seeded((1, 128, 8, RW), 70))), MP.seeded((1, sd[MP.MASK4 + ".conv_y.weight"].shape[1], 16, 2 * RW), 71)]
+    return lambda: MP.o_mask4x(sd, *xs), xs
+
+
+def _mask1(sd):
+    xs = [MP.uniform16((1, 1, 32, 4 * RW), 80, 0.0, 4.0 * (RW - 1)), MP.uniform16((1, 3, 32, 4 * RW), 81, -1.0, 1.0),
+          MP.seeded((1, sd[MP.MASK4 + ".conv_y.weight"].shape[1], 16, 2 * RW), 82)]
+    return lambda: MP.o_mask1x(sd, *xs), xs
+
+
+def _up4(sd):
+    xs = [MP.uniform16((1, 1, 8, RW), 90, 0.0, RW - 1.0), MP.uniform16((1, 1, 8, RW), 91, 0.0, 1.0), MP.uniform16((1, 1, 8, RW), 92, 0.0, 1.0),
+          MP.seeded((1, 9, 32, 4 * RW), 93)]
+    return lambda: MP.o_upsample4x(sd, *xs), xs
+
+
+REFINE_CASES = {
+    # id: (module under test -> (fn, inputs), mutation)
+    "lookup_level2_without_the_16th": (_refine, _lookup_edit(lambda c1, c2: (c1, c2 * 16))),
+    "corr_feat2_reads_level1_taps": (_refine, _lookup_edit(lambda c1, c2: (c1, c1))),
+    "nine_taps_reversed": (_refine, _lookup_edit(lambda c1, c2: (c1.flip(1), c2.flip(1)))),
+    "conf_occ_logits_swapped": (_refine, _conv_edit(lambda p, x: (p, x.flip(1) if p.endswith("conf_occ_feat.0") else x))),
+    "disp_not_divided_by_100": (_refine, _conv_edit(lambda p, x: (p, x * 1e2 if p.endswith("refiner.disp_feat.0") else x))),
+    "gru_z_r_halves_swapped": (_refine, _conv_edit(_swap(".gru.convz", ".gru.convr"))),
+    "gru_blend_z_exchanged": (_refine, lambda: _blend_exchanged()),
+    "update_heads_exchanged": (_refine, _conv_edit(_swap("refiner.disp_update.0", "refiner.conf_occ_update.0"))),
+    "mask4x_pixel_shuffle_transposed": (_mask4, _shuffle_transposed(".conv_x")),
+    "mask4x_out_pixel_shuffle_transposed": (_mask4, _shuffle_transposed(".conv_concat.2")),
+    "mask1x_ctx_pixel_shuffle_transposed": (_mask1, _shuffle_transposed(".conv_ctx")),
+    "mask1x_disparity_in_the_red_slot": (_mask1, lambda: _disp_in_rgb_slot()),
+    "upsample_neighbours_transposed": (_up4, lambda: _neigh_transposed()),
+    "upsample_zero_padding": (_up4, lambda: _neigh_zero_padded()),
+    "upsample_disparity_not_times_4": (_up4, lambda: MP.patched(MP, "UP4_SCALE", 1.0)),
+}
+_PAIRS = {}
+
+
+def _judged(sd, build, mutation=None):
+    """verdicts per output of the (mutated) module in the emulation against the comparator, occ outputs with their keep-mask"""
+    if build not in _PAIRS:
+        fn, xs = build(sd)
+        _PAIRS[build] = (fn, xs) + tuple(MP.oracle_pair(fn))
+    fn, xs, y32, y16e = _PAIRS[build]
+    ym = y16e
+    if mutation is not None:
+        with mutation(), torch.no_grad(), O.precision("fp16"):
+            ym = fn()
+    keep = MP.occ_keep(xs[2], y32[1], y16e[1]) if build is _refine else None
+    out = []
+    for k, (m, a, b) in enumerate(zip(ym, y32, y16e)):
+        kp = MP.nhwc(keep) if (keep is not None and k in MP.OCC_OUTPUTS) else None
+        if kp is not None:
+            assert 1.0 - float(kp.float().mean()) <= MP.MAX_MASKED
+        out.append(MP.judge(MP.nhwc(m), MP.nhwc(a), MP.nhwc(b), f"[{k}]", keep=kp))
+    return out
+
+
+@pytest.mark.parametrize("build", [_refine, _mask4, _mask1, _up4], ids=["refine", "mask4x", "mask1x", "upsample4x"])
+def test_judge_accepts_the_emulation_of_the_refinement_half(sd, build):
+    vs = _judged(sd, build)
+    assert all(v.ok for v in vs), "\n".join(v.msg for v in vs if not v.ok)
+
+
+@pytest.mark.parametrize("name", list(REFINE_CASES))
+def test_judge_rejects_refinement_mutation(sd, name):
+    build, mutation = REFINE_CASES[name]
+    vs = _judged(sd, build, mutation)
+    print(name, [k for k, v in enumerate(vs) if not v.ok], [{q: round(r, 2) for q, r in v.ratios().items()} for v in vs])
+    assert not all(v.ok for v in vs), f"{name} passed the comparator: " + " / ".join(v.row() for v in vs)
+
+
+def test_keep_mask_only_narrows_the_statistics(sd):
+    """judge(keep=): an error confined to the masked elements is not counted, the same error on a kept element is; the default
+    (keep=None) is the unmasked comparison"""
+    y32 = MP.seeded((1, 4, 8, 1), 5)
+    y16e = y32 + 1e-3 * MP.seeded((1, 4, 8, 1), 6)
+    keep = torch.ones_like(y32, dtype=torch.bool)
+    keep[0, 0, 0, 0] = False
+    bad = y16e.clone()
+    bad[0, 0, 0, 0] += 1.0
+    assert not MP.judge(bad, y32, y16e).ok and MP.judge(bad, y32, y16e, keep=keep).ok
+    bad = y16e.clone()
+    bad[0, 1, 1, 0] += 1.0
+    assert not MP.judge(bad, y32, y16e, keep=keep).ok
+    bad[0, 1, 1, 0] = float("nan")
+    keep[0, 1, 1, 0] = False
+    assert not MP.judge(bad, y32, y16e, keep=keep).ok          # non-finite values are never masked
+
+
 def test_precision_context_restores_the_mode():
     assert not O._Prec.half
     with O.precision("fp16"):
