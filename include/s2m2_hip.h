@@ -39,7 +39,10 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * (s2m2_row_attn and s2m2_conv_block added; the five ABI-400 entry points of K1 -- s2m2_ln_corr, _timed, _banded, _pitched, s2m2_corr -- removed: every form of
  * K1 is s2m2_cost_volume); 700 (engine files: s2m2_plan_save, s2m2_engine_*, s2m2_engine_region, s2m2_engine_info added; nothing changed
  * in place); 800 (s2m2_cloud, s2m2_cloud_workspace_bytes and s2m2_cloud_desc added: the 3D output stage behind the forward; nothing changed in place,
- * but engine files record the value and must be exported again). */
+ * but engine files record the value and must be exported again); still 800 with s2m2_rectify and s2m2_rectify_desc (K16, the rectifier in front of
+ * the forward): purely additive -- no existing struct or entry point changes, engine files do not contain the stage -- so neither callers nor
+ * engine files of 800 are invalidated.  A library built before K16 reports 800 as well and lacks the symbol: s2m2_amd/hip.py load() names the
+ * missing symbol and asks for a rebuild. */
 #define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
@@ -706,6 +709,61 @@ typedef struct s2m2_cloud_desc {
 } s2m2_cloud_desc;
 size_t s2m2_cloud_workspace_bytes(int B, int H, int W);     /* 0: bad extents */
 int s2m2_cloud(const s2m2_cloud_desc* desc, void* stream);
+
+/*
+ * K16 -- the rectifier in front of the forward: undistort + rectify + bilinear resample of raw sensor images, one launch for a whole population
+ *   of rectifications of one raw pair (online calibration: every candidate rotation correction is one record pair).  Replaces the host-side
+ *   cv2.initUndistortRectifyMap + cv2.remap(INTER_LINEAR, BORDER_CONSTANT, 0) of the reference (src/s2m2/core/utils/calib_utils.py:354-360,
+ *   image_utils.py:108-136) by their documented behaviour.
+ *     src[0..n_src-1]  one or two raw images of Hs x Ws pixels, 3 channels, values in [0,255]: src_format S2M2_RECTIFY_SRC_U8_HWC (uint8,
+ *                      (Hs,Ws,3) interleaved as image readers deliver it), _U8_CHW (uint8 (3,Hs,Ws) planar) or _F32_CHW (fp32 planar)
+ *     records          n_img records of S2M2_RECTIFY_RECORD_FLOATS fp32 in DEVICE memory (not kernel arguments: a captured hipGraph is replayed
+ *                      for the next population by rewriting this buffer only), fields at the S2M2_RECTIFY_REC_* offsets:
+ *                        SRC   index of the source image as a float (0 or 1; the kernel clamps it to [0, n_src-1])
+ *                        IR    iR = inv(P[:, :3] . R_rect), 9 values row-major
+ *                        FX, FY, CX, CY   of the raw camera;   K1, K2, P1, P2, K3   its distortion (OpenCV order)
+ *     out              (n_img, 3, Hd, Wd) planar, out_dtype S2M2_F32 or 2 (uint8) -- what S2M2.forward, s2m2_image_pad and s2m2_cloud take
+ *     maps             optional (n_img, 2, Hd, Wd) fp32: mapx, mapy of every output pixel (tests, debugging)
+ *   per output pixel (u, v), all in fp32 -- what cv2.initUndistortRectifyMap documents:
+ *     [X Y W] = iR . [u v 1];  x = X/W;  y = Y/W;  r2 = x*x + y*y;  kr = 1 + k1 r2 + k2 r2^2 + k3 r2^3
+ *     mapx = fx (x kr + 2 p1 x y + p2 (r2 + 2 x^2)) + cx;      mapy = fy (y kr + p1 (r2 + 2 y^2) + 2 p2 x y) + cy
+ *   then bilinear interpolation between the four taps around (mapx, mapy); taps outside the source contribute 0.  `round` != 0 rounds the
+ *   result to the nearest integer level (ties to even; the reference feeds the model uint8 images); uint8 output is always rounded and clamped.
+ *   DEVIATION from cv2.remap, documented and not imitated: OpenCV quantises the coordinates to 1/32 px and interpolates uint8 images with
+ *   15-bit fixed-point weights; this stage interpolates at the full fp32 coordinate.  The two differ by at most one grey level per 1/32 px of
+ *   local gradient (levels per pixel).
+ *   One launch, no atomics, no workspace, deterministic (every output element is written by one thread, from its own reads only).  Every lane
+ *   owns four consecutive output pixels of a row (16-byte plane stores when Wd % 4 == 0 and out / maps are 16-byte aligned; any Wd otherwise).
+ *   `order`: S2M2_RECTIFY_ORDER_SAMPLE (consecutive blocks are the same output tile of consecutive records, so that the blocks reading one
+ *   source region run together; the default) or S2M2_RECTIFY_ORDER_TILE (all tiles of a record, then the next record); same result.
+ *   Launch plans: s2m2_rectify is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing;
+ *   the stage is not part of engine files: it runs before s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture.
+ *   Errors (before any device call): null descriptor / records, no output requested, null source with out requested, n_src not 1 or 2,
+ *   non-positive n_img or extents, extents too large, unknown src_format / out_dtype / order, misaligned records / out / maps / fp32 source.
+ */
+enum { S2M2_RECTIFY_SRC_U8_HWC = 0, S2M2_RECTIFY_SRC_U8_CHW = 1, S2M2_RECTIFY_SRC_F32_CHW = 2 };
+enum { S2M2_RECTIFY_ORDER_SAMPLE = 0, S2M2_RECTIFY_ORDER_TILE = 1 };
+enum {
+    S2M2_RECTIFY_REC_SRC = 0,
+    S2M2_RECTIFY_REC_IR = 1,
+    S2M2_RECTIFY_REC_FX = 10, S2M2_RECTIFY_REC_FY = 11, S2M2_RECTIFY_REC_CX = 12, S2M2_RECTIFY_REC_CY = 13,
+    S2M2_RECTIFY_REC_K1 = 14, S2M2_RECTIFY_REC_K2 = 15, S2M2_RECTIFY_REC_P1 = 16, S2M2_RECTIFY_REC_P2 = 17, S2M2_RECTIFY_REC_K3 = 18,
+    S2M2_RECTIFY_RECORD_FLOATS = 20          /* the record stride: 80 bytes, 19 used */
+};
+typedef struct s2m2_rectify_desc {
+    const void* src[2];
+    const float* records;
+    void* out;                 /* may be NULL when maps is not */
+    float* maps;               /* may be NULL */
+    int n_src, n_img;
+    int Hs, Ws;                /* source extents */
+    int Hd, Wd;                /* output extents */
+    int src_format;
+    int out_dtype;             /* S2M2_F32 or 2 (uint8) */
+    int round;
+    int order;
+} s2m2_rectify_desc;
+int s2m2_rectify(const s2m2_rectify_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

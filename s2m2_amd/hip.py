@@ -110,6 +110,17 @@ class CloudDesc(ctypes.Structure):
                 ("conf_min", ctypes.c_double), ("occ_min", ctypes.c_double)]
 
 
+class RectifyDesc(ctypes.Structure):
+    """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
+    _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
+                ("Hd", _i), ("Wd", _i), ("src_format", _i), ("out_dtype", _i), ("round", _i), ("order", _i)]
+
+
+# s2m2_rectify: source formats, block orders and the record layout (include/s2m2_hip.h: S2M2_RECTIFY_*)
+RECTIFY_SRC_U8_HWC, RECTIFY_SRC_U8_CHW, RECTIFY_SRC_F32_CHW = 0, 1, 2
+RECTIFY_ORDER_SAMPLE, RECTIFY_ORDER_TILE = 0, 1
+RECTIFY_REC_SRC, RECTIFY_REC_IR, RECTIFY_REC_FX, RECTIFY_REC_K1, RECTIFY_RECORD_FLOATS = 0, 1, 10, 14, 20
+
 # name -> (restype, argtypes); must list every symbol declared in include/s2m2_hip.h
 ABI_VERSION = 800                     # include/s2m2_hip.h: S2M2_ABI_VERSION (checked in load())
 
@@ -176,6 +187,7 @@ SIGNATURES = {
     "s2m2_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, ctypes.c_float, _i, _vp]),
     "s2m2_cloud_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_cloud": (_i, [ctypes.POINTER(CloudDesc), _vp]),
+    "s2m2_rectify": (_i, [ctypes.POINTER(RectifyDesc), _vp]),
 }
 
 
@@ -188,7 +200,11 @@ def load() -> ctypes.CDLL:
                                "(the S2M2 hot path has no PyTorch fallback)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:                    # a stale library of the same ABI version (additive entry points do not bump it)
+                raise RuntimeError(f"{LIB_PATH} does not export {name} (include/s2m2_hip.h): "
+                                   "rebuild the library with `python -m s2m2_amd.build`") from None
             fn.restype = res
             fn.argtypes = args
         ver = lib.s2m2_version()
@@ -1153,3 +1169,46 @@ def cloud_workspace_bytes(B: int, H: int, W: int) -> int:
     if n == 0:
         raise ValueError(f"cloud: bad extents B={B} H={H} W={W}")
     return n
+
+
+def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, maps: Optional[torch.Tensor] = None, *, hd: Optional[int] = None,
+            wd: Optional[int] = None, round: bool = True, order: int = RECTIFY_ORDER_SAMPLE) -> None:
+    """s2m2_rectify (K16): ``srcs`` = one or two raw images of one shape and dtype -- (H,W,3) uint8 interleaved, (3,H,W) uint8 or (3,H,W) fp32 --
+    and ``records`` (n_img, RECTIFY_RECORD_FLOATS) fp32 -> the outputs the caller allocated: ``out`` (n_img,3,Hd,Wd) fp32 / uint8 and / or
+    ``maps`` (n_img,2,Hd,Wd) fp32.  With ``out`` None no source is read (``srcs`` gives the source extents only; pass ``hd`` / ``wd`` then, or
+    they are taken from ``maps``).  Thin: no allocation, no synchronisation."""
+    srcs = list(srcs)
+    _dev(*srcs, records, out, maps)
+    if len(srcs) not in (1, 2) or any(t.shape != srcs[0].shape or t.dtype != srcs[0].dtype for t in srcs):
+        raise ValueError("rectify: one or two source images of one shape and dtype")
+    s0 = srcs[0]
+    if s0.dim() == 3 and s0.dtype == torch.uint8 and s0.shape[2] == 3:
+        fmt, (Hs, Ws) = RECTIFY_SRC_U8_HWC, s0.shape[:2]
+    elif s0.dim() == 3 and s0.shape[0] == 3 and s0.dtype in (torch.uint8, torch.float32):
+        fmt, (Hs, Ws) = RECTIFY_SRC_U8_CHW if s0.dtype == torch.uint8 else RECTIFY_SRC_F32_CHW, s0.shape[1:]
+    else:
+        raise ValueError("rectify: a source is an (H,W,3) uint8, (3,H,W) uint8 or (3,H,W) fp32 tensor")
+    if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != RECTIFY_RECORD_FLOATS or records.shape[0] < 1:
+        raise ValueError(f"rectify: records must be an (n_img, {RECTIFY_RECORD_FLOATS}) fp32 tensor")
+    n = records.shape[0]
+    if out is None and maps is None:
+        raise ValueError("rectify: no output requested")
+    ref = out if out is not None else maps
+    if ref.dim() != 4:
+        raise ValueError("rectify: out is (n_img,3,Hd,Wd), maps is (n_img,2,Hd,Wd)")
+    Hd, Wd = (hd, wd) if hd is not None and wd is not None else ref.shape[-2:]
+    d = RectifyDesc()
+    if out is not None:
+        if out.dtype not in (torch.float32, torch.uint8) or tuple(out.shape) != (n, 3, Hd, Wd):
+            raise ValueError("rectify: out must be an (n_img,3,Hd,Wd) fp32 or uint8 tensor")
+        d.out, d.out_dtype = out.data_ptr(), _IMG_DT[out.dtype]
+        d.src[0] = srcs[0].data_ptr()
+        d.src[1] = srcs[-1].data_ptr()
+    if maps is not None:
+        if maps.dtype != torch.float32 or tuple(maps.shape) != (n, 2, Hd, Wd):
+            raise ValueError("rectify: maps must be an (n_img,2,Hd,Wd) fp32 tensor")
+        d.maps = maps.data_ptr()
+    d.records, d.n_src, d.n_img, d.Hs, d.Ws, d.Hd, d.Wd = records.data_ptr(), len(srcs), n, Hs, Ws, Hd, Wd
+    d.src_format, d.round, d.order = fmt, int(bool(round)), order
+    with torch.cuda.device(records.device):
+        _check(load().s2m2_rectify(ctypes.byref(d), _stream()), "s2m2_rectify")

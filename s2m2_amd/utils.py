@@ -10,6 +10,10 @@ image_utils.py) -- SURVEY.md section 8f rows 1-2: same names, arguments and retu
 * ``compute_confidence_scores``  the calibration objective (calibration/base.py:15-36 called 20 x 5 times one pair at a time by
   calibration/cem.py:66-72) for a whole population of rectified pairs at once: one batched forward, or sharded over the ranks of a
   ``torch.distributed`` group
+* the calibration glue in front of the forward -- ``parse_xml_calibration``, ``load_calibration_data``, ``euler_to_rotation_matrix``,
+  ``create_delta_rotation``, ``apply_delta_rotation``, ``build_camera_matrix``, ``compute_stereo_rectification`` (calib_utils.py),
+  ``rectify_images`` (image_utils.py:108-136), ``evaluate_sample`` (calibration/base.py), ``cem_calibration`` (calibration/cem.py) and
+  ``rectify_population`` -- lives in ``s2m2_amd.rectify`` (HIP kernel ``s2m2_rectify``) and is re-exported here
 """
 from __future__ import annotations
 
@@ -20,6 +24,9 @@ import torch
 
 from . import hip
 from .model import S2M2
+from .rectify import (apply_delta_rotation, build_camera_matrix, cem_calibration, compute_stereo_rectification,  # noqa: F401  (re-exports)
+                      create_delta_rotation, euler_to_rotation_matrix, evaluate_sample, load_calibration_data, parse_xml_calibration,
+                      rectify_images, rectify_population)
 from .spec import MODEL_CONFIGS
 
 
