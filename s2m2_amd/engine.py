@@ -18,7 +18,9 @@ time the token layout of the attention blocks.  Stage map (reference file:line -
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from functools import cached_property
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -28,9 +30,66 @@ from . import hip, pack
 Tensor = torch.Tensor
 
 
-class Spec(tuple):
-    """(packed weight, packed bias, KH, KW, Cout padded) of one K5 layer; ``korder`` = K order of the packed weight (s2m2_conv2d)."""
-    korder = 0
+@dataclass(eq=False)
+class Layer:
+    """One packed K5 layer: weight (``cout`` rows = Cout padded to 8; K = (tap, channel) in K order 0, the MFMA fragment stream of
+    pack.pack_conv_frag in K order 2 -- ``korder`` of s2m2_conv2d), fp32 bias, kernel size.  The layer owns the packings derived from
+    its weight: each is built on first use and lives exactly as long as the layer."""
+    weight: Tensor
+    bias: Optional[Tensor]
+    kh: int
+    kw: int
+    cout: int
+    korder: int = 0
+
+    def __post_init__(self):
+        # what the predicates below rely on: every packing keeps one row per output channel, and only spatial layers are fragment streams
+        assert self.weight.shape[0] == self.cout and (not self.korder or self.kh * self.kw > 1), (tuple(self.weight.shape), self.cout, self.korder)
+
+    @property
+    def is_1x1(self) -> bool:
+        return self.kh == 1 and self.kw == 1
+
+    def plain_1x1(self, cin: int, cout: int) -> bool:
+        """a 1x1 layer cin -> cout (padded widths) in K order 0: what K9, K10's neighbours, K11 and the fused K12 head take"""
+        return self.is_1x1 and not self.korder and tuple(self.weight.shape) == (cout, cin)
+
+    def frag_3x3(self, c: int) -> bool:
+        """a 3x3 layer c -> c packed as a fragment stream (K order 2): the spatial layers of K14"""
+        return self.korder == 2 and self.kh == 3 and self.kw == 3 and self.cout == c and self.weight.numel() == 9 * c * c
+
+    @cached_property
+    def wsum(self) -> Tensor:
+        """row sums of the packed weight: the pre-LayerNorm correction term of K5 / K9"""
+        return self.weight.float().sum(dim=1).contiguous()
+
+    @cached_property
+    def chain_frag(self) -> Tensor:
+        """a 1x1 weight in the MFMA-fragment order of the direct K9 form"""
+        return pack.chain_frag(self.weight)
+
+    @cached_property
+    def pw_frag(self) -> Tensor:
+        """a 1x1 weight in the fragment order of K11"""
+        return pack.pw_frag(self.weight)
+
+    @cached_property
+    def narrow_frag(self) -> Tensor:
+        """a spatial weight in the fragment order of K12"""
+        return pack.narrow_frag(self.weight, self.kh * self.kw)
+
+    @cached_property
+    def head_frag(self) -> Tensor:
+        """a 1x1 weight as the head fused behind a K12 3x3 layer"""
+        return pack.head_frag(self.weight)
+
+    def stage(self, act: int, frag: bool = True, ln: bool = False):
+        """the layer as a stage of a K9 chain (hip.mlp_chain): direct form (``frag``) or LDS-staged; ln: pre-LayerNorm folded in"""
+        return (self.chain_frag if frag else self.weight, self.bias, act, self.wsum if ln else None)
+
+    def fan(self, ln: bool = True):
+        """the layer as the fan-out stage of a direct K9 launch (hip.mlp_chain ``fan``, hip.mlp_fan)"""
+        return (self.chain_frag, self.bias, self.wsum if ln else None)
 
 
 def pe_tables(h: int, w: int, device, pe_dim: int = 32) -> Tuple[Tensor, Tensor]:
@@ -89,15 +148,15 @@ class Engine:
         self.output_upsample = model.output_upsample
         self.device = next(model.parameters()).device
         self.p: Dict[str, Tensor] = {n: q.detach().to(self.device, torch.float32) for n, q in model.named_parameters()}
-        self._packed: Dict[object, Spec] = {}
+        self._layers: Dict[object, Layer] = {}       # every packed layer, by what it was packed from (std / merged / convT2)
+        # packings built from more than one layer (the dual heads and K10 fragment stream of a FeatureFusion, the stem's fp32 copies, K13's
+        # per-step weights and vectors) and the identity chain of _normed_like_the_forward, by name: see composite()
+        self._composites: Dict[object, object] = {}
+        self._supported: Dict[tuple, object] = {}    # answers of hip.<name>_supported for this dtype, see supported()
         self._pe_cache: Dict[Tuple[int, int], Tuple[Tensor, Tensor]] = {}
         self._bufs: Dict[object, Tensor] = {}
         self._plans: Dict[object, object] = {}       # recorded refinement plans of EAGER calls (never evicted by zeros(): a plan owns the
         self._ns = None                              # tensors it returns); scratch namespace, see zeros()
-        self._wsum: Dict[int, Tensor] = {}
-        self._chain_ok: Dict[object, bool] = {}
-        self._fusion_ok: Dict[object, bool] = {}
-        self._wfrag = {}
         # One path per layer: which kernel form a layer takes follows from dtype and width alone (fp16 at C = 128 / 256: the direct forms of
         # K9 / K10 and the fragment-stream K5; other widths / fp32: the LDS-staged forms).  Two switches remain:
         # S2M2_FUSE_K1LN=0: K1 normalises the tokens itself (s2m2_ln_corr) instead of reading the LayerNorm output of the K9 launch that
@@ -134,11 +193,11 @@ class Engine:
         self.k1_events = None                        # bench.py: list collecting (start, end) HIP events around K1
 
     # ---- weight packing (once per engine) ------------------------------------------------------------
-    def std(self, name: str, splits: Optional[Sequence[Tuple[int, int]]] = None, transposed: bool = False, frag: bool = True) -> Spec:
+    def std(self, name: str, splits: Optional[Sequence[Tuple[int, int]]] = None, transposed: bool = False, frag: bool = True) -> Layer:
         """One nn.Conv2d / nn.Linear (or stride-1 nn.ConvTranspose2d when ``transposed``) as a K5 weight.  frag=False: the layer is
         launched with a stride (or its epilogue needs two operands: the GRU blend stays on the v3 tiles), keep K order 0."""
         key = (name, tuple(splits) if splits else None, transposed, bool(frag))     # frag selects the packing (K order 0 / 2)
-        s = self._packed.get(key)
+        s = self._layers.get(key)
         if s is None:
             w = self.p[name + ".weight"]
             if transposed:
@@ -148,15 +207,15 @@ class Engine:
             cin_p = sum(pd for _, pd in splits) if splits else pack.pad8(w.shape[1])
             frag = frag and pack.frag_eligible(pack.pad8(w.shape[0]), cin_p, w.shape[2], w.shape[3], self.dtype)
             wp = pack.pack_conv_frag(w, self.dtype, splits) if frag else pack.pack_conv(w, self.dtype, splits)
-            s = Spec((wp, pack.pack_bias(self.p.get(name + ".bias"), w.shape[0]), w.shape[2], w.shape[3], pack.pad8(w.shape[0])))
-            s.korder = 2 if frag else 0                            # spatial layers of wide tensors: weights as an MFMA fragment stream
-            self._packed[key] = s
+            # (K order 2: spatial layers of wide tensors, weights as an MFMA fragment stream)
+            s = self._layers[key] = Layer(wp, pack.pack_bias(self.p.get(name + ".bias"), w.shape[0]), w.shape[2], w.shape[3],
+                                          pack.pad8(w.shape[0]), 2 if frag else 0)
         return s
 
-    def merged(self, key: str, parts: Sequence[Tuple[str, int, float, bool]], cin_total: int) -> Spec:
+    def merged(self, key: str, parts: Sequence[Tuple[str, int, float, bool]], cin_total: int) -> Layer:
         """Several layers that read the same input tensor(s) stacked along Cout (each padded to 8 rows), every layer looking at its
         own channel window [offset, offset+Cin_i) of the combined input.  parts: (name, cin_offset, weight_scale, transposed)."""
-        s = self._packed.get(key)
+        s = self._layers.get(key)
         if s is None:
             rows, biases = [], []
             kh = kw = 1
@@ -176,57 +235,70 @@ class Engine:
                     bb[:co] = self.p[name + ".bias"]
                 biases.append(bb)
             wp = torch.cat(rows, 0)
-            s = Spec((wp.to(self.dtype).contiguous(), torch.cat(biases).float().contiguous(), kh, kw, wp.shape[0]))
-            if pack.frag_eligible(wp.shape[0], cin_total, kh, kw, self.dtype):
-                w4 = wp.reshape(wp.shape[0], kh, kw, cin_total).permute(0, 3, 1, 2)            # back to (Cout, Cin, KH, KW): rows are padded already
-                s = Spec((pack.pack_conv_frag(w4, self.dtype, [(cin_total, cin_total)]), s[1], kh, kw, wp.shape[0]))
-                s.korder = 2
-            self._packed[key] = s
+            cout = wp.shape[0]
+            s = Layer(wp.to(self.dtype).contiguous(), torch.cat(biases).float().contiguous(), kh, kw, cout)
+            if pack.frag_eligible(cout, cin_total, kh, kw, self.dtype):
+                # (the K-order-0 copy lives until the stream is packed: the sequence of allocations, and with it the allocator's block layout
+                # and torch.cuda.memory_allocated() of a packed engine, is what it always was)
+                w4 = wp.reshape(cout, kh, kw, cin_total).permute(0, 3, 1, 2)                   # back to (Cout, Cin, KH, KW): rows are padded already
+                s = Layer(pack.pack_conv_frag(w4, self.dtype, [(cin_total, cin_total)]), s.bias, kh, kw, cout, 2)
+            self._layers[key] = s
         return s
 
-    def convT2(self, name: str) -> Tuple[Spec, int]:
+    def convT2(self, name: str) -> Tuple[Layer, int]:
         """nn.ConvTranspose2d(kernel 2, stride 2) as the pixel-shuffle GEMM of K5."""
         key = (name, "T2")
-        s = self._packed.get(key)
+        s = self._layers.get(key)
         if s is None:
             w = self.p[name + ".weight"]
             wp, cp = pack.pack_convT_2x2s2(w, self.dtype)
-            s = Spec((wp, pack.pack_bias_shuffle(self.p.get(name + ".bias"), w.shape[1]), 1, 1, 4 * cp))
-            self._packed[key] = s
-        return s, s[4] // 4
+            s = self._layers[key] = Layer(wp, pack.pack_bias_shuffle(self.p.get(name + ".bias"), w.shape[1]), 1, 1, 4 * cp)
+        return s, s.cout // 4
 
-    def cconv(self, spec: Spec, srcs, ln: bool = False, **kw) -> Tensor:
+    def composite(self, key, build):
+        """a packing that derives from more than one layer (or from none: the identity chain), built once per engine under ``key``"""
+        ent = self._composites.get(key)
+        if ent is None:
+            ent = self._composites[key] = build()
+        return ent
+
+    def supported(self, name: str, *args):
+        """hip.<name>_supported(*args, dtype), asked once per (name, args): every query is a ctypes call"""
+        key = (name,) + args
+        ok = self._supported.get(key)
+        if ok is None:
+            ok = self._supported[key] = getattr(hip, name + "_supported")(*args, self.dtype)
+        return ok
+
+    def cconv(self, spec: Layer, srcs, ln: bool = False, **kw) -> Tensor:
         """K5 launch.  ln: the layer is a pre-LayerNorm (no affine, attentions.py:117) followed by this 1x1 layer, folded into
         the kernel -- needs the row sums of the packed weight, computed once per layer."""
-        wp, bp, kh, kw_, cout = spec
+        wp, bp, kh, kw_, cout = spec.weight, spec.bias, spec.kh, spec.kw, spec.cout
+        act, cin = kw.get("act", hip.ACT_NONE), sum(t.shape[-1] for t in srcs)
+        plain_act = act in (hip.ACT_NONE, hip.ACT_GELU, hip.ACT_RELU)
         # a plain 1x1 C -> C layer (C = 128 / 256, fp16, optionally + residual): the direct form of K9 as a one-stage chain -- the weight as
         # MFMA fragments straight into the operand registers instead of K5's LDS-staged K tiles
-        if (kh == 1 and kw_ == 1 and len(srcs) == 1 and srcs[0].shape[-1] == cout and tuple(wp.shape) == (cout, cout)
-                and not getattr(spec, "korder", 0) and set(kw) <= {"act", "epi", "aux0"}
-                and kw.get("act", hip.ACT_NONE) in (hip.ACT_NONE, hip.ACT_GELU, hip.ACT_RELU)
+        if (len(srcs) == 1 and spec.plain_1x1(cout, cout) and cin == cout and set(kw) <= {"act", "epi", "aux0"} and plain_act
                 and kw.get("epi", hip.EPI_NONE) in (hip.EPI_NONE, hip.EPI_ADD) and ("aux0" in kw) == (kw.get("epi", hip.EPI_NONE) == hip.EPI_ADD)
                 and ("aux0" not in kw or tuple(kw["aux0"].shape) == tuple(srcs[0].shape)) and self.chain_frag_ok(cout)):
-            st = [(self.wfrag(spec), bp, kw.get("act", hip.ACT_NONE), self.wsum(spec) if ln else None)]
+            st = [spec.stage(act, ln=ln)]
             if "aux0" in kw:
                 return hip.mlp_chain(srcs[0], st, res=kw["aux0"], res_stage=0, frag=True)
             return hip.mlp_chain(srcs[0], st, frag=True)
         # any other plain 1x1 layer (rectangular, up to four concatenated sources, ConvTranspose 2x2 s2 included): K11, the direct form
         # (profiles/r04/pwbench.txt: 1.3 - 2.4 x the K5 launch per layer; ab_pw_direct.txt: 8.87 vs 9.00 ms per pair)
-        if (kh == 1 and kw_ == 1 and not ln and not getattr(spec, "korder", 0) and len(srcs) <= 4 and set(kw) <= {"act", "shuffle2"}
-                and kw.get("act", hip.ACT_NONE) in (hip.ACT_NONE, hip.ACT_GELU, hip.ACT_RELU)
-                and wp.shape[1] == sum(t.shape[-1] for t in srcs) and self.pw_ok(wp.shape[1], cout)):
-            return hip.pw_direct(srcs, self.wpw(spec), bp, cout, act=kw.get("act", hip.ACT_NONE), shuffle2=kw.get("shuffle2", 0))
+        if (spec.plain_1x1(cin, cout) and not ln and len(srcs) <= 4 and set(kw) <= {"act", "shuffle2"} and plain_act
+                and self.pw_ok(cin, cout)):
+            return hip.pw_direct(srcs, spec.pw_frag, bp, cout, act=act, shuffle2=kw.get("shuffle2", 0))
         # spatial layers K5 would run on its LDS-staged tiles -- on an 8- / 16-channel tensor (the (disp, rgb) / (disp, conf, occ) side inputs,
         # the stem's output), or with few output channels (the mask / update heads, disp_feat.2): K12, the pixel-split direct form
         # (profiles/r04/narrowbench.txt)
-        if (kh > 1 and not ln and not getattr(spec, "korder", 0) and len(srcs) <= 2 and srcs[0].dim() == 4 and set(kw) <= {"act", "stride"}
-                and kw.get("act", hip.ACT_NONE) in (hip.ACT_NONE, hip.ACT_GELU, hip.ACT_RELU)
-                and wp.shape[1] == kh * kw_ * sum(t.shape[-1] for t in srcs)
-                and self.narrow_ok(kh, kw_, kw.get("stride", 1), sum(t.shape[-1] for t in srcs), cout)):
-            return hip.conv_narrow(srcs, self.wnarrow(spec, kh * kw_), bp, kh, kw_, cout, stride=kw.get("stride", 1), act=kw.get("act", hip.ACT_NONE))
+        if (kh > 1 and not ln and not spec.korder and len(srcs) <= 2 and srcs[0].dim() == 4 and set(kw) <= {"act", "stride"} and plain_act
+                and wp.shape[1] == kh * kw_ * cin and self.narrow_ok(kh, kw_, kw.get("stride", 1), cin, cout)):
+            return hip.conv_narrow(srcs, spec.narrow_frag, bp, kh, kw_, cout, stride=kw.get("stride", 1), act=act)
         if ln:
-            kw["ln_wsum"] = self.wsum(spec)
-        if getattr(spec, "korder", 0):
+            kw["ln_wsum"] = spec.wsum
+        if spec.korder:
             kw["korder"] = spec.korder
         return hip.conv2d(srcs, wp, bp, kh, kw_, cout, **kw)
 
@@ -249,11 +321,10 @@ class Engine:
         mean, rounded to the activation dtype like the stand-alone K7 launch it replaces)."""
         spec = self.std(p + ".1")
         c = x.shape[-1]
-        pooled = spec[2] == 1 and spec[3] == 1 and x.dim() == 4 and x.shape[1] >= 2 and x.shape[2] >= 2
-        if (pooled and tuple(spec[0].shape) in ((c, c), (2 * c, c)) and spec[4] == spec[0].shape[0] and not getattr(spec, "korder", 0)
-                and self.chain_frag_ok(c)):
+        pooled = spec.is_1x1 and x.dim() == 4 and x.shape[1] >= 2 and x.shape[2] >= 2
+        if pooled and (spec.plain_1x1(c, c) or spec.plain_1x1(c, 2 * c)) and self.chain_frag_ok(c):
             # pooled 1x1 C -> C / C -> 2C: a fan-out-only launch of the direct K9 form, the 2x2 mean formed while the row tile is loaded
-            return hip.mlp_fan(x, self.wfrag(spec), spec[1], None, pool2=True)
+            return hip.mlp_fan(x, *spec.fan(ln=False), pool2=True)
         if pooled:
             return self.cconv(spec, [x], pool2=True)
         return self.cconv(spec, [hip.resample2x(x, 0)])
@@ -263,7 +334,7 @@ class Engine:
         resampling (per-pixel interpolation weights sum to 1, so the bias passes through too): the GEMM runs on the coarse grid
         -- a quarter of the pixels -- and K7 resamples Cout channels instead of Cin."""
         spec = self.std(p + ".1")
-        if spec[2] == 1 and spec[3] == 1:
+        if spec.is_1x1:
             return hip.resample2x(self.cconv(spec, [x]), 1)
         return self.cconv(spec, [hip.resample2x(x, 1)])
 
@@ -271,65 +342,53 @@ class Engine:
         """ConvBlock2D (attentions.py:255-281): conv3-GELU-conv3 + conv1-ReLU-conv1."""
         c0, c2 = self.std(p + ".convs_1x.0"), self.std(p + ".convs_1x.2")
         c = z.shape[-1]
-        same = c0[4] == c and c2[4] == c
+        same = c0.cout == c and c2.cout == c
         if (self.use_convblock and same and z.dim() == 4 and z.shape[0] * z.shape[1] * z.shape[2] <= self.convblock_maxpix
                 and (c == 128 or self.convblock_c256) and self.chain_frag_ok(c) and self.convblock_ok(c, z.shape[1], z.shape[2])):
             k0, k2 = self.std(p + ".convs.0"), self.std(p + ".convs.2")
-            if (getattr(k0, "korder", 0) == 2 and getattr(k2, "korder", 0) == 2 and k0[2] == 3 and k0[3] == 3 and k2[2] == 3 and k2[3] == 3
-                    and k0[4] == c and k2[4] == c and k0[0].numel() == 9 * c * c and k2[0].numel() == 9 * c * c
-                    and tuple(c0[0].shape) == (c, c) and tuple(c2[0].shape) == (c, c)):
+            if k0.frag_3x3(c) and k2.frag_3x3(c) and c0.plain_1x1(c, c) and c2.plain_1x1(c, c):
                 # the whole block -- 1x1 branch, 3x3 - GELU - 3x3, the final add -- as ONE K14 launch (the coarse grids: latency chains)
-                return hip.conv_block(z, k0[0], k0[1], k2[0], k2[1], self.wfrag(c0), c0[1], self.wfrag(c2), c2[1])
+                return hip.conv_block(z, k0.weight, k0.bias, k2.weight, k2.bias, c0.chain_frag, c0.bias, c2.chain_frag, c2.bias)
         if same and self.chain_frag_ok(c):                         # the 1x1 branch as one K9 launch (direct form)
-            b = hip.mlp_chain(z, [(self.wfrag(c0), c0[1], hip.ACT_RELU, None), (self.wfrag(c2), c2[1], hip.ACT_NONE, None)], frag=True)
+            b = hip.mlp_chain(z, [c0.stage(hip.ACT_RELU), c2.stage(hip.ACT_NONE)], frag=True)
         elif same and self.chain_ok(c):
-            b = hip.mlp_chain(z, [(c0[0], c0[1], hip.ACT_RELU, None), (c2[0], c2[1], hip.ACT_NONE, None)])
+            b = hip.mlp_chain(z, [c0.stage(hip.ACT_RELU, frag=False), c2.stage(hip.ACT_NONE, frag=False)])
         else:
             b = self.cconv(c2, [self.cconv(c0, [z], act=hip.ACT_RELU)])
         t = self.cconv(self.std(p + ".convs.0"), [z], act=hip.ACT_GELU)
         return self.cconv(self.std(p + ".convs.2"), [t], epi=hip.EPI_ADD, aux0=b)
 
+    def gate_fusion(self, p: str, c: int) -> Layer:
+        """[feature_gate.0 | feature_fusion.0] of a FeatureFusion stacked along Cout: both first layers read cat(z0, z1), one GEMM"""
+        return self.merged(p + "|gate+fusion", [(p + ".feature_gate.0", 0, 1.0, False), (p + ".feature_fusion.0", 0, 1.0, False)], 2 * c)
+
     def dual_heads(self, p: str):
         """[gate.2 | fusion.2] stacked along K (the channel order of the hidden tensor) + the two biases"""
-        key = p + "|gate.2+fusion.2"
-        dual = self._packed.get(key)
-        if dual is None:
+        def build():
             g2, f2 = self.std(p + ".feature_gate.2"), self.std(p + ".feature_fusion.2")
-            dual = self._packed[key] = (torch.cat([g2[0], f2[0]], dim=1).contiguous(), g2[1], f2[1])
-        return dual
+            return torch.cat([g2.weight, f2.weight], dim=1).contiguous(), g2.bias, f2.bias
+        return self.composite(p + "|gate.2+fusion.2", build)
 
-    def fusion_ok(self, c: int) -> bool:
-        """K10 exists for this width in one of its forms (LDS-staged: 128 / 256 in both dtypes; direct: fp16 128 / 192 / 256 / 384)"""
-        ok = self._fusion_ok.get(c)
-        if ok is None:
-            ok = self._fusion_ok[c] = hip.feature_fusion_supported(c, self.dtype) or self.fusion_frag_ok(c)
-        return ok
-
-    def k10(self, p: str, z0: Tensor, z1: Tensor, first: Spec, z1_coarse: bool = False) -> Tensor:
+    def k10(self, p: str, z0: Tensor, z1: Tensor, first: Layer, z1_coarse: bool = False) -> Tensor:
         """one K10 launch; fp16 at C = 128 / 256 takes the direct form (weights as one fragment stream, permuted once per layer)"""
         dual = self.dual_heads(p)
-        c = z0.shape[-1]
-        if self.fusion_frag_ok(c):
-            key = p + "|k10 fragment stream"
-            ws = self._packed.get(key)
-            if ws is None:
-                ws = self._packed[key] = pack.fusion_frag(first[0], dual[0])
-            return hip.feature_fusion(z0, z1, ws, first[1], None, dual[1], dual[2], z1_coarse=z1_coarse, frag=True)
-        return hip.feature_fusion(z0, z1, first[0], first[1], dual[0], dual[1], dual[2], z1_coarse=z1_coarse)
+        if self.fusion_frag_ok(z0.shape[-1]):
+            ws = self.composite(p + "|k10 fragment stream", lambda: pack.fusion_frag(first.weight, dual[0]))
+            return hip.feature_fusion(z0, z1, ws, first.bias, None, dual[1], dual[2], z1_coarse=z1_coarse, frag=True)
+        return hip.feature_fusion(z0, z1, first.weight, first.bias, dual[0], dual[1], dual[2], z1_coarse=z1_coarse)
 
     def fusion_up_ok(self, p: str, c: int, pu: str) -> bool:
         """the decoder's fusion takes the coarse-grid form (1x1 up_conv on the coarse grid, K10 reads it through the bilinear resampling)"""
         spec = self.std(pu + ".1")
-        first = self.merged(p + "|gate+fusion", [(p + ".feature_gate.0", 0, 1.0, False), (p + ".feature_fusion.0", 0, 1.0, False)], 2 * c)
-        return (spec[2] == 1 and spec[3] == 1 and spec[4] == c and first[2] == 1 and first[3] == 1
+        return (spec.is_1x1 and spec.cout == c and self.gate_fusion(p, c).is_1x1
                 and self.p[p + ".feature_gate.0.weight"].shape[0] == c and self.fusion_ok(c))
 
-    def up_tail(self, p: str, c_fine: int, pu: str, c_coarse: int) -> Optional[Spec]:
+    def up_tail(self, p: str, c_fine: int, pu: str, c_coarse: int) -> Optional[Layer]:
         """the decoder's up_conv as a fan-out stage of the K9 launch that produces its input (attn_ffn ``tail``): a plain C -> C 1x1 layer in
         front of a coarse-grid fusion, direct K9 form available"""
         spec = self.std(pu + ".1")
-        if (self.coarse_fuse and self.fusion_up_ok(p, c_fine, pu) and tuple(spec[0].shape) == (c_coarse, c_coarse) and c_fine == c_coarse
-                and not getattr(spec, "korder", 0) and self.chain_frag_ok(c_coarse)):
+        if (self.coarse_fuse and self.fusion_up_ok(p, c_fine, pu) and spec.plain_1x1(c_coarse, c_coarse) and c_fine == c_coarse
+                and self.chain_frag_ok(c_coarse)):
             return spec
         return None
 
@@ -337,11 +396,10 @@ class Engine:
         """fusion(z0, up_conv(xc)) of the decoders (unet.py:98-110, stacked_MRT.py:113-121): the 1x1 up_conv runs on the coarse grid
         (see up()) and K10 reads its output through the bilinear resampling -- no stand-alone K7 launch, no upsampled tensor.
         up_pre: up_conv(xc) on the coarse grid, where the launch that produced xc computed it (up_tail)."""
-        spec = self.std(pu + ".1")
         c = z0.shape[-1]
-        first = self.merged(p + "|gate+fusion", [(p + ".feature_gate.0", 0, 1.0, False), (p + ".feature_fusion.0", 0, 1.0, False)], 2 * c)
         if self.fusion_up_ok(p, c, pu):
-            return self.k10(p, z0, up_pre if up_pre is not None else self.cconv(spec, [xc]), first, z1_coarse=True)
+            z1 = up_pre if up_pre is not None else self.cconv(self.std(pu + ".1"), [xc])
+            return self.k10(p, z0, z1, self.gate_fusion(p, c), z1_coarse=True)
         return self.fusion(p, z0, self.up(pu, xc))
 
     def fusion(self, p: str, z0: Tensor, z1: Tensor) -> Tensor:
@@ -349,8 +407,8 @@ class Engine:
         Both first layers read cat(z0, z1): one GEMM; the gate mix and the final add are epilogues."""
         c = z0.shape[-1]
         cg = self.p[p + ".feature_gate.0.weight"].shape[0]
-        spec = self.merged(p + "|gate+fusion", [(p + ".feature_gate.0", 0, 1.0, False), (p + ".feature_fusion.0", 0, 1.0, False)], 2 * c)
-        if spec[2] == 1 and spec[3] == 1 and cg == c and self.fusion_ok(c):
+        spec = self.gate_fusion(p, c)
+        if spec.is_1x1 and cg == c and self.fusion_ok(c):
             return self.k10(p, z0, z1, spec)                       # K10: the whole block in one launch, h never leaves the CU
         gf = self.cconv(spec, [z0, z1], act=hip.ACT_GELU)
         if cg % 64 == 0:
@@ -361,6 +419,38 @@ class Engine:
         m = self.cconv(self.std(p + ".feature_gate.2"), [gf[..., :cg]], act=hip.ACT_SIGMOID, epi=hip.EPI_GATEMIX, aux0=z0, aux1=z1)
         return self.cconv(self.std(p + ".feature_fusion.2"), [gf[..., cg:]], epi=hip.EPI_ADD, aux0=m)
 
+    # ---- which kernel forms exist for this dtype (thin names over supported(); the two switches gate K12 and K13 here) ----------
+    def chain_ok(self, c: int) -> bool:
+        """K9, LDS-staged form (fp32; fp16 at C = 384 / 512)"""
+        return self.supported("mlp_chain", c)
+
+    def chain_frag_ok(self, c: int) -> bool:
+        """K9, direct form"""
+        return self.supported("mlp_chain_frag", c)
+
+    def fusion_frag_ok(self, c: int) -> bool:
+        return self.supported("feature_fusion_frag", c)
+
+    def fusion_ok(self, c: int) -> bool:
+        """K10 exists for this width in one of its forms (LDS-staged: 128 / 256 in both dtypes; direct: fp16 128 / 192 / 256 / 384)"""
+        return self.supported("feature_fusion", c) or self.fusion_frag_ok(c)
+
+    def pw_ok(self, k: int, cout: int) -> bool:
+        """K11 (hip.pw_direct) for a (cout, k) 1x1 layer"""
+        return self.supported("pw_direct", k, cout)
+
+    def narrow_ok(self, kh: int, kw: int, stride: int, cin: int, cout: int) -> bool:
+        """K12 (hip.conv_narrow) for this spatial layer on a cin-channel tensor"""
+        return self.use_k12 and self.supported("conv_narrow", kh, kw, stride, cin, cout)
+
+    def convblock_ok(self, c: int, h: int, w: int) -> bool:
+        """K14 takes a ConvBlock2D of this width on this grid"""
+        return self.supported("conv_block", c, h, w)
+
+    def row_ok(self, z: Tensor, nh: int) -> bool:
+        """K13 takes the 1-D attention steps on this tensor"""
+        return self.use_rowfuse and z.dim() == 4 and self.supported("row_attn", z.shape[-1], nh, z.shape[2])
+
     # ---- attention -----------------------------------------------------------------------------------
     def pe(self, h: int, w: int) -> Tuple[Tensor, Tensor]:
         key = (h, w)
@@ -368,7 +458,7 @@ class Engine:
             self._pe_cache[key] = pe_tables(h, w, self.device)
         return self._pe_cache[key]
 
-    def qkv_spec(self, p: str) -> Spec:
+    def qkv_spec(self, p: str) -> Layer:
         """[q | k | v] of one attention module (attentions.py:24-28,71-74) stacked along Cout: one GEMM"""
         c = self.p[p + ".q.weight"].shape[1]
         return self.merged(p + "|qkv", [(p + ".q", 0, 1.0, False), (p + ".k", 0, 1.0, False), (p + ".v", 0, 1.0, False)], c)
@@ -376,8 +466,8 @@ class Engine:
     def qkv(self, p: str, x: Tensor) -> Tensor:
         spec = self.qkv_spec(p)
         c = x.shape[-1]
-        if spec[2] == 1 and spec[3] == 1 and spec[4] == 3 * c and self.chain_frag_ok(c):
-            return hip.mlp_fan(x, self.wfrag(spec), spec[1], self.wsum(spec))     # direct form: fragments straight into registers
+        if spec.is_1x1 and spec.cout == 3 * c and self.chain_frag_ok(c):
+            return hip.mlp_fan(x, *spec.fan())                                   # direct form: fragments straight into registers
         return self.cconv(spec, [x], ln=True)                                    # pre-LayerNorm folded into the K5 launch
 
     def attn_core(self, p: str, z: Tensor, nh: int, two_d: bool, cross: bool, use_pe: bool, qkv: Optional[Tensor] = None) -> Tensor:
@@ -397,24 +487,7 @@ class Engine:
             o = hip.attention(q, k, v, nh, swap_halves=cross)
         return o.reshape(n, h, w, c)
 
-    def wsum(self, spec: Spec) -> Tensor:
-        """row sums of a packed weight (the pre-LayerNorm correction term of K5 / K9), computed once per layer"""
-        wp = spec[0]
-        ws = self._wsum.get(wp.data_ptr())
-        if ws is None:
-            ws = wp.float().sum(dim=1).contiguous()
-            self._wsum[wp.data_ptr()] = ws
-        return ws
-
-    def wfrag(self, spec: Spec) -> Tensor:
-        """a packed 1x1 weight in the MFMA-fragment order of the direct K9 form (pack.chain_frag), permuted once per layer"""
-        wp = spec[0]
-        wf = self._wfrag.get(wp.data_ptr())
-        if wf is None:
-            wf = self._wfrag[wp.data_ptr()] = pack.chain_frag(wp)
-        return wf
-
-    def attn_ffn(self, pa: str, pf: str, o: Tensor, z: Tensor, ln_out=None, next_attn: Optional[str] = None, tail: Optional[Spec] = None):
+    def attn_ffn(self, pa: str, pf: str, o: Tensor, z: Tensor, ln_out=None, next_attn: Optional[str] = None, tail: Optional[Layer] = None):
         """z' = z + proj(o);  z' + ffn.2(GELU(ffn.0(LayerNorm(z')))) (attentions.py:311-321,347-355): one K9 launch when the width
         is supported, else three K5 launches (pre-LN folded into the first FFN layer).  ln_out = (gamma, beta, eps): the K9 launch also
         writes LayerNorm(result) * gamma + beta (kept in ``self._tokens_normed`` for K1, see features()).  next_attn: prefix of the
@@ -424,127 +497,57 @@ class Engine:
         proj, f0, f2 = self.std(pa + ".attn.proj"), self.std(pf + ".ffn.0"), self.std(pf + ".ffn.2")
         if ln_out is not None and not hip.mlp_chain_ln_out_supported(c, self.dtype):
             ln_out = None                                          # (widths without the LayerNorm output: K1 normalises the tokens itself)
-        # K1 places image row y on XCD y / (h / 8): hand the token rows of that eighth of every image to the same XCD
-        n, h, w, _ = z.shape
-        grp = ((h // 8) * w if h % 8 == 0 else 0) if ln_out is not None else 0
-        acts = (hip.ACT_NONE, hip.ACT_GELU, hip.ACT_NONE)
-        if self.chain_frag_ok(c):
-            # direct form: fragments straight into registers; the next attention's Q | K | V projection rides along as fan-out stages (one
-            # launch and one round trip of the rows less), or the launch that writes feature_tr_4x also writes K1's normalised tokens
-            st = [(self.wfrag(sp), sp[1], act, self.wsum(sp) if sp is f0 else None) for sp, act in zip((proj, f0, f2), acts)]
+        frag = self.chain_frag_ok(c)       # direct form: fragments straight into registers; else the LDS-staged form (fp32; fp16 at C = 384 / 512)
+        if frag or self.chain_ok(c):
+            st = [proj.stage(hip.ACT_NONE, frag), f0.stage(hip.ACT_GELU, frag, ln=True), f2.stage(hip.ACT_NONE, frag)]
+            extra = {}
             if ln_out is not None:
-                out, self._tokens_normed = hip.mlp_chain(o, st, res=z, res_stage=0, carry=True, ln_out=ln_out, xcd_group_rows=grp, frag=True)
-                return out, None
-            if next_attn is not None:
-                qs = self.qkv_spec(next_attn)
-                if qs[2] == 1 and qs[3] == 1 and qs[4] == 3 * c:
-                    return hip.mlp_chain(o, st, res=z, res_stage=0, carry=True, fan=(self.wfrag(qs), qs[1], self.wsum(qs)), frag=True)
-            if tail is not None:
-                # the layer applied to the result next (the decoder's 1x1 up_conv on the coarse grid) as a fan-out stage of this launch: no
-                # LayerNorm fold, its own bias -> (result, up_conv(result))
-                return hip.mlp_chain(o, st, res=z, res_stage=0, carry=True, fan=(self.wfrag(tail), tail[1], None), frag=True)
-            return hip.mlp_chain(o, st, res=z, res_stage=0, carry=True, frag=True), None
-        if self.chain_ok(c):                                       # LDS-staged form (fp32; fp16 at C = 384 / 512)
-            st = [(sp[0], sp[1], act, self.wsum(sp) if sp is f0 else None) for sp, act in zip((proj, f0, f2), acts)]
+                # the launch that writes feature_tr_4x also writes K1's normalised tokens.  K1 places image row y on XCD y / (h / 8): hand
+                # the token rows of that eighth of every image to the same XCD
+                n, h, w, _ = z.shape
+                extra.update(ln_out=ln_out, xcd_group_rows=(h // 8) * w if h % 8 == 0 else 0)
+            elif frag:
+                # the next attention's Q | K | V projection rides along as fan-out stages (one launch and one round trip of the rows less), or
+                # the layer applied to the result next (the decoder's 1x1 up_conv on the coarse grid; no LayerNorm fold, its own bias)
+                qs = self.qkv_spec(next_attn) if next_attn is not None else None
+                if qs is not None and qs.is_1x1 and qs.cout == 3 * c:
+                    extra["fan"] = qs.fan()
+                elif tail is not None:
+                    extra["fan"] = tail.fan(ln=False)
+            if frag:
+                extra["frag"] = True
+            r = hip.mlp_chain(o, st, res=z, res_stage=0, carry=True, **extra)
             if ln_out is not None:
-                out, self._tokens_normed = hip.mlp_chain(o, st, res=z, res_stage=0, carry=True, ln_out=ln_out, xcd_group_rows=grp)
-                return out, None
-            return hip.mlp_chain(o, st, res=z, res_stage=0, carry=True), None
+                r, self._tokens_normed = r
+            return r if "fan" in extra else (r, None)              # with a fan-out stage: (result, qkv / up_conv(result))
         z = self.cconv(proj, [o], epi=hip.EPI_ADD, aux0=z)         # widths K9 does not take (C = 192): three K5 launches
         hdn = self.cconv(f0, [z], ln=True, act=hip.ACT_GELU)
         return self.cconv(f2, [hdn], epi=hip.EPI_ADD, aux0=z), None
-
-    def chain_frag_ok(self, c: int, dtype=None) -> bool:
-        """the direct form of K9 exists for this width (asked once per width: the query is a ctypes call)"""
-        ok = self._chain_ok.get(("frag", c))
-        if ok is None:
-            ok = self._chain_ok[("frag", c)] = hip.mlp_chain_frag_supported(c, self.dtype)
-        return ok
-
-    def fusion_frag_ok(self, c: int) -> bool:
-        ok = self._fusion_ok.get(("frag", c))
-        if ok is None:
-            ok = self._fusion_ok[("frag", c)] = hip.feature_fusion_frag_supported(c, self.dtype)
-        return ok
-
-    def pw_ok(self, k: int, cout: int) -> bool:
-        """K11 (hip.pw_direct) exists for a (cout, k) 1x1 layer in this dtype (asked once per shape)"""
-        ok = self._chain_ok.get(("pw", k, cout))
-        if ok is None:
-            ok = self._chain_ok[("pw", k, cout)] = hip.pw_direct_supported(k, cout, self.dtype)
-        return ok
-
-    def narrow_ok(self, kh: int, kw: int, stride: int, cin: int, cout: int) -> bool:
-        """K12 (hip.conv_narrow) exists for this spatial layer on a cin-channel tensor in this dtype (asked once per shape)"""
-        key = ("narrow", kh, kw, stride, cin, cout)
-        ok = self._chain_ok.get(key)
-        if ok is None:
-            ok = self._chain_ok[key] = self.use_k12 and hip.conv_narrow_supported(kh, kw, stride, cin, cout, self.dtype)
-        return ok
-
-    def wnarrow(self, spec: Spec, ntap: int) -> Tensor:
-        """a packed spatial weight in the fragment order of K12 (pack.narrow_frag), permuted once per layer"""
-        wp = spec[0]
-        wf = self._wfrag.get(("narrow", wp.data_ptr()))
-        if wf is None:
-            wf = self._wfrag[("narrow", wp.data_ptr())] = pack.narrow_frag(wp, ntap)
-        return wf
-
-    def wpw(self, spec: Spec) -> Tensor:
-        """a packed 1x1 weight in the fragment order of K11 (pack.pw_frag), permuted once per layer"""
-        wp = spec[0]
-        wf = self._wfrag.get(("pw", wp.data_ptr()))
-        if wf is None:
-            wf = self._wfrag[("pw", wp.data_ptr())] = pack.pw_frag(wp)
-        return wf
-
-    def chain_ok(self, c: int) -> bool:
-        ok = self._chain_ok.get(c)
-        if ok is None:
-            ok = self._chain_ok[c] = hip.mlp_chain_supported(c, self.dtype)
-        return ok
 
     def first_attn(self, p: str) -> str:
         """prefix of the attention module a block applies first (cross attention where the block has one)"""
         return p + (".cross_attn.attn" if (p + ".cross_attn.attn.q.weight") in self.p else ".self_attn.attn")
 
-    def convblock_ok(self, c: int, h: int, w: int) -> bool:
-        """K14 takes a ConvBlock2D of this width on this grid (asked once per shape)"""
-        key = ("convblock", c, h, w)
-        ok = self._chain_ok.get(key)
-        if ok is None:
-            ok = self._chain_ok[key] = hip.conv_block_supported(c, h, w, self.dtype)
-        return ok
-
-    def row_ok(self, z: Tensor, nh: int) -> bool:
-        """K13 takes the 1-D attention steps on this tensor (asked once per shape)"""
-        key = ("row", z.shape[-1], nh, z.shape[2])
-        ok = self._chain_ok.get(key)
-        if ok is None:
-            ok = self._chain_ok[key] = self.use_rowfuse and z.dim() == 4 and hip.row_attn_supported(z.shape[-1], nh, z.shape[2], self.dtype)
-        return ok
-
     def row_step(self, pa: str, pf: str, z: Tensor, nh: int, cross: bool, ln_out=None) -> Tensor:
         """One 1-D attention step -- pre-LN, Q | K | V, attention along the row (against the other view's row when ``cross``), proj + residual,
         pre-LN, FFN + residual (attentions.py:131-161 / :99-128 with :229-250) -- as ONE K13 launch.  The step's six layers in the row_attn
         packing and its twelve per-channel vectors are packed once per step (pack.rowattn_pack / rowattn_vectors)."""
-        key = ("rowstep", pa, pf, ln_out is not None)
-        ent = self._packed.get(key)
-        if ent is None:
+        def build():
             c = z.shape[-1]
             qs, proj, f0, f2 = self.qkv_spec(pa + ".attn"), self.std(pa + ".attn.proj"), self.std(pf + ".ffn.0"), self.std(pf + ".ffn.2")
-            ws = self.wsum(qs)
             cut = lambda t: (None, None, None) if t is None else (t[:c], t[c:2 * c], t[2 * c:])      # noqa: E731
-            wts = pack.rowattn_pack(torch.cat([qs[0], proj[0], f0[0], f2[0]], 0))
-            vec = pack.rowattn_vectors(cut(ws) + (self.wsum(f0),), cut(qs[1]) + (proj[1], f0[1], f2[1]), ln_out[:2] if ln_out is not None else None)
-            ent = self._packed[key] = (wts, vec)
+            wts = pack.rowattn_pack(torch.cat([qs.weight, proj.weight, f0.weight, f2.weight], 0))
+            vec = pack.rowattn_vectors(cut(qs.wsum) + (f0.wsum,), cut(qs.bias) + (proj.bias, f0.bias, f2.bias),
+                                       ln_out[:2] if ln_out is not None else None)
+            return wts, vec
+        wts, vec = self.composite(("rowstep", pa, pf, ln_out is not None), build)
         if ln_out is not None:
-            out, self._tokens_normed = hip.row_attn(z, nh, cross, ent[0], ent[1], ln_out_eps=ln_out[2])
+            out, self._tokens_normed = hip.row_attn(z, nh, cross, wts, vec, ln_out_eps=ln_out[2])
             return out
-        return hip.row_attn(z, nh, cross, ent[0], ent[1])
+        return hip.row_attn(z, nh, cross, wts, vec)
 
     def attn_block(self, p: str, z: Tensor, nh: int, two_d: bool, use_pe: bool = False, ln_out=None, qkv_in: Optional[Tensor] = None,
-                   next_block: Optional[str] = None, tail: Optional[Spec] = None):
+                   next_block: Optional[str] = None, tail: Optional[Layer] = None):
         """BasicAttnBlock (1-D, attentions.py:347-355) / GlobalAttnBlock (2-D, :311-321).  ln_out: see attn_ffn (last launch of the block).
         qkv_in: the Q | K | V projection of ``z`` for the block's first attention, if the launch that produced ``z`` computed it;
         next_block: prefix of the attention block applied to the result next (its first projection is computed here).
@@ -578,13 +581,11 @@ class Engine:
         dspec = self.std(p + ".down_conv2.1")
         c2 = z2.shape[-1]
         qs = self.qkv_spec(self.first_attn(blocks[0][0])) if blocks else None
-        if (self.coarse_fuse and qs is not None and dspec[2] == 1 and dspec[3] == 1 and tuple(dspec[0].shape) == (c2, c2) and dspec[4] == c2
-                and not getattr(dspec, "korder", 0) and z2.shape[1] >= 2 and z2.shape[2] >= 2 and self.chain_frag_ok(c2)
-                and qs[2] == 1 and qs[3] == 1 and qs[4] == 3 * c2):
+        if (self.coarse_fuse and qs is not None and dspec.plain_1x1(c2, c2) and z2.shape[1] >= 2 and z2.shape[2] >= 2
+                and self.chain_frag_ok(c2) and qs.is_1x1 and qs.cout == 3 * c2):
             # AvgPool2d(2) + down_conv2 (unet.py:24-29) and the first attention block's pre-LN + Q | K | V in ONE K9 launch: a one-stage chain
             # on the pooled tile with the projection as its fan-out stages
-            z3, q = hip.mlp_chain(z2, [(self.wfrag(dspec), dspec[1], hip.ACT_NONE, None)], fan=(self.wfrag(qs), qs[1], self.wsum(qs)),
-                                  frag=True, pool2=True)
+            z3, q = hip.mlp_chain(z2, [dspec.stage(hip.ACT_NONE)], fan=qs.fan(), frag=True, pool2=True)
         else:
             z3 = self.down(p + ".down_conv2", z2)
         tail = self.up_tail(p + ".concat_conv2", c2, p + ".up_conv2", z3.shape[-1]) if blocks else None
@@ -634,7 +635,7 @@ class Engine:
         C = h.shape[-1]
         for sfx in ("1", "2"):
             zr = self.merged(f"{p}|zr{sfx}", [(f"{p}.convz{sfx}", 0, 1.0, False), (f"{p}.convr{sfx}", 0, 1.0, False)], h.shape[-1] + x.shape[-1])
-            if getattr(zr, "korder", 0) == 2 and zr[4] == 2 * C and C % 128 == 0:
+            if zr.korder == 2 and zr.cout == 2 * C and C % 128 == 0:
                 both = self.cconv(zr, [h, x], act=hip.ACT_SIGMOID, epi=hip.EPI_MUL, aux0=h, epi_cout0=C)
                 z, rh = both[..., :C], both[..., C:]
             else:
@@ -738,15 +739,11 @@ class Engine:
         c = self.cconv(sc, [f2x], shuffle2=cc)
         s0, s2 = self.std(p + ".conv_concat.0"), self.std(p + ".conv_concat.2", transposed=True)
         cin = ab.shape[-1] + c.shape[-1]
-        if (self.use_k12_head and cin == 48 and s0[2] == 3 and s0[3] == 3 and not getattr(s0, "korder", 0) and s2[2] == 1 and s2[3] == 1
-                and tuple(s0[0].shape) == (s0[4], 9 * cin) and tuple(s2[0].shape) == (s2[4], s0[4]) and s2[4] <= 32
-                and self.narrow_ok(3, 3, 1, cin, s0[4])):
+        if (self.use_k12_head and cin == 48 and s0.kh == 3 and s0.kw == 3 and not s0.korder and tuple(s0.weight.shape) == (s0.cout, 9 * cin)
+                and s2.plain_1x1(s0.cout, s2.cout) and s2.cout <= 32 and self.narrow_ok(3, 3, 1, cin, s0.cout)):
             # conv_concat.0 -> ReLU -> conv_concat.2 (1x1) as ONE K12 launch: the head's MFMAs read the 3x3 layer's accumulators as they are
             # (pack.head_frag); the 48-channel full-resolution tensor is never written
-            hf = self._wfrag.get(("head", s2[0].data_ptr()))
-            if hf is None:
-                hf = self._wfrag[("head", s2[0].data_ptr())] = pack.head_frag(s2[0])
-            return hip.conv_narrow([ab, c], self.wnarrow(s0, 9), s0[1], 3, 3, s0[4], act=hip.ACT_RELU, head=(hf, s2[1], s2[4]))
+            return hip.conv_narrow([ab, c], s0.narrow_frag, s0.bias, 3, 3, s0.cout, act=hip.ACT_RELU, head=(s2.head_frag, s2.bias, s2.cout))
         y = self.cconv(s0, [ab, c], act=hip.ACT_RELU)
         return self.cconv(s2, [y])
 
@@ -755,11 +752,10 @@ class Engine:
         """CNNEncoder (submodules.py:63-93) on the (2B,H,W,8) normalised image tensor -> (1/4 features f4, 1/2 features f2)."""
         p = "cnn_backbone"
         c0, c2 = self._conv0(), self.std(p + ".conv0.2")
-        if tuple(c0[0].shape) == (16, 8) and tuple(c2[0].shape) == (16, 16) and c0[2] == 1 and c2[2] == 1:
-            st = self._packed.get("stem|fp32")                                  # conv0 = 1x1 - GELU - 1x1 per pixel on the VALU (K8)
-            if st is None:
-                st = self._packed["stem|fp32"] = (c0[0].float().contiguous(), c0[1], c2[0].float().contiguous(), c2[1])
-            t = hip.stem_mlp(x8, *st)
+        if c0.plain_1x1(8, 16) and c2.plain_1x1(16, 16):
+            # conv0 = 1x1 - GELU - 1x1 per pixel on the VALU (K8), from fp32 copies of the two weights
+            t = hip.stem_mlp(x8, *self.composite("stem|fp32", lambda: (c0.weight.float().contiguous(), c0.bias,
+                                                                       c2.weight.float().contiguous(), c2.bias)))
         else:
             t = self.cconv(c0, [x8], act=hip.ACT_GELU)
             t = self.cconv(c2, [t])
@@ -819,10 +815,9 @@ class Engine:
         fus = self.fusion("feat_fusion_layer", tr0, py0)
         c0, c2 = self.std("ctx_feat.0"), self.std("ctx_feat.2")
         cc = fus.shape[-1]
-        if (c0[2] == 1 and c2[2] == 1 and tuple(c0[0].shape) == (cc, cc) and tuple(c2[0].shape) == (cc, cc) and not getattr(c0, "korder", 0)
-                and self.chain_frag_ok(cc)):
+        if c0.plain_1x1(cc, cc) and c2.plain_1x1(cc, cc) and self.chain_frag_ok(cc):
             # ctx_feat = 1x1 - GELU - 1x1 (s2m2.py:59,165): ONE two-stage K9 launch (the intermediate never leaves the CU) instead of two
-            ctx = hip.mlp_chain(fus, [(self.wfrag(c0), c0[1], hip.ACT_GELU, None), (self.wfrag(c2), c2[1], hip.ACT_NONE, None)], frag=True)
+            ctx = hip.mlp_chain(fus, [c0.stage(hip.ACT_GELU), c2.stage(hip.ACT_NONE)], frag=True)
         else:
             ctx = self.cconv(c2, [self.cconv(c0, [fus], act=hip.ACT_GELU)])
         return ctx, hip.tanh(ctx)
@@ -874,7 +869,7 @@ class Engine:
                 cap[f"disp_it{it}"], cap[f"conf_it{it}"], cap[f"occ_it{it}"] = disp, conf, occ
         m4 = self.mask4x("upsample_mask_4x_refine", hidden, f2_left)
         d_up, o_up, c_up = self.upsample4x(disp, occ, conf, m4, x8)
-        m1 =self.mask1x("upsample_mask_1x", x8, f2_left)
+        m1 = self.mask1x("upsample_mask_1x", x8, f2_left)
         if cap is not None:
             cap.update(hidden=hidden.permute(0, 3, 1, 2), mask4x=m4[..., :9].permute(0, 3, 1, 2), disp_up4=d_up,
                        mask1x=m1[..., :9].permute(0, 3, 1, 2))
@@ -897,16 +892,12 @@ class Engine:
         launch form: a one-stage K9 chain with an identity weight (x * 1 summed with zeros in fp32 is exact in both modes) whose
         LayerNorm output feeds hip.corr."""
         n, h, w, c = tr.shape
-        eye = self._packed.get("identity|k9")
-        if eye is None:
-            eye = self._packed["identity|k9"] = Spec((torch.eye(c, device=tr.device, dtype=tr.dtype).contiguous(), None, 1, 1, c))
-        grp = (h // 8) * w if h % 8 == 0 else 0
-        ln_out = (self.ln_w, self.ln_b, 1e-5)
-        if self.chain_frag_ok(c):
-            return hip.mlp_chain(tr, [(self.wfrag(eye), None, hip.ACT_NONE, None)], ln_out=ln_out, xcd_group_rows=grp, frag=True)[1]
-        return hip.mlp_chain(tr, [(eye[0], None, hip.ACT_NONE, None)], ln_out=ln_out, xcd_group_rows=grp)[1]
+        eye = self.composite("identity|k9", lambda: Layer(torch.eye(c, device=tr.device, dtype=tr.dtype).contiguous(), None, 1, 1, c))
+        frag = self.chain_frag_ok(c)
+        return hip.mlp_chain(tr, [eye.stage(hip.ACT_NONE, frag)], ln_out=(self.ln_w, self.ln_b, 1e-5),
+                             xcd_group_rows=(h // 8) * w if h % 8 == 0 else 0, **({"frag": True} if frag else {}))[1]
 
-    def _conv0(self) -> Spec:
+    def _conv0(self) -> Layer:
         """cnn_backbone.conv0.0 (1x1, 3 -> 16) reading the RGB planes from channels 1..3 of the 8-channel input tensor."""
         return self.merged("cnn_backbone.conv0.0|rgb@1", [("cnn_backbone.conv0.0", 1, 1.0, False)], 8)
 
@@ -940,10 +931,10 @@ class _PlanRecord:
 
 
 class GraphRunner:
-    """hipGraph replay of the forward for one (batch, height, width): the ~350 kernel launches of a forward cost more host time
-    than GPU time once the kernels are fast, so they are captured once (``torch.cuda.graph`` = hipStreamBeginCapture on the stream
-    every C-ABI call enqueues on) and replayed.  With ``split_k1`` the graph is cut around K1 so that bench.py can bracket that one
-    kernel with HIP events inside the timed region: features graph -> K1 (eager) -> finish graph."""
+    """hipGraph replay of the forward for one (batch, height, width): the 236 kernel launches of a forward (headline configuration)
+    cost more host time than GPU time once the kernels are fast, so they are captured once (``torch.cuda.graph`` =
+    hipStreamBeginCapture on the stream every C-ABI call enqueues on) and replayed.  With ``split_k1`` the graph is cut around K1 so
+    that bench.py can bracket that one kernel with HIP events inside the timed region: features graph -> K1 (eager) -> finish graph."""
 
     def __init__(self, eng: Engine, B: int, H: int, W: int, split_k1: bool = False):
         self.eng = eng

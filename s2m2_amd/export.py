@@ -20,7 +20,7 @@ import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
 from . import hip
-from .engine import Engine, check_limits, max_batch
+from .engine import Engine, Layer, check_limits, max_batch
 
 _IMG_DT = {torch.float32: 0, torch.float16: 1, torch.uint8: 2}
 _IMG_FROM = {v: k for k, v in _IMG_DT.items()}
@@ -46,7 +46,8 @@ class _TorchKernels(TorchDispatchMode):
 
 
 def _storages(obj, out: Dict[int, int], seen: set) -> None:
-    """device storages (base pointer -> bytes) reachable from obj through dicts, lists and tuples"""
+    """device storages (base pointer -> bytes) reachable from obj through dicts, lists, tuples and the engine's packed layers (a Layer's
+    weight, bias and the derived packings it has built so far)"""
     if isinstance(obj, torch.Tensor):
         if obj.is_cuda:
             st = obj.untyped_storage()
@@ -62,6 +63,8 @@ def _storages(obj, out: Dict[int, int], seen: set) -> None:
     elif isinstance(obj, (list, tuple)):
         for v in obj:
             _storages(v, out, seen)
+    elif isinstance(obj, Layer):
+        _storages(vars(obj), out, seen)
 
 
 def _engine_storages(eng: Engine) -> Dict[int, int]:
