@@ -6,6 +6,7 @@ library is missing or a call fails, a RuntimeError is raised.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional, Tuple
@@ -238,23 +239,122 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _dev(*ts: torch.Tensor) -> None:
+# ---- operand validation.  The C ABI sees raw pointers and integers, so this is the only place that can check what a pointer stands for.
+# A wrapper reads as: residency of all its operands (_resident, once), geometry of each operand (one helper call each: pure functions of
+# shape, stride and dtype, so they run on CPU tensors too), descriptor, launch.
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _ptrs(ts):
+    """ctypes array of the base pointers of ``ts`` (None -> NULL; never empty, so that it always has an address)"""
+    return (_vp * max(len(ts), 1))(*[_ptr(t) for t in ts])
+
+
+def _resident(what: str, *ts: Optional[torch.Tensor]) -> None:
+    """every tensor a kernel will dereference lives on the GPU, all on the same one (None: an absent optional operand)"""
+    dev = None
     for t in ts:
-        if t is not None and (not t.is_cuda or not t.is_contiguous()):
-            raise ValueError("s2m2_amd.hip: tensors must be contiguous device tensors")
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError(f"{what}: operands must be device tensors, got one on {t.device}")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{what}: operands must be device tensors on one device, got {dev} and {t.device}")
+        dev = t.device
+
+
+def _contig(what: str, *ts: Optional[torch.Tensor]) -> None:
+    """operands the kernel indexes as one dense block"""
+    for t in ts:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{what}: tensors must be contiguous, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
+def _rows(x: torch.Tensor, what: str):
+    """(rows, row stride) of a (..., C) tensor with contiguous channels and a uniform row stride (a channel slice of a wider tensor is fine)"""
+    C = x.shape[-1]
+    if x.stride(-1) != 1:
+        raise ValueError(f"{what}: channels must be contiguous")
+    xs = x.stride(-2) if x.dim() > 1 else C
+    for d in range(x.dim() - 2):
+        if x.shape[d] > 1 and x.stride(d) != x.stride(d + 1) * x.shape[d + 1]:
+            raise ValueError(f"{what}: rows must have a uniform stride")
+    return x.numel() // C, xs
+
+
+def _pixels(t: torch.Tensor, what: str) -> int:
+    """pixel stride of an (N,H,W,C) view, channels contiguous, pixels dense with a common pixel stride (a channel slice of a wider tensor is fine)"""
+    if t.dim() != 4 or t.stride(3) != 1:
+        raise ValueError(f"{what}: expected an (N,H,W,C) tensor with contiguous channels, got {tuple(t.shape)} {t.stride()}")
+    n, h, w, c = t.shape
+    ps = t.stride(2)
+    if (h > 1 and t.stride(1) != w * ps) or (n > 1 and t.stride(0) != h * w * ps):
+        raise ValueError(f"{what}: pixels are not dense: shape {tuple(t.shape)} strides {t.stride()}")
+    return ps
+
+
+def _cv_pitch(cv: torch.Tensor, what: str) -> int:
+    """(B,h,w,w) cost volume, columns contiguous, volume rows ``pitch`` elements apart (a padded allocation viewed ``[..., :w]``, or
+    plain contiguous: pitch = w), image rows and batch entries dense behind that."""
+    if cv.dim() != 4 or cv.shape[2] != cv.shape[3]:
+        raise ValueError(f"{what}: cv must be a (B,h,w,w) tensor, got {tuple(cv.shape)}")
+    B, h, w, _ = cv.shape
+    pitch = cv.stride(2)
+    if cv.stride(3) != 1 or pitch < w or pitch % 8 or (h > 1 and cv.stride(1) != w * pitch) or (B > 1 and cv.stride(0) != h * w * pitch):
+        raise ValueError(f"{what}: cv strides {cv.stride()} are not a row-padded (B,h,w,w) volume")
+    return pitch
+
+
+def _vec(t: Optional[torch.Tensor], n: int, what: str, *, at_least: bool = False, dtype: torch.dtype = torch.float32,
+         optional: bool = False) -> None:
+    """a contiguous block of exactly ``n`` elements of ``dtype`` (at_least: ``n`` or more, the padded biases of K11 / K12); optional: None passes"""
+    if t is None:
+        if optional:
+            return
+        raise ValueError(f"{what} is missing")
+    if t.dtype != dtype or not t.is_contiguous() or (t.numel() < n if at_least else t.numel() != n):
+        raise ValueError(f"{what} must be a contiguous {dtype} vector of {'at least ' if at_least else ''}{n} elements, "
+                         f"got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+
+
+def _mat(t: torch.Tensor, shape, dtype: torch.dtype, what: str) -> None:
+    """a contiguous tensor of exactly this shape and dtype"""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {tuple(shape)} {dtype} tensor, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+
+
+def _frag(t: torch.Tensor, cout: int, k: int, dtype: torch.dtype, what: str) -> None:
+    """the MFMA-fragment stream of a (cout, k) matrix: 32-row x 16-column tiles of 64 lanes x 8 values (pack.pw_frag / pack.narrow_frag)"""
+    _mat(t, ((cout + 31) // 32, (k + 15) // 16, 64, 8), dtype, f"{what} of a ({cout}, {k}) matrix")
+
+
+@contextlib.contextmanager
+def _bracket(events: Optional[list], *fields):
+    """the optional event pair around one launch (ATTN_EVENTS / ROW_EVENTS): appends (start, stop, *fields) once the launch went through"""
+    if events is None:
+        yield
+        return
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    yield
+    ev[1].record()
+    events.append(ev + fields)
 
 
 def pack_frag(kind: int, w: torch.Tensor, w2: Optional[torch.Tensor] = None, ntap: int = 1, rows: Optional[int] = None) -> torch.Tensor:
     """s2m2_pack_frag: the plain packing ``w`` (rows, K) fp16 on the device -> flat fp16 tensor holding the fragment stream of the direct-form
     kernel named by ``kind`` (PACK_ROWS / PACK_NARROW / PACK_CONV_FRAG / PACK_FUSION / PACK_HEAD; include/s2m2_hip.h).  One-time set-up."""
-    if w.dtype != torch.float16 or not w.is_cuda or w.dim() != 2 or w.stride(1) != 1:
-        raise ValueError("pack_frag: w must be a 2-D fp16 device tensor with contiguous rows")
+    _resident("pack_frag", w, w2)
     d = PackDesc()
-    d.kind, d.w, d.rows, d.cols, d.ld, d.ntap = kind, w.data_ptr(), rows if rows is not None else w.shape[0], w.shape[1], w.stride(0), ntap
+    for name, t in (("w", w), ("w2", w2)):
+        if t is not None and (t.dtype != torch.float16 or t.dim() != 2):
+            raise ValueError(f"pack_frag: {name} must be a 2-D fp16 device tensor with contiguous rows")
+    d.w, d.ld = w.data_ptr(), _rows(w, "pack_frag: w")[1]
     if w2 is not None:
-        if w2.dtype != torch.float16 or not w2.is_cuda or w2.dim() != 2 or w2.stride(1) != 1:
-            raise ValueError("pack_frag: w2 must be a 2-D fp16 device tensor with contiguous rows")
-        d.w2, d.ld2 = w2.data_ptr(), w2.stride(0)
+        d.w2, d.ld2 = w2.data_ptr(), _rows(w2, "pack_frag: w2")[1]
+    d.kind, d.rows, d.cols, d.ntap = kind, rows if rows is not None else w.shape[0], w.shape[1], ntap
     lib = load()
     n = lib.s2m2_pack_frag_elems(ctypes.byref(d))
     if n < 0:
@@ -290,9 +390,8 @@ class Plan:
                 lib.s2m2_plan_abort(self.plan.h)
                 return False
             n = len(self.ext)
-            base = (_vp * max(n, 1))(*[(t.data_ptr() if t is not None else None) for t in self.ext])
             size = (ctypes.c_size_t * max(n, 1))(*[(t.numel() * t.element_size() if t is not None else 0) for t in self.ext])
-            _check(lib.s2m2_plan_end(self.plan.h, base, size, n), "s2m2_plan_end")
+            _check(lib.s2m2_plan_end(self.plan.h, _ptrs(self.ext), size, n), "s2m2_plan_end")
             self.plan.n, self.plan.sealed = n, True
             return False
 
@@ -307,14 +406,11 @@ class Plan:
         return load().s2m2_plan_patches(self.h, slot)
 
     def run(self, externals) -> None:
-        n = len(externals)
-        ptrs = (_vp * max(n, 1))(*[(t.data_ptr() if t is not None else None) for t in externals])
-        _check(load().s2m2_plan_run(self.h, ptrs, n, _stream()), "s2m2_plan_run")
+        _check(load().s2m2_plan_run(self.h, _ptrs(externals), len(externals), _stream()), "s2m2_plan_run")
 
     def refine_step(self, hidden, ctx, disp, conf, occ, cv, side) -> None:
         """s2m2_refine_step: this plan as one refinement iteration, externals in the ABI's fixed order"""
-        p = [t.data_ptr() if t is not None else None for t in (hidden, ctx, disp, conf, occ, cv, side)]
-        _check(load().s2m2_refine_step(self.h, *p, _stream()), "s2m2_refine_step")
+        _check(load().s2m2_refine_step(self.h, *_ptrs((hidden, ctx, disp, conf, occ, cv, side)), _stream()), "s2m2_refine_step")
 
     def __del__(self):
         try:
@@ -346,49 +442,42 @@ class KernelTimer:
             pass
 
 
-def _cost_volume(tokens: torch.Tensor, ln, cv: torch.Tensor, timer, band: int, what: str) -> None:
-    """one launch of K1 through its descriptor (s2m2_cost_volume); ln = (weight, bias) fp32 or None (tokens normalised already)"""
+def _cost_volume(tokens: torch.Tensor, ln, cv_dtype, out, timer, band: int, what: str) -> torch.Tensor:
+    """one launch of K1 through its descriptor (s2m2_cost_volume); ln = (weight, bias) or None (tokens normalised already).  Without ``out`` the
+    volume is allocated plain (ln: the form ln_corr always returned) or with row-padded lines (cv_alloc)."""
+    ln = ln or ()
+    _resident(what, tokens, *ln, out)
+    _contig(what, tokens, *ln)
     twoB, h, w, C = tokens.shape
+    B = twoB // 2
+    if out is not None:
+        cv = out
+    elif ln:
+        cv = torch.empty((B, h, w, w), device=tokens.device, dtype=cv_dtype or tokens.dtype)
+    else:
+        cv = cv_alloc(B, h, w, cv_dtype or tokens.dtype, tokens.device)
+    if tuple(cv.shape) != (B, h, w, w):
+        raise ValueError(f"{what}: out must be a (B,h,w,w) tensor")
     d = CorrDesc()
     d.tokens, d.cv = tokens.data_ptr(), cv.data_ptr()
-    keep = None
-    if ln is not None:
-        keep = (ln[0].float().contiguous(), ln[1].float().contiguous())
+    keep = [t.float().contiguous() for t in ln]
+    if keep:
         d.ln_weight, d.ln_bias = keep[0].data_ptr(), keep[1].data_ptr()
-    d.B, d.h, d.w, d.C = twoB // 2, h, w, C
+    d.B, d.h, d.w, d.C = B, h, w, C
     d.cv_pitch, d.band = _cv_pitch(cv, what), band if band >= 0 else -1
     d.token_dtype, d.cv_dtype = _DT[tokens.dtype], _DT[cv.dtype]
     if timer is not None:
         d.start_event, d.stop_event = timer.start, timer.stop
     _check(load().s2m2_cost_volume(ctypes.byref(d), _stream()), "s2m2_cost_volume")
-    _meter("ln_corr", 2.0 * (twoB // 2) * h * w * w * C)
+    _meter("ln_corr", 2.0 * B * h * w * w * C)
+    return cv
 
 
 def ln_corr(feat: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, cv_dtype: Optional[torch.dtype] = None,
             out: Optional[torch.Tensor] = None, timer: Optional[KernelTimer] = None, band: int = -1) -> torch.Tensor:
     """feat (2B,h,w,C) channels-last tokens (left = first B) -> cv (B,h,w,w), LayerNorm inside the kernel.  [A4]   timer: see KernelTimer.
     band >= 0: only columns j <= i + band are written, the rest of ``cv`` keeps whatever it held.  ``out`` may be a row-padded view (cv_alloc)."""
-    _dev(feat, ln_w, ln_b)
-    twoB, h, w, C = feat.shape
-    B = twoB // 2
-    cv_dtype = cv_dtype or feat.dtype
-    cv = out if out is not None else torch.empty((B, h, w, w), device=feat.device, dtype=cv_dtype)
-    if tuple(cv.shape) != (B, h, w, w):
-        raise ValueError("ln_corr: out must be a (B,h,w,w) tensor")
-    _cost_volume(feat, (ln_w, ln_b), cv, timer, band, "ln_corr")
-    return cv
-
-
-def _cv_pitch(cv: torch.Tensor, what: str) -> int:
-    """(B,h,w,w) cost volume, columns contiguous, volume rows ``pitch`` elements apart (a padded allocation viewed ``[..., :w]``, or
-    plain contiguous: pitch = w), image rows and batch entries dense behind that."""
-    if cv.dim() != 4 or not cv.is_cuda or cv.shape[2] != cv.shape[3]:
-        raise ValueError(f"{what}: cv must be a (B,h,w,w) device tensor, got {tuple(cv.shape)}")
-    B, h, w, _ = cv.shape
-    pitch = cv.stride(2)
-    if cv.stride(3) != 1 or pitch < w or pitch % 8 or (h > 1 and cv.stride(1) != w * pitch) or (B > 1 and cv.stride(0) != h * w * pitch):
-        raise ValueError(f"{what}: cv strides {cv.stride()} are not a row-padded (B,h,w,w) volume")
-    return pitch
+    return _cost_volume(feat, (ln_w, ln_b), cv_dtype, out, timer, band, "ln_corr")
 
 
 def cv_alloc(B: int, h: int, w: int, dtype: torch.dtype, device, aligned: bool = True) -> torch.Tensor:
@@ -403,32 +492,26 @@ def corr(tokens: torch.Tensor, cv_dtype: Optional[torch.dtype] = None, out: Opti
          timer: Optional[KernelTimer] = None, band: int = -1) -> torch.Tensor:
     """tokens (2B,h,w,C) ALREADY LayerNorm'ed (left = first B) -> cv (B,h,w,w), a row-padded view (cv_alloc) unless ``out`` is given.
     [A4 without the LayerNorm: s2m2_cost_volume with ln_weight = NULL]"""
-    _dev(tokens)
-    twoB, h, w, C = tokens.shape
-    B = twoB // 2
-    cv = out if out is not None else cv_alloc(B, h, w, cv_dtype or tokens.dtype, tokens.device)
-    if tuple(cv.shape) != (B, h, w, w):
-        raise ValueError("corr: out must be a (B,h,w,w) tensor")
-    _cost_volume(tokens, None, cv, timer, band, "corr")
-    return cv
+    return _cost_volume(tokens, None, cv_dtype, out, timer, band, "corr")
 
 
 def sinkhorn_regress(cv: torch.Tensor, use_positivity: bool, ot_iter: int = 3, want_argmax: bool = False):
     """cv (B,h,w,w) (row-padded views accepted) -> disp, conf, occ (B,1,h,w) fp32 [, argmax (B,h,w) int32].  [A5+A6]"""
+    _resident("sinkhorn_regress", cv)
     pitch = _cv_pitch(cv, "sinkhorn_regress")
     B, h, w, _ = cv.shape
     out = torch.empty((3, B, 1, h, w), device=cv.device, dtype=torch.float32)
     am = torch.empty((B, h, w), device=cv.device, dtype=torch.int32) if want_argmax else None
-    _check(load().s2m2_sinkhorn_regress(cv.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                        am.data_ptr() if am is not None else None, B, h, w, ot_iter, int(use_positivity),
-                                        _DT[cv.dtype], pitch, None, _stream()), "s2m2_sinkhorn_regress")
+    _check(load().s2m2_sinkhorn_regress(cv.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _ptr(am), B, h, w, ot_iter,
+                                        int(use_positivity), _DT[cv.dtype], pitch, None, _stream()), "s2m2_sinkhorn_regress")
     return (out[0], out[1], out[2], am) if want_argmax else (out[0], out[1], out[2])
 
 
 def cv_lookup(cv: torch.Tensor, disp: torch.Tensor, radius: int = 4, channels_last: bool = False,
               out_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
     """cv (B,h,w,w), disp (B,1,h,w) fp32 -> corr1, corr2: (B,2r+1,h,w) planar or (B,h,w,2r+1) channels-last.  [A9+A10]"""
-    _dev(disp)
+    _resident("cv_lookup", cv, disp)
+    _contig("cv_lookup", disp)
     pitch = _cv_pitch(cv, "cv_lookup")
     B, h, w, _ = cv.shape
     T = 2 * radius + 1
@@ -445,17 +528,6 @@ def cv_lookup(cv: torch.Tensor, disp: torch.Tensor, radius: int = 4, channels_la
     return c1, c2
 
 
-def _nhwc(t: torch.Tensor):
-    """(N,H,W,C) view, channels contiguous, pixels dense with a common pixel stride (a channel slice of a wider tensor is fine)."""
-    if t.dim() != 4 or not t.is_cuda or t.stride(3) != 1:
-        raise ValueError(f"s2m2_amd.hip: expected an (N,H,W,C) device tensor with contiguous channels, got {tuple(t.shape)} {t.stride()}")
-    n, h, w, c = t.shape
-    ps = t.stride(2)
-    if (h > 1 and t.stride(1) != w * ps) or (n > 1 and t.stride(0) != h * w * ps):
-        raise ValueError(f"s2m2_amd.hip: pixels are not dense: shape {tuple(t.shape)} strides {t.stride()}")
-    return ps
-
-
 def conv2d(srcs, weight: torch.Tensor, bias: Optional[torch.Tensor], KH: int, KW: int, Cout: int, act: int = ACT_NONE,
            epi: int = EPI_NONE, aux0: Optional[torch.Tensor] = None, aux1: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, out_scale: float = 1.0, shuffle2: int = 0, tile: int = 0,
@@ -469,6 +541,9 @@ def conv2d(srcs, weight: torch.Tensor, bias: Optional[torch.Tensor], KH: int, KW
     >= epi_cout0 only and aux0 has Cout - epi_cout0 channels (two stacked layers, one launch: s2m2_conv_desc.epi_cout0)."""
     if isinstance(srcs, torch.Tensor):
         srcs = [srcs]
+    if pool2 and (KH, KW, stride) != (1, 1, 1):      # the output grid below is only that of AvgPool2d(2) + 1x1; refused like the library refuses it
+        raise RuntimeError("conv2d: pool2 needs a plain 1x1 stride-1 layer")
+    _resident("conv2d", *srcs, weight, bias, aux0, aux1, out, ln_wsum, bias2)
     d = ConvDesc()
     x0 = srcs[0]
     n, h, w, _ = x0.shape
@@ -477,16 +552,12 @@ def conv2d(srcs, weight: torch.Tensor, bias: Optional[torch.Tensor], KH: int, KW
     for i, t in enumerate(srcs):
         if t.dtype != dt or tuple(t.shape[:3]) != (n, h, w):
             raise ValueError("conv2d: sources must share dtype and (N,H,W)")
-        d.src[i] = t.data_ptr()
-        d.src_c[i] = t.shape[3]
-        d.src_stride[i] = _nhwc(t)
+        d.src[i], d.src_c[i], d.src_stride[i] = t.data_ptr(), t.shape[3], _pixels(t, "conv2d: source")
         cin += t.shape[3]
     ck = 192 if (Cout % 128 != 0 and Cout % 192 == 0 and cin % 192 == 0) else 128        # s2m2_conv_frag_chunk
     kcols = KH * KW * (-(-cin // ck) * ck) if korder == 2 else KH * KW * cin           # K order 2: K padded to whole chunks
-    if weight.dtype != dt or not weight.is_contiguous() or tuple(weight.shape) != (Cout, kcols):
-        raise ValueError(f"conv2d: packed weight must be {(Cout, kcols)} {dt}, got {tuple(weight.shape)} {weight.dtype}")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != Cout or not bias.is_contiguous()):
-        raise ValueError("conv2d: bias must be fp32 (Cout)")
+    _mat(weight, (Cout, kcols), dt, "conv2d: packed weight")
+    _vec(bias, Cout, "conv2d: bias", optional=True)
     ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
     if pool2:
         ho, wo = h // 2, w // 2
@@ -496,52 +567,28 @@ def conv2d(srcs, weight: torch.Tensor, bias: Optional[torch.Tensor], KH: int, KW
     if tuple(out.shape) != exp_shape or out.dtype != dt:
         raise ValueError(f"conv2d: out must be {exp_shape} {dt}, got {tuple(out.shape)} {out.dtype}")
     d.nsrc = len(srcs)
-    d.weight = weight.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.out = out.data_ptr()
-    d.out_stride = _nhwc(out)
+    d.weight, d.bias, d.out, d.out_stride = weight.data_ptr(), _ptr(bias), out.data_ptr(), _pixels(out, "conv2d: out")
     d.N, d.H, d.W, d.KH, d.KW, d.Cout = n, h, w, KH, KW, Cout
     d.act, d.epi = act, epi
-    for name, a in (("aux0", aux0), ("aux1", aux1)):
-        if a is not None:
-            ac = Cout - epi_cout0 if name == "aux0" else Cout
-            if a.dtype != dt or tuple(a.shape) != (n, ho, wo, ac):
-                raise ValueError(f"conv2d: {name} must be {(n, ho, wo, ac)} {dt}, got {tuple(a.shape)} {a.dtype}")
-            setattr(d, name, a.data_ptr())                       # (aux0 of an epi_cout0 launch: its own base; the library applies the cout offset)
-            setattr(d, name + "_stride", _nhwc(a))
-    d.epi_cout0 = epi_cout0
-    d.out_scale = out_scale
-    d.shuffle2 = shuffle2
-    d.tile = tile
-    d.stride = stride
-    d.korder = korder
-    d.pool2 = int(pool2)
+    for name, a, ac in (("aux0", aux0, Cout - epi_cout0), ("aux1", aux1, Cout)):
+        if a is not None and (a.dtype != dt or tuple(a.shape) != (n, ho, wo, ac)):
+            raise ValueError(f"conv2d: {name} must be {(n, ho, wo, ac)} {dt}, got {tuple(a.shape)} {a.dtype}")
+    if aux0 is not None:                   # (aux0 of an epi_cout0 launch: its own base; the library applies the cout offset)
+        d.aux0, d.aux0_stride = aux0.data_ptr(), _pixels(aux0, "conv2d: aux0")
+    if aux1 is not None:
+        d.aux1, d.aux1_stride = aux1.data_ptr(), _pixels(aux1, "conv2d: aux1")
+    d.epi_cout0, d.out_scale, d.shuffle2 = epi_cout0, out_scale, shuffle2
+    d.tile, d.stride, d.korder, d.pool2 = tile, stride, korder, int(pool2)
     if ln_wsum is not None:
-        if ln_wsum.dtype != torch.float32 or ln_wsum.numel() != Cout or not ln_wsum.is_contiguous():
-            raise ValueError("conv2d: ln_wsum must be fp32 (Cout)")
-        d.ln_wsum = ln_wsum.data_ptr()
-        d.ln_eps = ln_eps
+        _vec(ln_wsum, Cout, "conv2d: ln_wsum")
+        d.ln_wsum, d.ln_eps = ln_wsum.data_ptr(), ln_eps
     if epi == EPI_DUALMIX:
-        if bias2 is not None and (bias2.dtype != torch.float32 or bias2.numel() != Cout or not bias2.is_contiguous()):
-            raise ValueError("conv2d: bias2 must be fp32 (Cout)")
-        d.ksplit = ksplit
-        d.bias2 = bias2.data_ptr() if bias2 is not None else None
+        _vec(bias2, Cout, "conv2d: bias2", optional=True)
+        d.ksplit, d.bias2 = ksplit, _ptr(bias2)
     d.dtype = _DT[dt]
     _check(load().s2m2_conv2d(ctypes.byref(d), _stream()), "s2m2_conv2d")
     _meter("conv2d", 2.0 * n * ho * wo * Cout * KH * KW * cin)
     return out
-
-
-def _token_rows(x: torch.Tensor, what: str):
-    """(rows, row stride) of a (..., C) tensor with contiguous channels and a uniform row stride"""
-    C = x.shape[-1]
-    if x.stride(-1) != 1:
-        raise ValueError(f"{what}: channels must be contiguous")
-    xs = x.stride(-2) if x.dim() > 1 else C
-    for d in range(x.dim() - 2):
-        if x.shape[d] > 1 and x.stride(d) != x.stride(d + 1) * x.shape[d + 1]:
-            raise ValueError(f"{what}: rows must have a uniform stride")
-    return x.numel() // C, xs
 
 
 def mlp_chain_supported(C: int, dtype: torch.dtype) -> bool:
@@ -552,6 +599,31 @@ def mlp_fan_supported(C: int, nfan: int, dtype: torch.dtype) -> bool:
     return bool(load().s2m2_mlp_fan_supported(C, nfan, _DT[dtype]))
 
 
+def _chain_input(d: ChainDesc, x: torch.Tensor, pool2: bool, what: str):
+    """the x / rows / pool fields of a chain descriptor -> (rows, leading shape of the outputs); pool2: x (N,H,W,C) is read through AvgPool2d(2)"""
+    rows, xs = _rows(x, what)
+    oshape = tuple(x.shape[:-1])
+    if pool2:
+        oshape = (x.shape[0], x.shape[1] // 2, x.shape[2] // 2)
+        rows = oshape[0] * oshape[1] * oshape[2]
+        d.pool_h, d.pool_w = x.shape[1], x.shape[2]
+    d.x, d.x_stride, d.rows, d.C, d.dtype = x.data_ptr(), xs, rows, x.shape[-1], _DT[x.dtype]
+    return rows, oshape
+
+
+def _chain_fan(d: ChainDesc, x: torch.Tensor, oshape, weight: torch.Tensor, bias, ln_wsum, what: str):
+    """the fan block of a chain descriptor: n stacked C -> C layers, packed (n*C, C), on the rows the launch produces -> (fan_out (..., n*C), n)"""
+    C = x.shape[-1]
+    n = weight.shape[0] // C
+    _mat(weight, (n * C, C), x.dtype, f"{what}: fan weight, packed (n*{C}, {C}),")
+    _vec(bias, n * C, f"{what}: fan bias", optional=True)
+    _vec(ln_wsum, n * C, f"{what}: fan ln_wsum", optional=True)
+    out = torch.empty(oshape + (n * C,), device=x.device, dtype=x.dtype)
+    d.fan_weight, d.fan_out, d.fan_out_stride, d.nfan = weight.data_ptr(), out.data_ptr(), n * C, n
+    d.fan_bias, d.fan_ln_wsum = _ptr(bias), _ptr(ln_wsum)
+    return out, n
+
+
 def mlp_fan(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], ln_wsum: Optional[torch.Tensor], ln_eps: float = 1e-5,
             frag: bool = True, pool2: bool = False) -> torch.Tensor:
     """n stacked C -> C layers on the rows of x (..., C) -> (..., n*C) in one pass over the rows (s2m2_mlp_chain with nstage = 0: the
@@ -560,30 +632,14 @@ def mlp_fan(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
     the layers, folded into the tile load -> (N, H//2, W//2, n*C)."""
     if not frag:
         raise ValueError("mlp_fan: the fan-out-only launch exists in the direct form only (weight in fragment order, frag=True)")
+    _resident("mlp_fan", x, weight, bias, ln_wsum)
+    if pool2 and (x.dim() != 4 or x.shape[1] < 2 or x.shape[2] < 2):
+        raise ValueError("mlp_fan: pool2 needs frag and an (N,H,W,C) tensor of at least 2x2 pixels")
     C = x.shape[-1]
-    rows, xs = _token_rows(x, "mlp_fan")
-    n = weight.shape[0] // C
-    oshape = tuple(x.shape[:-1])
-    if pool2:
-        if not frag or x.dim() != 4 or x.shape[1] < 2 or x.shape[2] < 2:
-            raise ValueError("mlp_fan: pool2 needs frag and an (N,H,W,C) tensor of at least 2x2 pixels")
-        oshape = (x.shape[0], x.shape[1] // 2, x.shape[2] // 2)
-        rows = oshape[0] * oshape[1] * oshape[2]
-    if weight.dtype != x.dtype or tuple(weight.shape) != (n * C, C) or not weight.is_contiguous() or not weight.is_cuda or not x.is_cuda:
-        raise ValueError(f"mlp_fan: weight must be a packed (n*{C}, {C}) {x.dtype} device matrix")
-    for name, t in (("bias", bias), ("ln_wsum", ln_wsum)):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != n * C or not t.is_contiguous() or not t.is_cuda):
-            raise ValueError(f"mlp_fan: {name} must be fp32 ({n * C}) on the device")
-    out = torch.empty(oshape + (n * C,), device=x.device, dtype=x.dtype)
     d = ChainDesc()
-    d.x, d.x_stride, d.rows, d.C, d.nstage, d.dtype, d.ln_eps = x.data_ptr(), xs, rows, C, 0, _DT[x.dtype], ln_eps
-    d.res_stage = -1
-    d.weight_frag = int(bool(frag))
-    if pool2:
-        d.pool_h, d.pool_w = x.shape[1], x.shape[2]
-    d.fan_weight, d.fan_out, d.fan_out_stride, d.nfan = weight.data_ptr(), out.data_ptr(), n * C, n
-    d.fan_bias = bias.data_ptr() if bias is not None else None
-    d.fan_ln_wsum = ln_wsum.data_ptr() if ln_wsum is not None else None
+    rows, oshape = _chain_input(d, x, pool2, "mlp_fan")
+    d.nstage, d.ln_eps, d.res_stage, d.weight_frag = 0, ln_eps, -1, 1
+    out, n = _chain_fan(d, x, oshape, weight, bias, ln_wsum, "mlp_fan")
     _check(load().s2m2_mlp_chain(ctypes.byref(d), _stream()), "s2m2_mlp_chain")
     _meter("mlp_chain", 2.0 * rows * C * C * n)
     return out
@@ -614,64 +670,38 @@ def mlp_chain(x: torch.Tensor, stages, res: Optional[torch.Tensor] = None, res_s
     counts (mlp_chain_frag_supported).  pool2 (frag, x (N,H,W,C), no res / carry / ln_out): nn.AvgPool2d(2) in front of the first stage,
     folded into the tile load -> outputs on the (N, H//2, W//2) grid.
     Return value: out, or a tuple (out[, normalised][, fan_out]) in that order."""
-    C = x.shape[-1]
-    rows, xs = _token_rows(x, "mlp_chain")
-    oshape = tuple(x.shape[:-1])
-    d = ChainDesc()
-    if pool2:
-        if not frag or x.dim() != 4 or x.shape[1] < 2 or x.shape[2] < 2 or res_stage >= 0 or carry or ln_out is not None:
-            raise ValueError("mlp_chain: pool2 needs frag, an (N,H,W,C) tensor of at least 2x2 pixels and no res / carry / ln_out")
-        oshape = (x.shape[0], x.shape[1] // 2, x.shape[2] // 2)
-        rows = oshape[0] * oshape[1] * oshape[2]
-        d.pool_h, d.pool_w = x.shape[1], x.shape[2]
-    d.x, d.x_stride, d.rows, d.C, d.nstage, d.dtype = x.data_ptr(), xs, rows, C, len(stages), _DT[x.dtype]
+    _resident("mlp_chain", x, res, *[t for w, b, _, wsum in stages for t in (w, b, wsum)], *(ln_out[:2] if ln_out is not None else ()),
+              *(fan or ()))
+    if pool2 and (not frag or x.dim() != 4 or x.shape[1] < 2 or x.shape[2] < 2 or res_stage >= 0 or carry or ln_out is not None):
+        raise ValueError("mlp_chain: pool2 needs frag, an (N,H,W,C) tensor of at least 2x2 pixels and no res / carry / ln_out")
     if not 1 <= len(stages) <= 3:
         raise ValueError("mlp_chain: 1..3 stages")
-    keep = [x]
+    C = x.shape[-1]
+    d = ChainDesc()
+    rows, oshape = _chain_input(d, x, pool2, "mlp_chain")
+    d.nstage = len(stages)
     for i, (w, b, act, wsum) in enumerate(stages):
-        if w.dtype != x.dtype or tuple(w.shape) != (C, C) or not w.is_contiguous():
-            raise ValueError(f"mlp_chain: weight[{i}] must be a packed ({C}, {C}) {x.dtype} matrix, got {tuple(w.shape)} {w.dtype}")
-        for name, t in (("bias", b), ("ln_wsum", wsum)):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous()):
-                raise ValueError(f"mlp_chain: {name}[{i}] must be fp32 ({C})")
-        d.weight[i], d.act[i] = w.data_ptr(), act
-        d.bias[i] = b.data_ptr() if b is not None else None
-        d.ln_wsum[i] = wsum.data_ptr() if wsum is not None else None
-        keep += [w, b, wsum]
-    if not all(t.is_cuda for t in keep if t is not None):
-        raise ValueError("mlp_chain: tensors must live on the GPU")
+        _mat(w, (C, C), x.dtype, f"mlp_chain: packed weight[{i}]")
+        _vec(b, C, f"mlp_chain: bias[{i}]", optional=True)
+        _vec(wsum, C, f"mlp_chain: ln_wsum[{i}]", optional=True)
+        d.weight[i], d.act[i], d.bias[i], d.ln_wsum[i] = w.data_ptr(), act, _ptr(b), _ptr(wsum)
     d.res_stage, d.carry, d.ln_eps = res_stage, int(carry), ln_eps
     d.xcd_group_rows = int(xcd_group_rows)
     d.weight_frag = int(bool(frag))
     if res_stage >= 0:
         if res is None or res.dtype != x.dtype or tuple(res.shape) != tuple(x.shape):
             raise ValueError("mlp_chain: res must match x")
-        d.res, d.res_stride = res.data_ptr(), _token_rows(res, "mlp_chain")[1]
+        d.res, d.res_stride = res.data_ptr(), _rows(res, "mlp_chain: res")[1]
     out = torch.empty(oshape + (C,), device=x.device, dtype=x.dtype)
     d.out, d.out_stride = out.data_ptr(), C
     normed = None
     if ln_out is not None:
         gam, bet, eps = ln_out
-        _dev(gam, bet)
-        if gam.dtype != torch.float32 or bet.dtype != torch.float32 or gam.numel() != C or bet.numel() != C:
-            raise ValueError(f"mlp_chain: ln_out gamma / beta must be fp32 ({C})")
+        _vec(gam, C, "mlp_chain: ln_out gamma")
+        _vec(bet, C, "mlp_chain: ln_out beta")
         normed = torch.empty(x.shape, device=x.device, dtype=x.dtype)
-        ln_ptr = normed.data_ptr()
-        d.ln_out, d.ln_out_stride, d.ln_gamma, d.ln_beta, d.ln_out_eps = ln_ptr, C, gam.data_ptr(), bet.data_ptr(), float(eps)
-    fan_out = None
-    nfan = 0
-    if fan is not None:
-        fw, fb, fws = fan
-        nfan = fw.shape[0] // C
-        if fw.dtype != x.dtype or fw.dim() != 2 or fw.shape[1] != C or fw.shape[0] != nfan * C or not fw.is_contiguous() or not fw.is_cuda:
-            raise ValueError(f"mlp_chain: fan weight must be a packed (n*{C}, {C}) {x.dtype} device matrix")
-        for name, t in (("fan bias", fb), ("fan ln_wsum", fws)):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != nfan * C or not t.is_contiguous() or not t.is_cuda):
-                raise ValueError(f"mlp_chain: {name} must be fp32 ({nfan * C}) on the device")
-        fan_out = torch.empty(oshape + (nfan * C,), device=x.device, dtype=x.dtype)
-        d.fan_weight, d.fan_out, d.fan_out_stride, d.nfan = fw.data_ptr(), fan_out.data_ptr(), nfan * C, nfan
-        d.fan_bias = fb.data_ptr() if fb is not None else None
-        d.fan_ln_wsum = fws.data_ptr() if fws is not None else None
+        d.ln_out, d.ln_out_stride, d.ln_gamma, d.ln_beta, d.ln_out_eps = normed.data_ptr(), C, gam.data_ptr(), bet.data_ptr(), float(eps)
+    fan_out, nfan = _chain_fan(d, x, oshape, *fan, "mlp_chain") if fan is not None else (None, 0)
     _check(load().s2m2_mlp_chain(ctypes.byref(d), _stream()), "s2m2_mlp_chain")
     _meter("mlp_chain", 2.0 * rows * C * C * (len(stages) + nfan))
     res_t = (out,) + ((normed,) if normed is not None else ()) + ((fan_out,) if fan_out is not None else ())
@@ -688,23 +718,20 @@ def conv_block(x: torch.Tensor, w_conv0: torch.Tensor, b_conv0, w_conv2: torch.T
     """K14: ConvBlock2D (attentions.py:255-281) on x (N,H,W,C) in one launch: convs.2(GELU(convs.0(x))) + convs_1x.2(ReLU(convs_1x.0(x))).
     w_conv0 / w_conv2: the 3x3 layers as K5 v5 fragment streams (pack.pack_conv_frag), w_1x0 / w_1x2: the 1x1 layers in K9's fragment order
     (pack.chain_frag); biases fp32 (C) or None."""
-    if x.dim() != 4 or x.dtype != torch.float16 or not x.is_cuda or x.stride(3) != 1:
-        raise ValueError("conv_block: x must be an (N,H,W,C) fp16 device tensor with contiguous channels")
+    _resident("conv_block", x, w_conv0, b_conv0, w_conv2, b_conv2, w_1x0, b_1x0, w_1x2, b_1x2)
+    if x.dtype != torch.float16:
+        raise ValueError("conv_block: x must be an (N,H,W,C) fp16 tensor")
+    xs = _pixels(x, "conv_block: x")
     N, H, W, C = x.shape
-    xs = x.stride(2)
-    if x.stride(1) != W * xs or (N > 1 and x.stride(0) != H * W * xs):
-        raise ValueError("conv_block: the pixels of x must be evenly strided")
     d = ConvBlockDesc()
     out = torch.empty((N, H, W, C), device=x.device, dtype=x.dtype)
     d.x, d.x_stride, d.out, d.out_stride, d.N, d.H, d.W, d.C = x.data_ptr(), xs, out.data_ptr(), C, N, H, W, C
     for name, w, n in (("w_conv0", w_conv0, 9 * C * C), ("w_conv2", w_conv2, 9 * C * C), ("w_1x0", w_1x0, C * C), ("w_1x2", w_1x2, C * C)):
-        if w.dtype != x.dtype or w.numel() != n or not w.is_contiguous() or not w.is_cuda:
-            raise ValueError(f"conv_block: {name} must be a contiguous fp16 device tensor of {n} elements")
+        _vec(w, n, f"conv_block: {name}", dtype=x.dtype)
         setattr(d, name, w.data_ptr())
     for name, b in (("b_conv0", b_conv0), ("b_conv2", b_conv2), ("b_1x0", b_1x0), ("b_1x2", b_1x2)):
-        if b is not None and (b.dtype != torch.float32 or b.numel() != C or not b.is_contiguous() or not b.is_cuda):
-            raise ValueError(f"conv_block: {name} must be fp32 ({C}) on the device or None")
-        setattr(d, name, b.data_ptr() if b is not None else None)
+        _vec(b, C, f"conv_block: {name}", optional=True)
+        setattr(d, name, _ptr(b))
     d.patch_rows, d.dtype = patch_rows, _DT[x.dtype]
     _check(load().s2m2_conv_block(ctypes.byref(d), _stream()), "s2m2_conv_block")
     _meter("conv_block", 2.0 * N * H * W * C * C * 20)
@@ -723,16 +750,13 @@ def row_attn(x: torch.Tensor, heads: int, cross: bool, weights: torch.Tensor, ve
     weights: (6 * 128, 128) fp16 -- q, k, v, proj, ffn.0, ffn.2 in the row_attn packing (pack.rowattn_pack); vectors: (12, 128) fp32 --
     bias q, row sums q, bias k, row sums k, bias v, row sums v, bias proj, bias ffn.0, row sums ffn.0, bias ffn.2, ln_out gamma, ln_out beta
     (pack.rowattn_vectors).  ln_out_eps: also return LayerNorm(out) * gamma + beta with that eps -> (out, normalised)."""
-    if x.dim() != 4 or x.dtype != torch.float16 or not x.is_cuda or x.stride(3) != 1:
-        raise ValueError("row_attn: x must be an (nimg, h, w, C) fp16 device tensor with contiguous channels")
+    _resident("row_attn", x, weights, vectors)
+    if x.dtype != torch.float16:
+        raise ValueError("row_attn: x must be an (nimg, h, w, C) fp16 tensor")
+    xs = _pixels(x, "row_attn: x")
     nimg, h, w, C = x.shape
-    xs = x.stride(2)
-    if x.stride(1) != w * xs or (nimg > 1 and x.stride(0) != h * w * xs):
-        raise ValueError("row_attn: the tokens of x must be evenly strided")
-    if weights.dtype != x.dtype or tuple(weights.shape) != (6 * C, C) or not weights.is_contiguous() or not weights.is_cuda:
-        raise ValueError(f"row_attn: weights must be a contiguous ({6 * C}, {C}) {x.dtype} device tensor (pack.rowattn_pack)")
-    if vectors.dtype != torch.float32 or tuple(vectors.shape) != (12, C) or not vectors.is_contiguous() or not vectors.is_cuda:
-        raise ValueError(f"row_attn: vectors must be a contiguous (12, {C}) fp32 device tensor (pack.rowattn_vectors)")
+    _mat(weights, (6 * C, C), x.dtype, "row_attn: weights (pack.rowattn_pack)")
+    _mat(vectors, (12, C), torch.float32, "row_attn: vectors (pack.rowattn_vectors)")
     d = RowAttnDesc()
     out = torch.empty((nimg, h, w, C), device=x.device, dtype=x.dtype)
     d.x, d.x_stride, d.out, d.out_stride = x.data_ptr(), xs, out.data_ptr(), C
@@ -743,17 +767,11 @@ def row_attn(x: torch.Tensor, heads: int, cross: bool, weights: torch.Tensor, ve
     if ln_out_eps is not None:
         normed = torch.empty((nimg, h, w, C), device=x.device, dtype=x.dtype)
         d.ln_out, d.ln_out_stride, d.ln_out_eps = normed.data_ptr(), C, float(ln_out_eps)
-    ev = None
-    if ROW_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    _check(load().s2m2_row_attn(ctypes.byref(d), _stream()), "s2m2_row_attn")
     rows = nimg * h * w
     flops = 2.0 * rows * C * C * 6 + 4.0 * nimg * h * w * w * C
-    if ev is not None:
-        ev[1].record()
-        ROW_EVENTS.append((ev[0], ev[1], flops, 2.0 * rows * C * (3 if normed is not None else 2),      # unique bytes: rows read once, written once (+ ln_out)
-                           f"({nimg},{h},{w},{C}) heads {heads} {'cross' if cross else 'self'}"))
+    with _bracket(ROW_EVENTS, flops, 2.0 * rows * C * (3 if normed is not None else 2),      # unique bytes: rows read once, written once (+ ln_out)
+                  f"({nimg},{h},{w},{C}) heads {heads} {'cross' if cross else 'self'}"):
+        _check(load().s2m2_row_attn(ctypes.byref(d), _stream()), "s2m2_row_attn")
     _meter("row_attn", flops)
     return out if normed is None else (out, normed)
 
@@ -767,25 +785,21 @@ def pw_direct(srcs, weight_frag: torch.Tensor, bias: Optional[torch.Tensor], Cou
     """K11: a 1x1 layer on the channel concatenation of ``srcs`` ((N,H,W,Ci) / (..., Ci) tensors with contiguous channels and the same leading
     shape), weight in the fragment order of pack.pw_frag, fp32 bias (Cout) or None -> (..., Cout).  shuffle2 = C' > 0: the ConvTranspose2d(2,
     stride 2) store, Cout = 4 * C' -> (N, 2H, 2W, C')."""
+    _resident("pw_direct", *srcs, weight_frag, bias)
     x0 = srcs[0]
     d = PwDesc()
     d.nsrc = len(srcs)
     K = 0
     rows = None
     for i, x in enumerate(srcs):
-        r, xs = _token_rows(x, "pw_direct")
-        if rows is not None and r != rows:
-            raise ValueError("pw_direct: sources must have the same number of rows")
+        r, xs = _rows(x, "pw_direct")
+        if (rows is not None and r != rows) or x.dtype != x0.dtype:
+            raise ValueError("pw_direct: sources must have the same number of rows and one dtype")
         rows = r
-        if x.dtype != x0.dtype or not x.is_cuda:
-            raise ValueError("pw_direct: sources must be device tensors of one dtype")
         d.src[i], d.src_c[i], d.src_stride[i] = x.data_ptr(), x.shape[-1], xs
         K += x.shape[-1]
-    if weight_frag.dtype != x0.dtype or not weight_frag.is_cuda or not weight_frag.is_contiguous() or weight_frag.dim() != 4 or \
-            tuple(weight_frag.shape[2:]) != (64, 8) or weight_frag.shape[0] != (Cout + 31) // 32 or weight_frag.shape[1] != (K + 15) // 16:
-        raise ValueError(f"pw_direct: weight must be pack.pw_frag of a ({Cout}, {K}) matrix, got {tuple(weight_frag.shape)} {weight_frag.dtype}")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < Cout or not bias.is_cuda):
-        raise ValueError(f"pw_direct: bias must be fp32 ({Cout}) on the device")
+    _frag(weight_frag, Cout, K, x0.dtype, "pw_direct: weight (pack.pw_frag)")
+    _vec(bias, Cout, "pw_direct: bias", at_least=True, optional=True)
     if shuffle2:
         if x0.dim() != 4 or Cout != 4 * shuffle2:
             raise ValueError("pw_direct: shuffle2 needs (N,H,W,C) sources and Cout = 4 * shuffle2")
@@ -794,7 +808,7 @@ def pw_direct(srcs, weight_frag: torch.Tensor, bias: Optional[torch.Tensor], Cou
     else:
         out = torch.empty(tuple(x0.shape[:-1]) + (Cout,), device=x0.device, dtype=x0.dtype)
         d.out_stride = Cout
-    d.rows, d.weight_frag, d.bias, d.out = rows, weight_frag.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr()
+    d.rows, d.weight_frag, d.bias, d.out = rows, weight_frag.data_ptr(), _ptr(bias), out.data_ptr()
     d.Cout, d.act, d.dtype = Cout, act, _DT[x0.dtype]
     _check(load().s2m2_pw_direct(ctypes.byref(d), _stream()), "s2m2_pw_direct")
     _meter("conv2d", 2.0 * rows * K * Cout)                          # (as K5 counts the same layer: no MFMA-tile padding)
@@ -815,34 +829,29 @@ def conv_narrow(srcs, weight_frag: torch.Tensor, bias: Optional[torch.Tensor], K
     inside the same launch (Cin = 48 form) -> (..., Cout2); the Cout-channel tensor is not produced."""
     if isinstance(srcs, torch.Tensor):
         srcs = [srcs]
+    hf, hb, cout_final = head if head is not None else (None, None, Cout)
+    _resident("conv_narrow", *srcs, weight_frag, bias, hf, hb)
     if not 1 <= len(srcs) <= 2 or any(t.shape[:3] != srcs[0].shape[:3] or t.dtype != srcs[0].dtype for t in srcs):
         raise ValueError("conv_narrow: one or two (N,H,W,C) sources of the same grid and dtype")
     x = srcs[0]
-    xs = _nhwc(x)
+    xs = _pixels(x, "conv_narrow: source")
     n, h, w, _ = x.shape
     cin = sum(t.shape[-1] for t in srcs)
     K = KH * KW * cin
-    if weight_frag.dtype != x.dtype or not weight_frag.is_cuda or not weight_frag.is_contiguous() or weight_frag.dim() != 4 or \
-            tuple(weight_frag.shape[2:]) != (64, 8) or weight_frag.shape[0] != (Cout + 31) // 32 or weight_frag.shape[1] != (K + 15) // 16:
-        raise ValueError(f"conv_narrow: weight must be pack.narrow_frag of a ({Cout}, {K}) matrix, got {tuple(weight_frag.shape)} {weight_frag.dtype}")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() < Cout or not bias.is_cuda):
-        raise ValueError(f"conv_narrow: bias must be fp32 ({Cout}) on the device")
+    _frag(weight_frag, Cout, K, x.dtype, "conv_narrow: weight (pack.narrow_frag)")
+    _vec(bias, Cout, "conv_narrow: bias", at_least=True, optional=True)
     ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
-    cout_final = Cout
     if head is not None:
-        hf, hb, cout_final = head
-        if hf.dtype != x.dtype or not hf.is_cuda or not hf.is_contiguous() or tuple(hf.shape) != (1, 2 * ((Cout + 31) // 32), 64, 8):
-            raise ValueError(f"conv_narrow: head weight must be pack.head_frag of a (Cout2, {Cout}) matrix, got {tuple(hf.shape)} {hf.dtype}")
-        if hb is not None and (hb.dtype != torch.float32 or hb.numel() < cout_final or not hb.is_cuda):
-            raise ValueError(f"conv_narrow: head bias must be fp32 ({cout_final}) on the device")
+        _mat(hf, (1, 2 * ((Cout + 31) // 32), 64, 8), x.dtype, f"conv_narrow: head weight (pack.head_frag of a (Cout2, {Cout}) matrix)")
+        _vec(hb, cout_final, "conv_narrow: head bias", at_least=True, optional=True)
     out = torch.empty((n, ho, wo, cout_final), device=x.device, dtype=x.dtype)
     d = NarrowDesc()
     if head is not None:
-        d.head_frag, d.head_bias, d.head_cout = hf.data_ptr(), hb.data_ptr() if hb is not None else None, cout_final
+        d.head_frag, d.head_bias, d.head_cout = hf.data_ptr(), _ptr(hb), cout_final
     d.x, d.x_stride, d.N, d.H, d.W, d.Cin = x.data_ptr(), xs, n, h, w, cin
     if len(srcs) == 2:
-        d.x1, d.x1_stride, d.Cin1 = srcs[1].data_ptr(), _nhwc(srcs[1]), srcs[1].shape[-1]
-    d.weight_frag, d.bias, d.out, d.out_stride = weight_frag.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), cout_final
+        d.x1, d.x1_stride, d.Cin1 = srcs[1].data_ptr(), _pixels(srcs[1], "conv_narrow: source"), srcs[1].shape[-1]
+    d.weight_frag, d.bias, d.out, d.out_stride = weight_frag.data_ptr(), _ptr(bias), out.data_ptr(), cout_final
     d.Cout, d.KH, d.KW, d.stride, d.act, d.dtype = Cout, KH, KW, stride, act, _DT[x.dtype]
     _check(load().s2m2_conv_narrow(ctypes.byref(d), _stream()), "s2m2_conv_narrow")
     _meter("conv2d", 2.0 * n * ho * wo * (K * Cout + (Cout * cout_final if head is not None else 0)))   # (as K5 counts the same layers: no MFMA-tile padding)
@@ -864,6 +873,7 @@ def feature_fusion(z0: torch.Tensor, z1: torch.Tensor, w1: torch.Tensor, b1: tor
     w2 packed (C, 3C) = [gate.2 | fusion.2]; biases fp32.  z1_coarse: z0 is (N, 2h, 2w, C) and z1 the coarse (N, h, w, C) tensor,
     read through the bilinear x2 resampling.  frag: w1 is the fragment stream of BOTH layers (pack.fusion_frag(w1, w2), 9*C*C values),
     w2 is None -> the direct form (s2m2_feature_fusion_frag), meant for short row counts."""
+    _resident("feature_fusion", z0, z1, w1, b1, w2, bg, bf)
     C = z0.shape[-1]
     if z1.dtype != z0.dtype or z1.shape[-1] != C:
         raise ValueError("feature_fusion: z0 and z1 must match")
@@ -875,47 +885,44 @@ def feature_fusion(z0: torch.Tensor, z1: torch.Tensor, w1: torch.Tensor, b1: tor
     elif z1.shape != z0.shape:
         raise ValueError("feature_fusion: z0 and z1 must match")
     if frag:
-        if w2 is not None or w1.numel() != 9 * C * C or w1.dtype != z0.dtype or not w1.is_contiguous():
-            raise ValueError(f"feature_fusion: frag needs the {9 * C * C}-value fragment stream as w1 and w2 = None")
-    elif tuple(w1.shape) != (3 * C, 2 * C) or tuple(w2.shape) != (C, 3 * C) or w1.dtype != z0.dtype or w2.dtype != z0.dtype:
-        raise ValueError(f"feature_fusion: w1 must be ({3 * C}, {2 * C}) and w2 ({C}, {3 * C}) in {z0.dtype}")
-    for t, n in ((b1, 3 * C), (bg, C), (bf, C)):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
-            raise ValueError("feature_fusion: biases must be fp32 (3C), (C), (C)")
-    _dev(w1, b1, bg, bf) if frag else _dev(w1, w2, b1, bg, bf)
-    rows, s0 = _token_rows(z0, "feature_fusion")
-    _, s1 = _token_rows(z1, "feature_fusion")
+        if w2 is not None:
+            raise ValueError("feature_fusion: frag takes the fragment stream of both layers as w1 and w2 = None")
+        _vec(w1, 9 * C * C, "feature_fusion: w1 (pack.fusion_frag)", dtype=z0.dtype)
+    else:
+        _mat(w1, (3 * C, 2 * C), z0.dtype, "feature_fusion: w1")
+        _mat(w2, (C, 3 * C), z0.dtype, "feature_fusion: w2")
+    for name, t, n in (("b1", b1, 3 * C), ("bg", bg, C), ("bf", bf, C)):
+        _vec(t, n, f"feature_fusion: bias {name}")
+    rows, s0 = _rows(z0, "feature_fusion: z0")
+    _, s1 = _rows(z1, "feature_fusion: z1")
     out = torch.empty(z0.shape, device=z0.device, dtype=z0.dtype)
-    if frag:
-        _check(load().s2m2_feature_fusion_frag(z0.data_ptr(), z1.data_ptr(), out.data_ptr(), s0, s1, C, rows, C, w1.data_ptr(), b1.data_ptr(),
-                                               bg.data_ptr(), bf.data_ptr(), hc, wc, _DT[z0.dtype], _stream()), "s2m2_feature_fusion_frag")
-        _meter("feature_fusion", 2.0 * rows * C * C * 9)
-        return out
-    _check(load().s2m2_feature_fusion(z0.data_ptr(), z1.data_ptr(), out.data_ptr(), s0, s1, C, rows, C, w1.data_ptr(), b1.data_ptr(),
-                                      w2.data_ptr(), bg.data_ptr(), bf.data_ptr(), hc, wc, _DT[z0.dtype], _stream()), "s2m2_feature_fusion")
+    head = (z0.data_ptr(), z1.data_ptr(), out.data_ptr(), s0, s1, C, rows, C, w1.data_ptr(), b1.data_ptr())
+    tail = (bg.data_ptr(), bf.data_ptr(), hc, wc, _DT[z0.dtype], _stream())
+    if frag:                                                        # the direct form takes no second weight
+        _check(load().s2m2_feature_fusion_frag(*head, *tail), "s2m2_feature_fusion_frag")
+    else:
+        _check(load().s2m2_feature_fusion(*head, w2.data_ptr(), *tail), "s2m2_feature_fusion")
     _meter("feature_fusion", 2.0 * rows * C * C * 9)                # (2C -> 3C) + (C -> C) + (2C -> C)
     return out
 
 
 def layernorm(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """LayerNorm without affine over the last axis of a (..., C) tensor with contiguous channels and a uniform row stride."""
+    _resident("layernorm", x, out)
     C = x.shape[-1]
-    if x.stride(-1) != 1:
-        raise ValueError("layernorm: channels must be contiguous")
-    rows = x.numel() // C
-    xs = x.stride(-2) if x.dim() > 1 else C
-    for d in range(x.dim() - 2):
-        if x.shape[d] > 1 and x.stride(d) != x.stride(d + 1) * x.shape[d + 1]:
-            raise ValueError("layernorm: rows must have a uniform stride")
+    rows, xs = _rows(x, "layernorm")
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    else:
+        _mat(out, x.shape, x.dtype, "layernorm: out")
     _check(load().s2m2_layernorm(x.data_ptr(), out.data_ptr(), rows, C, xs, C, _DT[x.dtype], _stream()), "s2m2_layernorm")
     return out
 
 
 def groupnorm_nhwc(x: torch.Tensor, groups: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """nn.GroupNorm on a contiguous (N,H,W,C) tensor; gamma/beta fp32."""
-    _dev(x, gamma, beta)
+    _resident("groupnorm_nhwc", x, gamma, beta)
+    _contig("groupnorm_nhwc", x, gamma, beta)
     n, h, w, c = x.shape
     ws = torch.empty(load().s2m2_groupnorm_workspace_bytes(n, groups) // 8, device=x.device, dtype=torch.float64)
     out = torch.empty_like(x)
@@ -928,26 +935,25 @@ def convex_upsample(maps, logits: torch.Tensor, factor: int, scales=None, logit_
                     chan_out: Optional[torch.Tensor] = None):
     """maps: list of (B,1,hs,ws) or (B,hs,ws) fp32 tensors; logits (B,Ho,Wo,>=16) NHWC (9 used).  -> list of (B,1,Ho,Wo) fp32.
     chan_out: optional (B,Ho,Wo) view (one channel of an NHWC tensor, dense pixels) that also receives map 0 in its dtype."""
+    _resident("convex_upsample", *maps, logits, chan_out)
     B, hs, ws = maps[0].shape[0], maps[0].shape[-2], maps[0].shape[-1]
     n = len(maps)
     maps = [m.float().contiguous() for m in maps]
-    _dev(*maps)
-    ls = _nhwc(logits)
+    ls = _pixels(logits, "convex_upsample: logits")
     Ho, Wo = hs * factor, ws * factor
     exp_l = (B, hs, ws) if logit_up2 else (B, Ho, Wo)
     if tuple(logits.shape[:3]) != exp_l:
         raise ValueError(f"convex_upsample: logits must be {exp_l + ('>=16',)}, got {tuple(logits.shape)}")
     base = torch.empty((n, B, 1, Ho, Wo), device=logits.device, dtype=torch.float32)      # one allocation: callers can copy all maps at once
     outs = [base[k] for k in range(n)]
-    xp = (_vp * n)(*[m.data_ptr() for m in maps])
-    op = (_vp * n)(*[o.data_ptr() for o in outs])
     sc = (ctypes.c_float * n)(*[float(v) for v in (scales or [1.0] * n)])
-    if chan_out is not None and (chan_out.dtype != logits.dtype or tuple(chan_out.shape) != (B, Ho, Wo)):
-        raise ValueError("convex_upsample: chan_out must be a (B,Ho,Wo) channel view in the logits dtype")
-    _check(load().s2m2_convex_upsample(xp, op, sc, n, logits.data_ptr(), ls, B, hs, ws, factor, int(logit_up2),
-                                       chan_out.data_ptr() if chan_out is not None else None,
-                                       chan_out.stride(2) if chan_out is not None else 0, _DT[logits.dtype], _stream()),
-           "s2m2_convex_upsample")
+    cs = 0
+    if chan_out is not None:
+        if chan_out.dtype != logits.dtype or tuple(chan_out.shape) != (B, Ho, Wo):
+            raise ValueError("convex_upsample: chan_out must be a (B,Ho,Wo) channel view in the logits dtype")
+        cs = _pixels(chan_out.unsqueeze(-1), "convex_upsample: chan_out")       # as (B,Ho,Wo,1): the pixels of a one-channel NHWC view
+    _check(load().s2m2_convex_upsample(_ptrs(maps), _ptrs(outs), sc, n, logits.data_ptr(), ls, B, hs, ws, factor, int(logit_up2),
+                                       _ptr(chan_out), cs, _DT[logits.dtype], _stream()), "s2m2_convex_upsample")
     return outs
 
 
@@ -955,34 +961,21 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, swa
               pe: Optional[Tuple[torch.Tensor, torch.Tensor, int, int]] = None, scale: Optional[float] = None):
     """q, k, v: (nb, N, heads*D) views with contiguous channels and dense token rows (e.g. slices of a fused QKV buffer).
     -> out (nb, Nq, heads*D) [, pe_sum (nb, Nq, heads*32) when pe = (px (2w-1,16) fp32, py (2h-1,16) fp32, w, h)]."""
+    px, py, gw, gh = pe if pe is not None else (None, None, 0, 0)
+    _resident("attention", q, k, v, px, py)
+    _contig("attention: pe tables", px, py)
     nb, Nq, C = q.shape
     Nk = k.shape[1]
     D = C // heads
-    for t in (q, k, v):
-        if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)) or not t.is_cuda:
-            raise ValueError("attention: q/k/v must be device tensors with contiguous channels and dense token rows")
+    qs, ks, vs = (_rows(t, f"attention: {name}")[1] for name, t in (("q", q), ("k", k), ("v", v)))
     out = torch.empty((nb, Nq, C), device=q.device, dtype=q.dtype)
-    pe_out = None
-    px = py = None
-    gw = gh = 0
-    if pe is not None:
-        px, py, gw, gh = pe
-        _dev(px, py)
-        pe_out = torch.empty((nb, Nq, heads * 32), device=q.device, dtype=q.dtype)
+    pe_out = torch.empty((nb, Nq, heads * 32), device=q.device, dtype=q.dtype) if pe is not None else None
     flops = 4.0 * nb * heads * Nq * Nk * D                            # QK^T + PV (SURVEY.md Table A: 4 N^2 d per batch x head)
-    ev = None
-    if ATTN_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    _check(load().s2m2_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(1), k.stride(1), v.stride(1), C,
-                                 nb, heads, Nq, Nk, D, float(scale if scale is not None else D ** -0.5), int(swap_halves),
-                                 px.data_ptr() if px is not None else None, py.data_ptr() if py is not None else None,
-                                 pe_out.data_ptr() if pe_out is not None else None, heads * 32, gw, gh, _DT[q.dtype], _stream()),
-           "s2m2_attention")
-    if ev is not None:
-        ev[1].record()
-        ATTN_EVENTS.append((ev[0], ev[1], flops, f"({nb},{heads},{Nq},{D}){'+pe' if pe is not None else ''}",
-                            2.0 * nb * heads * D * (2 * Nq + 2 * Nk)))       # unique bytes: q, k, v read + o written (fp16)
+    with _bracket(ATTN_EVENTS, flops, f"({nb},{heads},{Nq},{D}){'+pe' if pe is not None else ''}",
+                  2.0 * nb * heads * D * (2 * Nq + 2 * Nk)):          # unique bytes: q, k, v read + o written (fp16)
+        _check(load().s2m2_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), qs, ks, vs, C, nb, heads, Nq, Nk, D,
+                                     float(scale if scale is not None else D ** -0.5), int(swap_halves), _ptr(px), _ptr(py), _ptr(pe_out),
+                                     heads * 32, gw, gh, _DT[q.dtype], _stream()), "s2m2_attention")
     _meter("attention", flops)
     return (out, pe_out) if pe is not None else out
 
@@ -997,8 +990,9 @@ def attention_supported(nb: int, heads: int, N: int, D: int, dtype: torch.dtype,
 
 def resample2x(x: torch.Tensor, mode: int) -> torch.Tensor:
     """(N,H,W,C) -> AvgPool2d(2) (mode 0) or bilinear x2, align_corners=False (mode 1)."""
+    _resident("resample2x", x)
+    xs = _pixels(x, "resample2x")
     n, h, w, c = x.shape
-    xs = _nhwc(x)
     out = torch.empty((n, h // 2, w // 2, c) if mode == 0 else (n, 2 * h, 2 * w, c), device=x.device, dtype=x.dtype)
     _check(load().s2m2_resample2x(x.data_ptr(), out.data_ptr(), n, h, w, c, xs, c, mode, _DT[x.dtype], _stream()), "s2m2_resample2x")
     return out
@@ -1007,7 +1001,8 @@ def resample2x(x: torch.Tensor, mode: int) -> torch.Tensor:
 def cv_lookup_into(cv: torch.Tensor, disp: torch.Tensor, buf: torch.Tensor, off1: int, off2: int, radius: int = 4) -> None:
     """K3 writing straight into channel slots of a wider NHWC tensor: taps of level 0 -> buf[..., off1:off1+2r+1], level 1 ->
     buf[..., off2:off2+2r+1] (buf (B,h,w,Cb) contiguous; the other channels are left untouched)."""
-    _dev(disp, buf)
+    _resident("cv_lookup_into", cv, disp, buf)
+    _contig("cv_lookup_into", disp, buf)
     pitch = _cv_pitch(cv, "cv_lookup")
     B, h, w, _ = cv.shape
     cb = buf.shape[-1]
@@ -1021,15 +1016,14 @@ _IMG_DT = {torch.float32: 0, torch.float16: 1, torch.uint8: 2}
 
 def image_prep(img0: torch.Tensor, img1: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """img0, img1 (B,3,H,W) fp32 / fp16 / uint8 in [0,255] -> x8 (2B,H,W,8): channels 1..3 = normalised RGB, others 0 (``out``: written in place)."""
+    _resident("image_prep", img0, img1, out)
     if img0.dtype not in _IMG_DT:
         img0 = img0.float()
     img1 = img1.to(img0.dtype)
     img0, img1 = img0.contiguous(), img1.contiguous()
-    _dev(img0, img1)
     B, _, H, W = img0.shape
     if out is not None:
-        if tuple(out.shape) != (2 * B, H, W, 8) or out.dtype != dtype or not out.is_contiguous() or out.device != img0.device:
-            raise RuntimeError(f"image_prep: out must be a contiguous {(2 * B, H, W, 8)} {dtype} tensor on {img0.device}")
+        _mat(out, (2 * B, H, W, 8), dtype, "image_prep: out")
         x8 = out
     else:
         x8 = torch.empty((2 * B, H, W, 8), device=img0.device, dtype=dtype)
@@ -1040,7 +1034,8 @@ def image_prep(img0: torch.Tensor, img1: torch.Tensor, dtype: torch.dtype, out: 
 
 def clock_probe(out: torch.Tensor) -> None:
     """Measurement aid: out (2,) int64 device tensor <- {shader-clock ticks, 100 MHz real-time ticks} when the stream reaches this point."""
-    _dev(out)
+    _resident("clock_probe", out)
+    _contig("clock_probe", out)
     _check(load().s2m2_debug_clock_probe(out.data_ptr(), _stream()), "s2m2_debug_clock_probe")
 
 
@@ -1051,20 +1046,22 @@ def poison_lds() -> None:
 
 def refine_prep(disp: torch.Tensor, conf: torch.Tensor, occ: Optional[torch.Tensor], mode: int, dtype: torch.dtype) -> torch.Tensor:
     """(B,1,h,w) fp32 maps -> (B,h,w,8) side input of the global (mode 0) / local (mode 1) refiner."""
-    _dev(disp, conf, occ)
+    _resident("refine_prep", disp, conf, occ)
+    _contig("refine_prep", disp, conf, occ)
     B, _, h, w = disp.shape
     out = torch.empty((B, h, w, 8), device=disp.device, dtype=dtype)
-    _check(load().s2m2_refine_prep(disp.data_ptr(), conf.data_ptr(), occ.data_ptr() if occ is not None else None, out.data_ptr(),
-                                   B * h * w, mode, _DT[dtype], _stream()), "s2m2_refine_prep")
+    _check(load().s2m2_refine_prep(disp.data_ptr(), conf.data_ptr(), _ptr(occ), out.data_ptr(), B * h * w, mode, _DT[dtype], _stream()),
+           "s2m2_refine_prep")
     return out
 
 
 def global_update(upd: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor, clamp0: bool) -> torch.Tensor:
     """upd (B,h,w,C>=1) NHWC (channel 0 used), disp/conf (B,1,h,w) fp32 -> refined disparity (B,1,h,w) fp32."""
-    _dev(disp, conf)
+    _resident("global_update", upd, disp, conf)
+    _contig("global_update", disp, conf)
     out = torch.empty_like(disp)
-    _check(load().s2m2_global_update(upd.data_ptr(), _nhwc(upd), disp.data_ptr(), conf.data_ptr(), out.data_ptr(), disp.numel(),
-                                     int(clamp0), _DT[upd.dtype], _stream()), "s2m2_global_update")
+    _check(load().s2m2_global_update(upd.data_ptr(), _pixels(upd, "global_update: upd"), disp.data_ptr(), conf.data_ptr(), out.data_ptr(),
+                                     disp.numel(), int(clamp0), _DT[upd.dtype], _stream()), "s2m2_global_update")
     return out
 
 
@@ -1072,18 +1069,19 @@ def refine_update(dco: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor, occ
                   want_small: bool = False):
     """dco (B,h,w,>=10) NHWC deltas; disp/conf/occ (B,1,h,w) fp32 -> new (disp, conf, occ) (fresh tensors) [, small (B,h,w,8): the
     refine_prep(mode 1) side input of the next iteration, from the same launch]."""
-    _dev(disp, conf, occ)
+    _resident("refine_update", dco, disp, conf, occ)
+    _contig("refine_update", disp, conf, occ)
     outs = torch.empty((3,) + tuple(disp.shape), device=disp.device, dtype=torch.float32)
     small = torch.empty((disp.shape[0], disp.shape[-2], disp.shape[-1], 8), device=disp.device, dtype=dco.dtype) if want_small else None
-    _check(load().s2m2_refine_update_to(dco.data_ptr(), _nhwc(dco), disp.data_ptr(), conf.data_ptr(), occ.data_ptr(),
-                                        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                                        small.data_ptr() if small is not None else None, disp.numel(), disp.shape[-1],
+    _check(load().s2m2_refine_update_to(dco.data_ptr(), _pixels(dco, "refine_update: dco"), disp.data_ptr(), conf.data_ptr(), occ.data_ptr(),
+                                        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), _ptr(small), disp.numel(), disp.shape[-1],
                                         int(use_positivity), _DT[dco.dtype], _stream()), "s2m2_refine_update_to")
     return (outs[0], outs[1], outs[2], small) if want_small else (outs[0], outs[1], outs[2])
 
 
 def tanh(x: torch.Tensor) -> torch.Tensor:
-    _dev(x)
+    _resident("tanh", x)
+    _contig("tanh", x)
     y = torch.empty_like(x)
     _check(load().s2m2_tanh(x.data_ptr(), y.data_ptr(), x.numel(), _DT[x.dtype], _stream()), "s2m2_tanh")
     return y
@@ -1091,11 +1089,14 @@ def tanh(x: torch.Tensor) -> torch.Tensor:
 
 def stem_mlp(x8: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
     """(N,H,W,8) -> (N,H,W,16): Conv1x1(8->16) - GELU - Conv1x1(16->16) per pixel (s2m2_stem_mlp); fp32 weights (16,8), (16,16), biases (16)."""
-    _dev(x8, w0, b0, w1, b1)
-    if x8.shape[-1] != 8 or tuple(w0.shape) != (16, 8) or tuple(w1.shape) != (16, 16) or b0.numel() != 16 or b1.numel() != 16:
-        raise ValueError("stem_mlp: x8 (...,8), w0 (16,8), w1 (16,16), biases (16)")
-    if any(t.dtype != torch.float32 for t in (w0, b0, w1, b1)):
-        raise ValueError("stem_mlp: weights and biases must be fp32")
+    _resident("stem_mlp", x8, w0, b0, w1, b1)
+    _contig("stem_mlp", x8)
+    if x8.shape[-1] != 8:
+        raise ValueError("stem_mlp: x8 must be (..., 8)")
+    _mat(w0, (16, 8), torch.float32, "stem_mlp: w0")
+    _mat(w1, (16, 16), torch.float32, "stem_mlp: w1")
+    _vec(b0, 16, "stem_mlp: b0")
+    _vec(b1, 16, "stem_mlp: b1")
     out = torch.empty(tuple(x8.shape[:-1]) + (16,), device=x8.device, dtype=x8.dtype)
     _check(load().s2m2_stem_mlp(x8.data_ptr(), w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), out.data_ptr(),
                                 x8.numel() // 8, _DT[x8.dtype], _stream()), "s2m2_stem_mlp")
@@ -1104,10 +1105,10 @@ def stem_mlp(x8: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w1: torch.Ten
 
 def image_pad(img: torch.Tensor, factor: int = 32) -> torch.Tensor:
     """Reference image_pad (image_utils.py:27-71) on the device: (B,C,H,W) fp32/fp16/uint8 -> (B,C,Hn,Wn) fp32."""
+    _resident("image_pad", img)
     if img.dtype not in _IMG_DT:
         img = img.float()
     img = img.contiguous()
-    _dev(img)
     B, C, H, W = img.shape
     Hn, Wn = -(-H // factor) * factor, -(-W // factor) * factor
     pooled = torch.empty((B, C, H // factor, W // factor), device=img.device, dtype=torch.float32)
@@ -1124,7 +1125,8 @@ def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torc
     """s2m2_cloud (K15): the padded maps (B,1,Hp,Wp) fp32 and the UNPADDED left image (B,3,H,W) uint8 / fp16 / fp32 -> the outputs the caller
     allocated: ``records`` (B, capacity, 4) int32 = 16-byte point records in raster order with ``count`` (B) int32 and a ``workspace`` of
     ``cloud_workspace_bytes`` bytes, ``depth`` (B,1,H,W) fp32, ``mask`` (B,1,H,W) uint8.  Thin: no allocation, no synchronisation."""
-    _dev(disp, occ, conf, image, records, count, workspace, depth, mask)
+    _resident("cloud", disp, occ, conf, image, records, count, workspace, depth, mask)
+    _contig("cloud", disp, occ, conf, image, records, count, workspace, depth, mask)
     if disp.dtype != torch.float32 or occ.dtype != torch.float32 or conf.dtype != torch.float32 or disp.dim() != 4 or disp.shape[1] != 1:
         raise ValueError("cloud: disp / occ / conf must be (B,1,Hp,Wp) fp32 tensors")
     if occ.shape != disp.shape or conf.shape != disp.shape:
@@ -1137,18 +1139,15 @@ def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torc
     d.disp, d.occ, d.conf, d.image = disp.data_ptr(), occ.data_ptr(), conf.data_ptr(), image.data_ptr()
     d.B, d.H, d.W, d.Hp, d.Wp, d.image_dtype, d.unfiltered = B, H, W, Hp, Wp, _IMG_DT[image.dtype], int(unfiltered)
     if depth is not None:
-        if depth.dtype != torch.float32 or tuple(depth.shape) != (B, 1, H, W):
-            raise ValueError("cloud: depth must be a (B,1,H,W) fp32 tensor")
+        _mat(depth, (B, 1, H, W), torch.float32, "cloud: depth")
         d.depth = depth.data_ptr()
     if mask is not None:
-        if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, 1, H, W):
-            raise ValueError("cloud: mask must be a (B,1,H,W) uint8 tensor")
+        _mat(mask, (B, 1, H, W), torch.uint8, "cloud: mask")
         d.mask = mask.data_ptr()
     if count is not None:
-        if count.dtype != torch.int32 or count.numel() != B:
-            raise ValueError("cloud: count must hold B int32")
+        _vec(count, B, "cloud: count", dtype=torch.int32)
         need = cloud_workspace_bytes(B, H, W)
-        if workspace is None or workspace.numel() * workspace.element_size() < need:
+        if workspace is None or workspace.nbytes < need:
             raise ValueError(f"cloud: a workspace of {need} bytes is required with count")
         d.count, d.workspace = count.data_ptr(), workspace.data_ptr()
         if records is not None:
@@ -1178,7 +1177,8 @@ def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, map
     ``maps`` (n_img,2,Hd,Wd) fp32.  With ``out`` None no source is read (``srcs`` gives the source extents only; pass ``hd`` / ``wd`` then, or
     they are taken from ``maps``).  Thin: no allocation, no synchronisation."""
     srcs = list(srcs)
-    _dev(*srcs, records, out, maps)
+    _resident("rectify", *srcs, records, out, maps)
+    _contig("rectify", *srcs, records, out, maps)
     if len(srcs) not in (1, 2) or any(t.shape != srcs[0].shape or t.dtype != srcs[0].dtype for t in srcs):
         raise ValueError("rectify: one or two source images of one shape and dtype")
     s0 = srcs[0]
@@ -1199,14 +1199,13 @@ def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, map
     Hd, Wd = (hd, wd) if hd is not None and wd is not None else ref.shape[-2:]
     d = RectifyDesc()
     if out is not None:
-        if out.dtype not in (torch.float32, torch.uint8) or tuple(out.shape) != (n, 3, Hd, Wd):
+        if out.dtype not in (torch.float32, torch.uint8):
             raise ValueError("rectify: out must be an (n_img,3,Hd,Wd) fp32 or uint8 tensor")
+        _mat(out, (n, 3, Hd, Wd), out.dtype, "rectify: out")
         d.out, d.out_dtype = out.data_ptr(), _IMG_DT[out.dtype]
-        d.src[0] = srcs[0].data_ptr()
-        d.src[1] = srcs[-1].data_ptr()
+        d.src[0], d.src[1] = srcs[0].data_ptr(), srcs[-1].data_ptr()
     if maps is not None:
-        if maps.dtype != torch.float32 or tuple(maps.shape) != (n, 2, Hd, Wd):
-            raise ValueError("rectify: maps must be an (n_img,2,Hd,Wd) fp32 tensor")
+        _mat(maps, (n, 2, Hd, Wd), torch.float32, "rectify: maps")
         d.maps = maps.data_ptr()
     d.records, d.n_src, d.n_img, d.Hs, d.Ws, d.Hd, d.Wd = records.data_ptr(), len(srcs), n, Hs, Ws, Hd, Wd
     d.src_format, d.round, d.order = fmt, int(bool(round)), order

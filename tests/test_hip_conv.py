@@ -163,7 +163,7 @@ def test_conv_frag_stream(hip, case, ph):
 
 def test_conv_frag_argument_checks(hip):
     x = torch.zeros(1, 8, 8, 128, device="cuda", dtype=torch.float16)
-    w = pack.pack_conv_frag(torch.zeros(128, 128, 3, 3), torch.float16)
+    w = pack.pack_conv_frag(torch.zeros(128, 128, 3, 3), torch.float16).cuda()      # (a host weight never reaches the library: the binding refuses it)
     with pytest.raises(RuntimeError, match="K order 2"):
         hip.conv2d([x], w, None, 3, 3, 128, korder=2, stride=2)
     x32 = x.float()
