@@ -27,6 +27,7 @@
 //           runs once per query after the key loop.  (A first version binned with ds_add_f32: twice SLOWER than the VALU loop.)
 // fp16: v_mfma_f32_32x32x16_f16 with fp32 softmax/accumulators;  fp32 (parity mode): exact v_mfma_f32_32x32x2_f32.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 
 #ifndef S2M2_ATTN_DBG
@@ -622,7 +623,6 @@ __global__ __launch_bounds__(CFG::MAXW * 64) void attention_kernel(AttnArgs a) {
 template <typename T, int DP, bool PE, int MINW, bool KSPLIT, int NXT, int NYT>
 static int launch_attn_t(const AttnArgs& a, int nw, hipStream_t st) {
     using CFG = AttnCfg<T, DP, PE, MINW, KSPLIT, NXT, NYT>;
-    auto kern = attention_kernel<CFG, T>;
     size_t lds = CFG::K_BYTES + CFG::V_BYTES;
     if (KSPLIT) lds = lds > CFG::MERGE_BYTES ? lds : CFG::MERGE_BYTES;
     if (CFG::QLDS) lds = CFG::Q_OFF + (size_t)nw * CFG::Q_WAVE_BYTES;
@@ -635,17 +635,14 @@ static int launch_attn_t(const AttnArgs& a, int nw, hipStream_t st) {
     }
     if (lds > kLdsBytes) return set_error("attention: %zu bytes of LDS needed (head dim %d, %d x %d token grid)", lds, a.D, a.gw, a.gh);
     if (a.dry) return 0;
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), lds, lds_granted, "attention")) return 1;
     const int ntq = (a.Nq + 31) / 32;
     const int nblk = KSPLIT ? ntq : (ntq + nw - 1) / nw;
     if ((long long)nblk * a.nb * a.heads >= (1LL << 31)) return set_error("attention: %lld blocks do not fit a grid dimension", (long long)nblk * a.nb * a.heads);
     AttnArgs b = a;
     b.nblk = nblk;
-    static const bool xcd_off = [] { const char* e = getenv("S2M2_ATTN_XCD"); return e && e[0] == '0'; }();   // A/B switch (profiles/r05/ab_attn_xcd.txt)
+    static const bool xcd_off = env_is0("S2M2_ATTN_XCD");   // A/B switch (profiles/r05/ab_attn_xcd.txt)
     b.xcd = xcd_off ? 0 : 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * a.nb * a.heads)), dim3(nw * 64), lds, st, b);
-    return check_launch("attention");
+    return launch<attention_kernel<CFG, T>>("attention", dim3((unsigned)(nblk * a.nb * a.heads)), dim3(nw * 64), lds, st, b);
 }
 
 // PE variant: bin tiles sized for the token grid -- (2, 1) covers grids up to 64 x 32 (the 1/32 grid of 2048 x 1024 images), (3, 2) up to
@@ -678,7 +675,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
     const int bh = a.nb * a.heads;
     // register-heavy head dims (d >= 96: ~190-250 VGPRs = 8 waves per CU): blocks of at most 4 waves so that two are co-resident
     int maxw = (DP >= 96 && MAXW > 4) ? 4 : MAXW;
-    static const int maxw_env = [] { const char* e = getenv("S2M2_ATTN_MAXW"); return e ? atoi(e) : 0; }();   // experiment switch
+    static const int maxw_env = (int)env_int("S2M2_ATTN_MAXW", 0);   // experiment switch
     if (maxw_env > 0 && maxw_env <= MAXW) maxw = maxw_env;
     int nblk = (ntq + maxw - 1) / maxw;
     int nw = (ntq + nblk - 1) / nblk;                              // <= maxw waves per block, minimal idle tail
@@ -746,9 +743,10 @@ static int attention_entry(const void* q, const void* k, const void* v, void* ou
     a.nb = nb; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.D = D; a.swap = swap_halves; a.scale = scale;
     a.px = pe_x; a.py = pe_y; a.pe_out = pe_out; a.spe = pe_stride; a.gw = grid_w; a.gh = grid_h; a.dry = dry;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16) return pe ? dispatch_attn<half_t, true>(a, st) : dispatch_attn<half_t, false>(a, st);
-    if (dtype == S2M2_F32) return pe ? dispatch_attn<float, true>(a, st) : dispatch_attn<float, false>(a, st);
-    return set_error("attention: unsupported dtype %d", dtype);
+    return by_dtype(dtype, "attention", [&](auto t) {
+        using T = decltype(t);
+        return pe ? dispatch_attn<T, true>(a, st) : dispatch_attn<T, false>(a, st);
+    });
 }
 
 static int attention_impl(const void* q, const void* k, const void* v, void* out, long long q_stride, long long k_stride,

@@ -18,9 +18,10 @@
 //     K loop; `carry` adds the output of stage 0 (still in the other LDS buffer) to the last stage of a 3-stage chain.
 // Every intermediate is rounded to the I/O dtype exactly where the separate launches round it (tile in LDS instead of HBM).
 #include "common.h"
+#include "chain_select.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
-#include <stdlib.h>
 
 namespace s2m2 {
 
@@ -576,11 +577,7 @@ __global__ __launch_bounds__(CFG::NT, (CFG::DIRECT && CFG::C == 128) ? S2M2_CHAI
 template <typename T, int C, int BM, int NST, int NW, int WP = 4>
 static int launch_chain(const ChainArgs& a, hipStream_t st) {
     using CFG = ChainCfg<T, C, BM, NST, NW, WP>;
-    auto kern = mlp_chain_kernel<CFG, T>;
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "mlp_chain")) return 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.rows + BM - 1) / BM)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
-    return check_launch("mlp_chain");
+    return launch<mlp_chain_kernel<CFG, T>>("mlp_chain", dim3((unsigned)((a.rows + BM - 1) / BM)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
 }
 
 template <typename T, int C, int BM, int NW, int WP = 4>
@@ -602,12 +599,12 @@ extern "C" int s2m2_mlp_chain_supported(int C, int dtype) {
 // C = 384 / 512).  C = 512 (r06: the L model's 1/16 and 1/32 levels, 54 launches per forward on the LDS-staged form before): 16 waves = four per SIMD,
 // 128 registers each, 32-row tiles only
 extern "C" int s2m2_mlp_chain_frag_supported(int C, int dtype) {
-    static const bool no512 = getenv("S2M2_CHAIN_FRAG512") != nullptr && atoi(getenv("S2M2_CHAIN_FRAG512")) == 0;      // A/B switch
+    static const bool no512 = s2m2::env_is0("S2M2_CHAIN_FRAG512");      // A/B switch
     return dtype == S2M2_F16 && (C == 128 || C == 192 || C == 256 || C == 384 || (C == 512 && !no512));
 }
 
 namespace s2m2 {
-// direct form, by width: 32-row tiles while they fit the chip in about one round, else 64-row tiles (half the weight traffic per row)
+// direct form, by width and tile height (chain_select.h)
 template <int NST>
 static int launch_chain_direct(const ChainArgs& a, int C, bool tall, hipStream_t st) {
     switch (C) {
@@ -618,10 +615,9 @@ static int launch_chain_direct(const ChainArgs& a, int C, bool tall, hipStream_t
         default: return tall ? launch_chain<half_t, 384, 64, NST, 12, 0>(a, st) : launch_chain<half_t, 384, 32, NST, 12, 0>(a, st);
     }
 }
-static bool chain_direct_tall(int C, long long rows) {
-    static const int force_bm = getenv("S2M2_CHAIN_DIRECT_BM") ? atoi(getenv("S2M2_CHAIN_DIRECT_BM")) : 0;      // 32 / 64 forces one (tuning)
-    if (C >= 384) return false;                                    // (64-row tiles at 12 waves per block spill: 55 - 88 registers; 16 waves: 128 registers each)
-    return force_bm ? force_bm == 64 : rows > (C == 128 ? 24576 : C == 192 ? 16384 : 8192);
+static ChainChoice chain_choice(const s2m2_chain_desc* d) {
+    static const ChainTuning tuning = {env_is0("S2M2_K9_XCD"), (int)env_int("S2M2_CHAIN_DIRECT_BM", 0)};
+    return chain_select(d->C, d->dtype, d->rows, d->nstage, d->nfan, d->weight_frag, d->xcd_group_rows, tuning);
 }
 }  // namespace s2m2
 
@@ -650,10 +646,8 @@ static int mlp_chain_impl(const s2m2_chain_desc* d, void* stream) {
         f.fan_w = d->fan_weight; f.fan_b = d->fan_bias; f.fan_wsum = d->fan_ln_wsum; f.fan_out = d->fan_out; f.fan_out_stride = d->fan_out_stride;
         f.nfan = d->nfan;
         f.pool_h = d->pool_h; f.pool_w = d->pool_w;
-        f.zero = zero_page();
-        S2M2_REQUIRE(f.zero, "mlp_chain: cannot allocate the zero page");
-        hipStream_t fst = static_cast<hipStream_t>(stream);
-        return launch_chain_direct<0>(f, d->C, chain_direct_tall(d->C, d->rows), fst);
+        if (bind_zero_page(f, "mlp_chain")) return 1;
+        return launch_chain_direct<0>(f, d->C, chain_choice(d).BM == 64, static_cast<hipStream_t>(stream));
     }
     S2M2_REQUIRE(d->nstage != 0, "mlp_chain: fan-out only (nstage = 0) exists in the direct form: weight_frag = 1, fp16, C = 128 / 192 / 256 / 384 / 512");
     S2M2_REQUIRE(d->out, "mlp_chain: null out");
@@ -698,29 +692,20 @@ static int mlp_chain_impl(const s2m2_chain_desc* d, void* stream) {
         S2M2_REQUIRE(d->ln_gamma && d->ln_beta && d->ln_out_eps > 0.f && d->ln_out_stride >= d->C && d->ln_out_stride % 8 == 0,
                      "mlp_chain: ln_out needs gamma, beta, a positive eps and a row stride that is a multiple of 8");
     }
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "mlp_chain: cannot allocate the zero page");
-    a.xcd_tiles = 0;
-    static const bool xcd_off = getenv("S2M2_K9_XCD") != nullptr && atoi(getenv("S2M2_K9_XCD")) == 0;    // A/B switch
-    const int bm = (d->dtype == S2M2_F32 || d->rows <= 8192 || d->C >= 384) ? 32 : 64;   // (the tile heights picked below)
-    if (d->xcd_group_rows > 0 && !xcd_off && d->xcd_group_rows % bm == 0 && d->rows % (8LL * d->xcd_group_rows) == 0)
-        a.xcd_tiles = (int)(d->xcd_group_rows / bm);
+    if (bind_zero_page(a, "mlp_chain")) return 1;
+    const ChainChoice c = chain_choice(d);
+    a.xcd_tiles = c.xcd_tiles;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const char cfg = d->rows <= 8192 ? 's' : 'm';                 // at most one 32-row tile per CU: short tiles, more CUs busy (measured: tools/chainbench.py)
-    if (d->weight_frag) {                                         // direct form: 32-row tiles, one wave per 32 couts
-        a.xcd_tiles = (d->xcd_group_rows > 0 && !xcd_off && d->xcd_group_rows % 32 == 0 && d->rows % (8LL * d->xcd_group_rows) == 0) ? (int)(d->xcd_group_rows / 32) : 0;
-        const bool tall = chain_direct_tall(d->C, d->rows);
-        if (tall) a.xcd_tiles = a.xcd_tiles % 2 == 0 ? a.xcd_tiles / 2 : 0;
+    const bool tall = c.BM == 64;
+    if (c.form == ChainForm::direct) {
         if (d->nstage == 1) return launch_chain_direct<1>(a, d->C, tall, st);
         if (d->nstage == 2) return launch_chain_direct<2>(a, d->C, tall, st);
         return launch_chain_direct<3>(a, d->C, tall, st);
     }
     if (d->dtype == S2M2_F16) {
         switch (d->C) {
-            case 128:
-                return cfg == 's' ? launch_chain_n<half_t, 128, 32, 4>(a, d->nstage, st) : launch_chain_n<half_t, 128, 64, 4>(a, d->nstage, st);
-            case 256:
-                return cfg == 's' ? launch_chain_n<half_t, 256, 32, 8>(a, d->nstage, st) : launch_chain_n<half_t, 256, 64, 8>(a, d->nstage, st);
+            case 128: return tall ? launch_chain_n<half_t, 128, 64, 4>(a, d->nstage, st) : launch_chain_n<half_t, 128, 32, 4>(a, d->nstage, st);
+            case 256: return tall ? launch_chain_n<half_t, 256, 64, 8>(a, d->nstage, st) : launch_chain_n<half_t, 256, 32, 8>(a, d->nstage, st);
             case 384: return launch_chain_n<half_t, 384, 32, 4>(a, d->nstage, st);
             default: return launch_chain_n<half_t, 512, 32, 8>(a, d->nstage, st);
         }

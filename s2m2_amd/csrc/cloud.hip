@@ -7,6 +7,7 @@
 // offset is (the first group of a row starts (Wp-W)/2 % 4 pixels left of the image): with Wp % 4 == 0 every map read is one aligned 16-byte
 // load that stays inside the padded row.  Image reads and the dense stores follow the unpadded rows and are per pixel unless a group is aligned.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 
 namespace s2m2 {
@@ -254,20 +255,14 @@ static int cloud_impl(const s2m2_cloud_desc* d, void* stream) {
                      ((uintptr_t)d->depth & 15) == 0 && ((uintptr_t)d->mask & 3) == 0;
     const dim3 grid(p.tiles, d->B), block(kCloudThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(cloud_count_kernel<true>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(cloud_count_kernel<false>, grid, block, 0, s, p);
-    if (int rc = check_launch("cloud (count)")) return rc;
+    if (int rc = vec ? launch<cloud_count_kernel<true>>("cloud (count)", grid, block, 0, s, p) : launch<cloud_count_kernel<false>>("cloud (count)", grid, block, 0, s, p))
+        return rc;
     if (!d->count) return 0;
-#define S2M2_CLOUD_B(IT)                                                                      \
-    do {                                                                                      \
-        if (vec) hipLaunchKernelGGL((cloud_scatter_kernel<true, IT>), grid, block, 0, s, p);  \
-        else hipLaunchKernelGGL((cloud_scatter_kernel<false, IT>), grid, block, 0, s, p);     \
-    } while (0)
-    if (d->image_dtype == S2M2_F32) S2M2_CLOUD_B(float);
-    else if (d->image_dtype == S2M2_F16) S2M2_CLOUD_B(half_t);
-    else S2M2_CLOUD_B(unsigned char);
-#undef S2M2_CLOUD_B
-    return check_launch("cloud (scatter)");
+    return by_image_dtype(d->image_dtype, "cloud", [&](auto ti) {            // (validated above)
+        using IT = decltype(ti);
+        if (vec) return launch<cloud_scatter_kernel<true, IT>>("cloud (scatter)", grid, block, 0, s, p);
+        return launch<cloud_scatter_kernel<false, IT>>("cloud (scatter)", grid, block, 0, s, p);
+    });
 }
 
 }  // namespace s2m2

@@ -17,8 +17,9 @@
 //            pieces of whole pixel rows (NHWC: channels contiguous) for the aux epilogue and fully coalesced stores.
 // fp16: v_mfma_f32_32x32x16_f16, fp32 accumulate.  fp32 (parity mode): exact v_mfma_f32_32x32x2_f32.
 #include "common.h"
+#include "conv_select.h"
+#include "launch.h"
 #include "plan.h"
-#include <stdlib.h>
 
 // compile-time ablation switches (tools/conv_ablate.py; never set in the shipped library):
 // 2 no MFMA, 8 no fragment reads, 16 no bias/activation math, 32 no global stores, 64 no K loop at all
@@ -1325,8 +1326,8 @@ struct ConvCfgP {
     static constexpr int CRS = BN + VEC;
     static constexpr size_t A_BYTES = (size_t)2 * BM * RS * sizeof(T);
     static constexpr size_t C_BYTES = (size_t)BM * CRS * sizeof(T);
-    static size_t w_bytes(int K) { return (size_t)BN * (K + VEC) * sizeof(T); }
-    static size_t lds_bytes(int K) { return A_BYTES + C_BYTES + w_bytes(K); }
+    static constexpr size_t w_bytes(int K) { return (size_t)BN * (K + VEC) * sizeof(T); }
+    static constexpr size_t lds_bytes(int K) { return A_BYTES + C_BYTES + w_bytes(K); }
 };
 
 template <typename CFG, typename T>
@@ -1454,77 +1455,50 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(ConvArgs p, int ntiles) {
     }
 }
 
+// Launchers: one per kernel family.  Whether the family can take the layer was decided by conv_select (conv_select.h); these compute the grid.
 template <typename T, int BM, int BN, int WGM, int PPR = 8, int NPF = 1, int NWAVES = 4, int MODE = 0>
 static int launch_conv(const ConvArgs& a, hipStream_t st) {
     using CFG = ConvCfg<T, BM, BN, WGM, PPR, NPF, NWAVES>;
-    auto kern = conv_igemm_kernel<CFG, T, MODE>;
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "conv2d")) return 1;
     const long long M = (long long)a.N * a.Ho * a.Wo;
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((a.Cout + BN - 1) / BN));
-    hipLaunchKernelGGL(kern, grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a);
-    return check_launch("conv2d");
+    return launch<conv_igemm_kernel<CFG, T, MODE>>("conv2d", grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a);
 }
 
 template <typename T, int BM, int BN, int KP, int NS>
 static int launch_conv2(const ConvArgs& a, hipStream_t st) {
     using CFG = ConvCfg2<T, BM, BN, KP, NS>;
-    auto kern = conv_igemm2_kernel<CFG, T>;
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "conv2d")) return 1;
     const long long M = (long long)a.N * a.Ho * a.Wo;
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((a.Cout + BN - 1) / BN));
-    hipLaunchKernelGGL(kern, grid, dim3(256), CFG::LDS_BYTES, st, a);
-    return check_launch("conv2d");
+    return launch<conv_igemm2_kernel<CFG, T>>("conv2d", grid, dim3(256), CFG::LDS_BYTES, st, a);
 }
 
 template <typename T, int BN, int NWAVES = 4, int WGM = 2, int DW = 1>
 static int launch_conv_halo(const ConvArgs& a, hipStream_t st) {
     using CFG = ConvCfgH<T, BN, NWAVES, WGM, DW>;
-    auto kern = conv_halo_kernel<CFG, T>;
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "conv2d")) return 1;
-    if (a.stride != 1 || a.shuffle2 || a.korder || a.KH > 3 || a.KW > 3) return set_error("conv2d: the halo tile needs a stride-1 kernel of at most 3x3 taps in K order 0");
     const int tx = (a.W + CFG::PW - 1) / CFG::PW, ty = (a.H + CFG::PH - 1) / CFG::PH;
     dim3 grid((unsigned)(a.N * tx * ty), (unsigned)((a.Cout + BN - 1) / BN));
-    hipLaunchKernelGGL(kern, grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
-    return check_launch("conv2d");
+    return launch<conv_halo_kernel<CFG, T>>("conv2d", grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
 }
 
+// naux: epilogue operands parked in registers (two operands of 8 pieces each do not fit the 128-pixel block's register budget: conv_select
+// refuses them)
 template <typename T, int BN, int CH, int PH = 4, int PW = 32>
-static int launch_conv_frag(const ConvArgs& a, hipStream_t st) {
-    if constexpr (sizeof(T) != 2) {
-        return set_error("conv2d: K order 2 (fragment stream) is an fp16 layout");
-    } else {
-        using CFG = ConvCfgF<T, BN, CH, PH, PW>;
-        const bool two = a.epi == S2M2_EPI_GRU || a.epi == S2M2_EPI_GATEMIX;
-        const int naux = a.epi == S2M2_EPI_NONE ? 0 : two ? 2 : 1;   // epilogue operands parked in registers
-        // (two operands of 8 pieces each do not fit the 128-pixel block's register budget: rejected below, the instantiation is a dummy)
-        auto kern = naux == 0 ? conv_frag_kernel<CFG, T, 0> : (naux == 2 && PH == 2) ? conv_frag_kernel<CFG, T, (PH == 2 ? 2 : 1)>
-                                                                                      : conv_frag_kernel<CFG, T, 1>;
-        static size_t lds_granted[3][kMaxDevices] = {};                 // per instantiation and epilogue-operand variant
-        if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted[naux], "conv2d")) return 1;
-        if (a.stride != 1 || a.shuffle2 || a.KH > 3 || a.KW > 3 || a.KH * a.KW < 2 || a.Cout % BN || a.Cin % 8 || a.ln_wsum)
-            return set_error("conv2d: K order 2 needs a stride-1 3x3 / 3x1 / 1x3 layer with Cout a multiple of %d (Cout=%d)", BN, a.Cout);
-        if (a.epi == S2M2_EPI_DUALMIX || (PH == 4 && (a.epi == S2M2_EPI_GRU || a.epi == S2M2_EPI_GATEMIX)))
-            return set_error("conv2d: K order 2 with 128-pixel blocks takes one-operand epilogues only (epi=%d has two)", a.epi);
-        if (PW != 32 && naux == 2) return set_error("conv2d: K order 2 with 160-pixel blocks takes one-operand epilogues only (epi=%d has two)", a.epi);
-        const int tx = (a.W + CFG::PW - 1) / CFG::PW, ty = (a.H + CFG::PH - 1) / CFG::PH;
-        dim3 grid((unsigned)(a.N * tx * ty), (unsigned)(a.Cout / BN));
-        hipLaunchKernelGGL(kern, grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
-        return check_launch("conv2d");
-    }
+static int launch_conv_frag(const ConvArgs& a, hipStream_t st, int naux) {
+    using CFG = ConvCfgF<T, BN, CH, PH, PW>;
+    const int tx = (a.W + CFG::PW - 1) / CFG::PW, ty = (a.H + CFG::PH - 1) / CFG::PH;
+    dim3 grid((unsigned)(a.N * tx * ty), (unsigned)(a.Cout / BN));
+    if (naux == 0) return launch<conv_frag_kernel<CFG, T, 0>>("conv2d", grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
+    if constexpr (PH == 2)
+        if (naux == 2) return launch<conv_frag_kernel<CFG, T, 2>>("conv2d", grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
+    return launch<conv_frag_kernel<CFG, T, 1>>("conv2d", grid, dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
 }
 
 template <typename T, int BN>
 static int launch_conv_pw(const ConvArgs& a, hipStream_t st) {
     using CFG = ConvCfgP<T, BN>;
-    auto kern = conv_pw_kernel<CFG, T>;
-    if (a.KH != 1 || a.KW != 1 || a.stride != 1) return set_error("conv2d: the pointwise kernel needs a 1x1 stride-1 layer");
+    static_assert(CFG::lds_bytes(0) == conv_pw_lds_bytes(BN, 0, sizeof(T)) && CFG::lds_bytes(64) == conv_pw_lds_bytes(BN, 64, sizeof(T)),
+                  "conv_select.h checks this kernel's LDS bound with its own copy of the (linear) formula");
     const size_t lds = CFG::lds_bytes(a.Cin);
-    if (lds > 160 * 1024) return set_error("conv2d: pointwise kernel: Cin=%d needs %zu bytes of LDS", a.Cin, lds);
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), lds, lds_granted, "conv2d")) return 1;
     const long long M = (long long)a.N * a.H * a.W;
     const int ntiles = (int)((M + CFG::BM - 1) / CFG::BM);
     const int per_cu = (int)(160 * 1024 / lds) < 4 ? (int)(160 * 1024 / lds) : 4;      // co-resident blocks per CU
@@ -1532,141 +1506,90 @@ static int launch_conv_pw(const ConvArgs& a, hipStream_t st) {
     int gx = 256 * per_cu / ny;                                   // persistent grid: one wave of blocks over the chip
     gx = gx < 1 ? 1 : gx;
     gx = gx > ntiles ? ntiles : gx;
-    hipLaunchKernelGGL(kern, dim3(gx, ny), dim3(256), lds, st, a, ntiles);
-    return check_launch("conv2d");
+    return launch<conv_pw_kernel<CFG, T>>("conv2d", dim3(gx, ny), dim3(256), lds, st, a, ntiles);
+}
+
+static const ConvTuning& conv_tuning() {                          // read once, at the first s2m2_conv2d call
+    static const ConvTuning t = [] {
+        ConvTuning t;
+        t.frag_ph = (int)env_int("S2M2_FRAG_PH", t.frag_ph);
+        t.frag_pw = (int)env_int("S2M2_FRAG_PW", t.frag_pw);
+        t.frag_aux_pw = (int)env_int("S2M2_FRAG_AUX_PW", t.frag_aux_pw);
+        t.t20_min = env_int("S2M2_T20_MIN", t.t20_min);
+        t.small_tile = (int)env_int("S2M2_SMALL_TILE", t.small_tile);
+        t.no_halo8 = env_flag("S2M2_CONV_NO_HALO8");
+        t.halo_big_min = env_int("S2M2_HALO_BIG_MIN", t.halo_big_min);
+        t.halo_narrow = (int)env_int("S2M2_HALO_NARROW", t.halo_narrow);
+        t.halo_coarse = (int)env_int("S2M2_HALO_COARSE", t.halo_coarse);
+        t.npf = env_flag("S2M2_CONV_NPF");
+        return t;
+    }();
+    return t;
+}
+
+// ConvChoice -> instantiation: every kernel of this file that conv_select can name, once
+template <typename T>
+static int launch_choice(const ConvChoice& c, const ConvArgs& a, hipStream_t st) {
+#define S2M2_ROW(FAMILY, LAUNCHER, ...) \
+    if (c.is(ConvFamily::FAMILY, __VA_ARGS__)) return LAUNCHER<T, __VA_ARGS__>(a, st)
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 8, 1, 4, 0);        // tile 1
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 8, 1, 4, 0);          // 2
+    S2M2_ROW(igemm, launch_conv, 128, 32, 4, 8, 1, 4, 0);         // 3
+    S2M2_ROW(igemm, launch_conv, 128, 64, 2, 8, 1, 4, 0);         // 4
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 4, 1, 4, 0);        // 5
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 4, 1, 4, 0);          // 6
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 4, 4, 4, 0);          // 16
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 8, 4, 4, 0);          // 17
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 4, 4, 4, 0);        // 18
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 4, 1, 8, 0);        // 20
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 8, 1, 8, 0);        // 21
+    S2M2_ROW(igemm, launch_conv, 64, 128, 2, 4, 1, 8, 0);         // 22
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 4, 4, 8, 0);        // 27
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 8, 1, 4, 1);          // MODE 1: pre-LayerNorm folded in (tiles 2, 3, 6, 20)
+    S2M2_ROW(igemm, launch_conv, 128, 32, 4, 8, 1, 4, 1);
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 4, 1, 4, 1);
+    S2M2_ROW(igemm, launch_conv, 128, 128, 2, 4, 1, 8, 1);
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 8, 1, 4, 2);          // MODE 2: DUALMIX (tiles 2, 6, 20)
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 4, 1, 4, 2);
+    if constexpr (sizeof(T) == 2) S2M2_ROW(igemm, launch_conv, 128, 128, 2, 4, 1, 8, 2);
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 8, 1, 4, 3);          // MODE 3: AvgPool2d(2) in front
+    S2M2_ROW(igemm, launch_conv, 64, 64, 2, 4, 1, 4, 3);
+    S2M2_ROW(igemm2, launch_conv2, 128, 128, 1, 4);               // 7
+    S2M2_ROW(igemm2, launch_conv2, 128, 128, 2, 2);               // 8
+    S2M2_ROW(igemm2, launch_conv2, 128, 128, 2, 3);               // 9
+    S2M2_ROW(igemm2, launch_conv2, 64, 64, 2, 4);                 // 10
+    S2M2_ROW(igemm2, launch_conv2, 64, 64, 1, 4);                 // 11
+    S2M2_ROW(halo, launch_conv_halo, 128, 4, 2, 1);               // 12
+    S2M2_ROW(halo, launch_conv_halo, 64, 4, 2, 1);                // 13
+    S2M2_ROW(halo, launch_conv_halo, 128, 8, 2, 1);               // 19
+    S2M2_ROW(halo, launch_conv_halo, 64, 8, 4, 1);                // 23
+    S2M2_ROW(halo, launch_conv_halo, 64, 8, 4, 4);                // 24
+    S2M2_ROW(halo, launch_conv_halo, 64, 4, 2, 4);                // 25
+    S2M2_ROW(halo, launch_conv_halo, 128, 8, 2, 2);               // 26
+    S2M2_ROW(pw, launch_conv_pw, 128);                            // 14
+    S2M2_ROW(pw, launch_conv_pw, 64);                             // 15
+#undef S2M2_ROW
+    if constexpr (sizeof(T) == 2) {                               // K order 2: p[4] = epilogue operands, a run-time argument of the launcher
+#define S2M2_ROW(...) \
+    if (c.is(ConvFamily::frag, __VA_ARGS__, c.p[4])) return launch_conv_frag<T, __VA_ARGS__>(a, st, c.p[4])
+        S2M2_ROW(128, 128, 2, 32);
+        S2M2_ROW(128, 128, 4, 32);
+        S2M2_ROW(128, 128, 4, 40);
+        S2M2_ROW(192, 192, 2, 32);
+        S2M2_ROW(192, 192, 4, 32);
+        S2M2_ROW(192, 192, 4, 40);
+#undef S2M2_ROW
+    }
+    return set_error("conv2d: no instantiation for the selected kernel (family %d: %d %d %d %d %d %d %d)", (int)c.family, c.p[0], c.p[1], c.p[2],
+                     c.p[3], c.p[4], c.p[5], c.p[6]);
 }
 
 template <typename T>
-static int dispatch_conv(const ConvArgs& a, int tile, hipStream_t st) {
-    const long long M = (long long)a.N * a.Ho * a.Wo;
-    const bool auto_tile = tile == 0;
-    if (a.korder == 2) {                                          // weights packed as a fragment stream: one kernel takes them
-        // 64-pixel blocks where 128-pixel blocks would leave most of the 256 CUs without one (tile: 2 / 4 force the patch height)
-        static const int force_ph = getenv("S2M2_FRAG_PH") ? atoi(getenv("S2M2_FRAG_PH")) : 0;   // A/B switch
-        const long long blocks4 = (long long)a.N * ((a.W + 31) / 32) * ((a.H + 3) / 4) * (a.Cout / 128);
-        // layers with an epilogue operand: always 64-pixel blocks (4 operand pieces per thread instead of 8, 160 registers: three blocks per
-        // CU -- measured -190 us per pair against the v3 tiles, where the 128-pixel variant was +90 us)
-        // (32-pixel blocks, PH = 1, for the 1/8 and 1/16 levels -- twice the blocks again, 8 MFMAs per tap and wave -- measured round 4:
-        // 8.18 / 8.18 / 8.21 ms per pair at thresholds 0 / 320 / 640 blocks, same box, 3 alternating runs: no gain, not kept)
-        const int ph = tile == 2 || tile == 4 ? tile : (force_ph == 2 || force_ph == 4) ? force_ph
-                       : (a.epi != S2M2_EPI_NONE || blocks4 <= 256) ? 2 : 4;
-        // 4x40 patches (160 pixels, 5 MFMA tiles) instead of 4x32 where that saves a partial round of blocks: cost = rounds of the 512
-        // co-resident block slots (2 per CU) times MFMA tiles per block (tile 40 forces it, S2M2_FRAG_PW=32 switches it off)
-        static const int force_pw = getenv("S2M2_FRAG_PW") ? atoi(getenv("S2M2_FRAG_PW")) : 0;         // A/B switch
-        bool wide = false;
-        static const int aux_pw = getenv("S2M2_FRAG_AUX_PW") ? atoi(getenv("S2M2_FRAG_AUX_PW")) : 40;    // A/B switch: 32 = one-operand layers on 64-pixel blocks only
-        const bool one_op = a.epi == S2M2_EPI_ADD || a.epi == S2M2_EPI_MUL;
-        if (one_op && (tile == 40 || (tile == 0 && aux_pw == 40 && force_ph == 0))) {
-            const long long b4 = (long long)a.N * ((a.W + 31) / 32) * ((a.H + 3) / 4) * (a.Cout / 128);
-            const long long b5 = (long long)a.N * ((a.W + 39) / 40) * ((a.H + 3) / 4) * (a.Cout / 128);
-            wide = tile == 40 || (b4 > 256 && ((b5 + 511) / 512) * 5 < ((b4 + 511) / 512) * 4 + 4);
-        } else if (ph == 4 && a.epi == S2M2_EPI_NONE) {
-            const long long blocks5 = (long long)a.N * ((a.W + 39) / 40) * ((a.H + 3) / 4) * (a.Cout / 128);
-            const long long cost4 = ((blocks4 + 511) / 512) * 4, cost5 = ((blocks5 + 511) / 512) * 5;
-            wide = tile == 40 || force_pw == 40 || (tile == 0 && force_pw != 32 && cost5 < cost4);
-        }
-        if constexpr (sizeof(T) == 2) {
-            // Cout a multiple of 192 but not of 128 with Cin a multiple of 192 (the M model's C = 192 layers): blocks of 192 couts (six
-            // waves) on 192-channel chunks (12 k16 steps per tap) -- no padded couts, no half-empty chunk; the weight stream is chunked
-            // accordingly by the packers (same rule: s2m2_conv_frag_chunk).  One block per CU (100 KB halo tile): 256 block slots per round
-            if (s2m2_conv_frag_chunk(a.Cout, a.Cin) == 192) {
-                const long long b4 = (long long)a.N * ((a.W + 31) / 32) * ((a.H + 3) / 4) * (a.Cout / 192);
-                const long long b5 = (long long)a.N * ((a.W + 39) / 40) * ((a.H + 3) / 4) * (a.Cout / 192);
-                // same choices as below with 256 slots per round: 64-pixel blocks for layers with an epilogue operand and for small grids,
-                // 4 x 40 patches where they save a partial round
-                const int ph192 = tile == 2 || tile == 4 ? tile : (a.epi != S2M2_EPI_NONE || b4 <= 128) ? 2 : 4;
-                const bool one = a.epi == S2M2_EPI_ADD || a.epi == S2M2_EPI_MUL;
-                bool wide192 = false;
-                if (one && (tile == 40 || tile == 0)) wide192 = tile == 40 || (b4 > 128 && ((b5 + 255) / 256) * 5 < ((b4 + 255) / 256) * 4 + 4);
-                else if (ph192 == 4 && a.epi == S2M2_EPI_NONE) wide192 = tile == 40 || (tile == 0 && ((b5 + 255) / 256) * 5 < ((b4 + 255) / 256) * 4);
-                if (wide192) return launch_conv_frag<T, 192, 192, 4, 40>(a, st);
-                return ph192 == 2 ? launch_conv_frag<T, 192, 192, 2>(a, st) : launch_conv_frag<T, 192, 192, 4>(a, st);
-            }
-            if (wide) return launch_conv_frag<T, 128, 128, 4, 40>(a, st);
-            return ph == 2 ? launch_conv_frag<T, 128, 128, 2>(a, st) : launch_conv_frag<T, 128, 128, 4>(a, st);
-        } else {
-            return launch_conv_frag<T, 128, 128, 4>(a, st);      // (reports the dtype error)
-        }
-    }
-    if (a.pool2) {                                                // AvgPool2d(2) + 1x1 (the coarse grids): 64x64 tiles, 64- / 128-byte K rows
-        if (tile == 2 || (tile != 6 && a.Cin > 512)) return launch_conv<T, 64, 64, 2, 8, 1, 4, 3>(a, st);
-        return launch_conv<T, 64, 64, 2, 4, 1, 4, 3>(a, st);
-    }
-    static const long long t20_min = getenv("S2M2_T20_MIN") ? atoll(getenv("S2M2_T20_MIN")) : 300;   // tuning only
-    static const int small_tile = getenv("S2M2_SMALL_TILE") ? atoi(getenv("S2M2_SMALL_TILE")) : 0;
-    if (tile == 0) {                                              // measured on MI355X (tools/convbench.py, profiles/r01)
-        const int Ktot = a.KH * a.KW * a.Cin;
-        if (a.KH * a.KW > 1 && a.KH <= 3 && a.KW <= 3 && a.stride == 1 && !a.shuffle2 && !a.korder && a.Cin > 16) {
-            static const bool no8 = getenv("S2M2_CONV_NO_HALO8") != nullptr;    // A/B switch
-            static const long long big_min = getenv("S2M2_HALO_BIG_MIN") ? atoll(getenv("S2M2_HALO_BIG_MIN")) : 30000;   // tuning only
-            static const int narrow = getenv("S2M2_HALO_NARROW") ? atoi(getenv("S2M2_HALO_NARROW")) : 13;
-            static const int coarse = getenv("S2M2_HALO_COARSE") ? atoi(getenv("S2M2_HALO_COARSE")) : 24;
-            tile = (a.Cout >= 128 && !no8) ? (M >= big_min ? 26 : coarse) : narrow;   // 8-wave tiles with 2 / 4 weight tiles in flight
-        }      // spatial kernels: halo tile; 8 waves x 128 couts when there is enough work
-        else if (a.KH * a.KW > 1 && a.Cin <= 16 && a.stride == 1) tile = 6;   // spatial kernel on <= 16 channels: a 128-byte halo chunk would be
-                                                                      // mostly padding; K = taps x channels packed densely instead (8->32 full res: 108 vs 156 us)
-        else if (a.Cout <= 32) tile = 3;                               // 128x32: narrow heads
-        else if (a.Cout >= 128 && ((M + 127) / 128) * ((a.Cout + 127) / 128) >= t20_min) tile = 20;  // 128x128, 64-byte K rows, 8 waves
-        else tile = small_tile ? small_tile : (Ktot <= 512 ? 6 : 2);   // 64x64 with 64- / 128-byte K rows
-        static const bool deep = getenv("S2M2_CONV_NPF") != nullptr;  // A/B switch: 4 K tiles in flight for the v1 tiles
-        if (deep && !a.ln_wsum) tile = tile == 6 ? 16 : tile == 2 ? 17 : tile == 20 ? 27 : tile;
-    }
-    if (a.ln_wsum) {                                              // pre-LN folded in: the v1 tiles the heuristic picks for 1x1 layers
-        switch (tile) {
-            case 2: return launch_conv<T, 64, 64, 2, 8, 1, 4, 1>(a, st);
-            case 3: return launch_conv<T, 128, 32, 4, 8, 1, 4, 1>(a, st);
-            case 6: return launch_conv<T, 64, 64, 2, 4, 1, 4, 1>(a, st);
-            case 20: return launch_conv<T, 128, 128, 2, 4, 1, 8, 1>(a, st);
-            default: return set_error("conv2d: tile %d has no pre-LayerNorm variant (2, 3, 6, 20 do)", tile);
-        }
-    }
-    if (a.epi == S2M2_EPI_DUALMIX) {                              // two GEMMs, one launch: the v1 tiles the heuristic picks for 1x1 layers
-        if (auto_tile) tile = 2;                                  // measured end to end: 64x64 / 128-byte K rows (the 8-wave 128x128 tile needs 168 VGPRs with two accumulator sets: one block per CU)
-        if constexpr (sizeof(T) == 2) {
-            switch (tile) {
-                case 2: return launch_conv<T, 64, 64, 2, 8, 1, 4, 2>(a, st);
-                case 6: return launch_conv<T, 64, 64, 2, 4, 1, 4, 2>(a, st);
-                case 20: return launch_conv<T, 128, 128, 2, 4, 1, 8, 2>(a, st);
-                default: return set_error("conv2d: tile %d has no dual-GEMM variant (2, 6, 20 do)", tile);
-            }
-        } else {
-            switch (tile) {                                       // fp32: 64x64 tiles only (4 staged pieces per thread)
-                case 2: case 20: return launch_conv<T, 64, 64, 2, 8, 1, 4, 2>(a, st);
-                case 6: return launch_conv<T, 64, 64, 2, 4, 1, 4, 2>(a, st);
-                default: return set_error("conv2d: tile %d has no dual-GEMM variant (2, 6, 20 do)", tile);
-            }
-        }
-    }
-    switch (tile) {
-        case 1: return launch_conv<T, 128, 128, 2>(a, st);
-        case 2: return launch_conv<T, 64, 64, 2>(a, st);
-        case 3: return launch_conv<T, 128, 32, 4>(a, st);
-        case 4: return launch_conv<T, 128, 64, 2>(a, st);
-        case 5: return launch_conv<T, 128, 128, 2, 4>(a, st);      // 64-byte K rows: half the LDS, 3 blocks per CU
-        case 6: return launch_conv<T, 64, 64, 2, 4>(a, st);
-        case 7: return launch_conv2<T, 128, 128, 1, 4>(a, st);     // v2 (LDS-direct ring): 64 KB, 3 tiles ahead
-        case 8: return launch_conv2<T, 128, 128, 2, 2>(a, st);     // v2: 128-byte K rows, 1 tile ahead
-        case 9: return launch_conv2<T, 128, 128, 2, 3>(a, st);     // v2: 96 KB, 2 tiles ahead
-        case 10: return launch_conv2<T, 64, 64, 2, 4>(a, st);      // v2: 64x64, 64 KB
-        case 11: return launch_conv2<T, 64, 64, 1, 4>(a, st);      // v2: 64x64, 32 KB
-        case 12: return launch_conv_halo<T, 128>(a, st);           // v3 halo tile, 4x32 pixel patch x 128 couts
-        case 13: return launch_conv_halo<T, 64>(a, st);            // v3 halo tile, x 64 couts
-        case 14: return launch_conv_pw<T, 128>(a, st);             // v4 persistent pointwise, 128 couts per block
-        case 15: return launch_conv_pw<T, 64>(a, st);              // v4 persistent pointwise, 64 couts per block
-        case 16: return launch_conv<T, 64, 64, 2, 4, 4>(a, st);    // 64x64, 64-byte K rows, 4 K tiles in flight
-        case 17: return launch_conv<T, 64, 64, 2, 8, 4>(a, st);    // 64x64, 128-byte K rows, 4 K tiles in flight
-        case 18: return launch_conv<T, 128, 128, 2, 4, 4>(a, st);  // 128x128, 64-byte K rows, 4 K tiles in flight
-        case 19: return launch_conv_halo<T, 128, 8>(a, st);        // v3 halo tile, 128 couts, 8 waves (32 couts per wave)
-        case 20: return launch_conv<T, 128, 128, 2, 4, 1, 8>(a, st);   // 128x128, 64-byte K rows, 8 waves (64 px x 32 couts each)
-        case 21: return launch_conv<T, 128, 128, 2, 8, 1, 8>(a, st);   // 128x128, 128-byte K rows, 8 waves
-        case 22: return launch_conv<T, 64, 128, 2, 4, 1, 8>(a, st);    // 64x128, 64-byte K rows, 8 waves (32 px x 32 couts each)
-        case 23: return launch_conv_halo<T, 64, 8, 4>(a, st);      // v3 halo tile, 64 couts, 8 waves (one patch row x 32 couts each)
-        case 27: return launch_conv<T, 128, 128, 2, 4, 4, 8>(a, st);   // t20 with 4 K tiles in flight
-        case 24: return launch_conv_halo<T, 64, 8, 4, 4>(a, st);   // t23 with 4 weight tiles in flight (short grids)
-        case 25: return launch_conv_halo<T, 64, 4, 2, 4>(a, st);   // t13 with 4 weight tiles in flight
-        case 26: return launch_conv_halo<T, 128, 8, 2, 2>(a, st);  // t19 with 2 weight tiles in flight
-        default: return set_error("conv2d: unknown tile id %d", tile);
-    }
+static int dispatch_conv(ConvArgs& a, int tile, hipStream_t st) {
+    const ConvChoice c = conv_select(a, tile, sizeof(T) == 2, conv_tuning());
+    if (c.family == ConvFamily::error) return set_error("%s", c.error);
+    if (bind_zero_page(a, "conv2d")) return 1;                    // (first device call: every argument check is above)
+    return launch_choice<T>(c, a, st);
 }
 
 }  // namespace s2m2
@@ -1754,12 +1677,7 @@ static int conv2d_impl(const s2m2_conv_desc* d, void* stream) {
     S2M2_REQUIRE(d->korder >= 0 && d->korder <= 2, "conv2d: korder=%d (0, 1 or 2)", d->korder);
     S2M2_REQUIRE(d->korder != 1 || a.Cin % (d->dtype == S2M2_F16 ? 32 : 16) == 0, "conv2d: korder 1 needs Cin=%d to be a multiple of 64 bytes of channels", a.Cin);
     S2M2_REQUIRE(d->korder != 2 || d->dtype == S2M2_F16, "conv2d: korder 2 (fragment stream) is an fp16 layout");
-    a.zero = zero_page();                                         // (first device call: every argument check is above)
-    S2M2_REQUIRE(a.zero, "conv2d: cannot allocate the zero page");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (d->dtype == S2M2_F16) return dispatch_conv<half_t>(a, d->tile, st);
-    if (d->dtype == S2M2_F32) return dispatch_conv<float>(a, d->tile, st);
-    return set_error("conv2d: unsupported dtype %d", d->dtype);
+    return by_dtype(d->dtype, "conv2d", [&](auto t) { return dispatch_conv<decltype(t)>(a, d->tile, static_cast<hipStream_t>(stream)); });
 }
 extern "C" int s2m2_conv2d(const s2m2_conv_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_conv_desc>("s2m2_conv2d", &conv2d_impl, d, stream);

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
 
@@ -430,36 +431,28 @@ __global__ __launch_bounds__(CFG::NT) void conv_px_kernel(NarrowArgs p, int tile
 template <int CH, int NTL, int MT, int NW = 4, bool HEAD = false>
 static int launch_px(const NarrowArgs& a, hipStream_t st) {
     using CFG = PxCfg<CH, NTL, MT, NW>;
-    auto kern = conv_px_kernel<CFG, HEAD>;
-    static size_t lds_granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "conv_narrow")) return 1;
     const int tx = (a.Wo + CFG::PW - 1) / CFG::PW, ty = (a.Ho + CFG::PH - 1) / CFG::PH;
     const long long nblk = (long long)a.N * tx * ty;
     if (nblk >= (1LL << 31)) return set_error("conv_narrow: %lld blocks", nblk);
     const int gy = (a.Cout + CFG::WN - 1) / CFG::WN;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)gy), dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
-    return check_launch("conv_narrow");
+    return launch<conv_px_kernel<CFG, HEAD>>("conv_narrow", dim3((unsigned)nblk, (unsigned)gy), dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty);
 }
 
 template <int KH, int KW, int S, int CIN, int MT, int NTL, int NWN>
 static int launch_narrow(const NarrowArgs& a, hipStream_t st) {
     using CFG = NarrowCfg<KH, KW, S, CIN, MT, NTL, NWN>;
-    auto kern = conv_narrow_kernel<CFG>;
-    static size_t lds_granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "conv_narrow")) return 1;
     const int tx = (a.Wo + CFG::PW - 1) / CFG::PW, ty = (a.Ho + CFG::PH - 1) / CFG::PH;
     const long long nblk = (long long)a.N * tx * ty;
     if (nblk >= (1LL << 31)) return set_error("conv_narrow: %lld blocks", nblk);
     // cout groups per block: all of them on a grid that fills the chip by itself, one where every CU would get less than ~4 blocks
     const int ngroups = (a.Cout + CFG::NWN * CFG::WN - 1) / (CFG::NWN * CFG::WN);
     const int gpb = nblk >= 1024 ? ngroups : 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)((ngroups + gpb - 1) / gpb)), dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty, gpb);
-    return check_launch("conv_narrow");
+    return launch<conv_narrow_kernel<CFG>>("conv_narrow", dim3((unsigned)nblk, (unsigned)((ngroups + gpb - 1) / gpb)), dim3(CFG::NT), CFG::LDS_BYTES, st, a, tx, ty, gpb);
 }
 
 // 8 output rows per block where that still gives every CU several blocks, else 4
 static bool narrow_tall(const NarrowArgs& a) {
-    static const int force_mt = getenv("S2M2_NARROW_MT") ? atoi(getenv("S2M2_NARROW_MT")) : 0;       // A/B switch: 1 = 4-row blocks, 2 = 8-row blocks
+    static const int force_mt = (int)env_int("S2M2_NARROW_MT", 0);       // A/B switch: 1 = 4-row blocks, 2 = 8-row blocks
     const long long blocks8 = (long long)a.N * ((a.Wo + 31) / 32) * ((a.Ho + 7) / 8);
     return force_mt ? force_mt == 2 : blocks8 >= 1024;
 }
@@ -503,8 +496,7 @@ static int conv_narrow_impl(const s2m2_narrow_desc* d, void* stream) {
     a.Ho = (d->H + d->stride - 1) / d->stride; a.Wo = (d->W + d->stride - 1) / d->stride;
     a.w = d->weight_frag; a.bias = d->bias; a.out = d->out; a.out_stride = d->out_stride; a.Cout = d->Cout; a.act = d->act;
     a.w2 = d->head_frag; a.bias2 = d->head_bias; a.Cout2 = d->head_cout;
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "conv_narrow: cannot allocate the zero page");
+    if (bind_zero_page(a, "conv_narrow")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool tall = narrow_tall(a);
     if (d->Cin == 48 && a.Cout2) return tall ? launch_px<48, 2, 2, 4, true>(a, st) : launch_px<48, 2, 1, 4, true>(a, st);
@@ -518,7 +510,7 @@ static int conv_narrow_impl(const s2m2_narrow_desc* d, void* stream) {
     if (d->Cin >= 128) return launch_px<64, 1, 2, 2>(a, st);
     if (d->Cin == 8) return tall ? launch_narrow<3, 3, 1, 8, 2, 1, 1>(a, st) : launch_narrow<3, 3, 1, 8, 1, 1, 1>(a, st);
     // 5x5: wave pairs split the two cout tiles of a group and share 2 / 4 output rows (A/B switch S2M2_NARROW_NWN=1: every wave both tiles)
-    static const bool split = !(getenv("S2M2_NARROW_NWN") && atoi(getenv("S2M2_NARROW_NWN")) == 1);
+    static const bool split = env_int("S2M2_NARROW_NWN", 0) != 1;
     if (split) return tall ? launch_narrow<5, 5, 2, 16, 4, 1, 2>(a, st) : launch_narrow<5, 5, 2, 16, 2, 1, 2>(a, st);
     return tall ? launch_narrow<5, 5, 2, 16, 2, 2, 1>(a, st) : launch_narrow<5, 5, 2, 16, 1, 2, 1>(a, st);
 }

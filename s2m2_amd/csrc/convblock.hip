@@ -17,6 +17,7 @@
 // Accumulation order = K5 v5's (chunk, tap, channel) and K9's (channel): bit-identical to the three launches (tests/test_hip_convblock.py).
 // fp16, C = 128 (PH = 2 / 4) and C = 256 (PH = 2).
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
 #include <stdlib.h>
@@ -290,11 +291,7 @@ static int launch_cb(const CbArgs& a0, hipStream_t st) {
     CbArgs a = a0;
     a.tiles_x = (a.W + 31) / 32;
     a.tiles_y = (a.H + PH - 1) / PH;
-    auto kern = conv_block_kernel<CFG>;
-    static size_t granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, granted, "conv_block")) return 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * a.tiles_x * a.tiles_y)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
-    return check_launch("conv_block");
+    return launch<conv_block_kernel<CFG>>("conv_block", dim3((unsigned)(a.N * a.tiles_x * a.tiles_y)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
 }
 
 }  // namespace s2m2
@@ -317,8 +314,7 @@ static int conv_block_impl(const s2m2_convblock_desc* d, void* stream) {
     a.w1 = static_cast<const raw16_t*>(d->w_conv0); a.w2 = static_cast<const raw16_t*>(d->w_conv2);
     a.wa = static_cast<const raw16_t*>(d->w_1x0); a.wb = static_cast<const raw16_t*>(d->w_1x2);
     a.b1 = d->b_conv0; a.b2 = d->b_conv2; a.ba = d->b_1x0; a.bb = d->b_1x2;
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "conv_block: cannot allocate the zero page");
+    if (bind_zero_page(a, "conv_block")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->C == 256) return launch_cb<256, 2>(a, st);
     // C = 128: 4-row patches while they give every CU about a block, 2-row patches on the smaller grids

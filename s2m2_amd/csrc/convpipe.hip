@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 #include "epilogue.h"
 
 namespace s2m2 {
@@ -212,12 +213,8 @@ static int launch_pipe(PipeArgs a, int Cout, hipStream_t st) {
     a.tiles_x = (a.W + PW - 1) / PW;
     a.tiles_y = (a.H + 3) / 4;
     a.npatch = a.N * a.tiles_x * a.tiles_y;
-    auto kern = conv_pipe_kernel<CFG, ACT, ADD>;
-    static size_t granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(kern), 2 * CFG::BUF_BYTES, granted, "conv_pipe")) return 1;
     const int grid = a.npatch < 512 ? a.npatch : 512;
-    hipLaunchKernelGGL(kern, dim3(grid, Cout / 128), dim3(320), 2 * CFG::BUF_BYTES, st, a);
-    return check_launch("conv_pipe");
+    return launch<conv_pipe_kernel<CFG, ACT, ADD>>("conv_pipe", dim3(grid, Cout / 128), dim3(320), 2 * CFG::BUF_BYTES, st, a);
 }
 
 }  // namespace s2m2
@@ -235,8 +232,7 @@ extern "C" int s2m2_debug_conv_pipe(const void* x, long long x_stride, void* out
     a.x = static_cast<const half_t*>(x); a.xs = x_stride; a.out = static_cast<half_t*>(out); a.os = out_stride;
     a.aux = static_cast<const half_t*>(aux); a.as = aux_stride;
     a.w = static_cast<const raw16_t*>(w_frag64); a.bias = bias; a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.act = act;
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "conv_pipe: cannot allocate the zero page");
+    if (bind_zero_page(a, "conv_pipe")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define S2M2_PIPE(PWV)                                                                                                   \
     if (aux) {                                                                                                           \

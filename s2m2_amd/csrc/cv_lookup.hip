@@ -7,6 +7,7 @@
 // so the effective coordinate is off by ~1 ulp and a vanishing weight can land on the neighbouring row;
 // that arithmetic is reproduced here with contraction disabled.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "cv_lookup.h"
 
@@ -39,9 +40,8 @@ template <typename TI, typename TO>
 static int launch_lookup(const void* cv, const float* disp, void* c1, void* c2, int B, int h, int w, int radius, long long bs,
                          long long ps, long long ts, int pitch, hipStream_t st) {
     const int per_row = w * 2 * (2 * radius + 1);
-    hipLaunchKernelGGL((cv_lookup_kernel<TI, TO>), dim3((per_row + 255) / 256, B * h), dim3(256), 0, st, static_cast<const TI*>(cv), disp,
-                       static_cast<TO*>(c1), static_cast<TO*>(c2), B, h, w, radius, bs, ps, ts, pitch);
-    return check_launch("cv_lookup");
+    return launch<cv_lookup_kernel<TI, TO>>("cv_lookup", dim3((per_row + 255) / 256, B * h), dim3(256), 0, st, static_cast<const TI*>(cv), disp,
+                                            static_cast<TO*>(c1), static_cast<TO*>(c2), B, h, w, radius, bs, ps, ts, pitch);
 }
 
 }  // namespace s2m2
@@ -56,11 +56,13 @@ static int cv_lookup_impl(const void* cv, const float* disp, void* corr1, void* 
     if (cv_pitch == 0) cv_pitch = w;
     S2M2_REQUIRE(cv_pitch >= w, "cv_lookup: cv_pitch=%d must be at least w=%d", cv_pitch, w);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (cv_dtype == S2M2_F16 && out_dtype == S2M2_F16) return launch_lookup<half_t, half_t>(cv, disp, corr1, corr2, B, h, w, radius, batch_stride, pix_stride, tap_stride, cv_pitch, st);
-    if (cv_dtype == S2M2_F16 && out_dtype == S2M2_F32) return launch_lookup<half_t, float>(cv, disp, corr1, corr2, B, h, w, radius, batch_stride, pix_stride, tap_stride, cv_pitch, st);
-    if (cv_dtype == S2M2_F32 && out_dtype == S2M2_F32) return launch_lookup<float, float>(cv, disp, corr1, corr2, B, h, w, radius, batch_stride, pix_stride, tap_stride, cv_pitch, st);
-    if (cv_dtype == S2M2_F32 && out_dtype == S2M2_F16) return launch_lookup<float, half_t>(cv, disp, corr1, corr2, B, h, w, radius, batch_stride, pix_stride, tap_stride, cv_pitch, st);
-    return set_error("cv_lookup: unsupported dtypes cv=%d out=%d", cv_dtype, out_dtype);
+    const auto known = [](int dt) { return dt == S2M2_F16 || dt == S2M2_F32; };
+    if (!known(cv_dtype) || !known(out_dtype)) return set_error("cv_lookup: unsupported dtypes cv=%d out=%d", cv_dtype, out_dtype);
+    return by_dtype(cv_dtype, "cv_lookup", [&](auto ti) {
+        return by_dtype(out_dtype, "cv_lookup", [&](auto to) {
+            return launch_lookup<decltype(ti), decltype(to)>(cv, disp, corr1, corr2, B, h, w, radius, batch_stride, pix_stride, tap_stride, cv_pitch, st);
+        });
+    });
 }
 extern "C" int s2m2_cv_lookup(const void* cv, const float* disp, void* corr1, void* corr2, int B, int h, int w, int radius,
                               int cv_dtype, int out_dtype, long long batch_stride, long long pix_stride, long long tap_stride,

@@ -15,6 +15,7 @@
 //   * MFMA roles, staging and rounding points as in K5 / K9: h, g, the mix and the fusion term are each rounded to the I/O dtype
 //     where the separate launches stored them.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
 #include <stdlib.h>
@@ -421,21 +422,13 @@ __global__ __launch_bounds__(CFG::NT) void feature_fusion_direct_kernel(FusionAr
 template <int C, int BM, int NW, int D>
 static int launch_fusion_direct(const FusionArgs& a, hipStream_t st) {
     using CFG = FusionDirectCfg<C, BM, NW, D>;
-    auto kern = feature_fusion_direct_kernel<CFG>;
-    static size_t lds_granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "feature_fusion")) return 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.rows + BM - 1) / BM)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
-    return check_launch("feature_fusion");
+    return launch<feature_fusion_direct_kernel<CFG>>("feature_fusion", dim3((unsigned)((a.rows + BM - 1) / BM)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
 }
 
 template <typename T, int C, int BM, int NW, int WP = 4>
 static int launch_fusion(const FusionArgs& a, hipStream_t st) {
     using CFG = FusionCfg<T, C, BM, NW, WP>;
-    auto kern = feature_fusion_kernel<CFG, T>;
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "feature_fusion")) return 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.rows + BM - 1) / BM)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
-    return check_launch("feature_fusion");
+    return launch<feature_fusion_kernel<CFG, T>>("feature_fusion", dim3((unsigned)((a.rows + BM - 1) / BM)), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
 }
 
 }  // namespace s2m2
@@ -446,7 +439,7 @@ extern "C" int s2m2_feature_fusion_supported(int C, int dtype) {
 
 // (C = 512, r06: the L model's 1/16 level, ten fusions per forward that ran as two K5 launches each; 16 waves per block, ring of 6 fragments: 8 spill)
 extern "C" int s2m2_feature_fusion_frag_supported(int C, int dtype) {
-    static const bool no512 = getenv("S2M2_FUSION_FRAG512") != nullptr && atoi(getenv("S2M2_FUSION_FRAG512")) == 0;        // A/B switch
+    static const bool no512 = s2m2::env_is0("S2M2_FUSION_FRAG512");        // A/B switch
     return dtype == S2M2_F16 && (C == 128 || C == 192 || C == 256 || C == 384 || (C == 512 && !no512));
 }
 
@@ -465,11 +458,10 @@ static int feature_fusion_frag_impl(const void* z0, const void* z1, void* out, l
     a.z0 = z0; a.z1 = z1; a.out = out; a.z0_stride = z0_stride; a.z1_stride = z1_stride; a.out_stride = out_stride; a.rows = rows;
     a.w1 = w_stream; a.w2 = nullptr; a.b1 = b1; a.bg = bg; a.bf = bf;
     a.up_h = z1_coarse_h; a.up_w = z1_coarse_w;
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "feature_fusion_frag: cannot allocate the zero page");
+    if (bind_zero_page(a, "feature_fusion_frag")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // 32-row tiles while one round of them fits the chip, else 64-row tiles (half the weight traffic per row); S2M2_FUSION_DIRECT_BM forces one
-    static const int force_bm = getenv("S2M2_FUSION_DIRECT_BM") ? atoi(getenv("S2M2_FUSION_DIRECT_BM")) : 0;
+    static const int force_bm = (int)env_int("S2M2_FUSION_DIRECT_BM", 0);
     const bool tall = force_bm ? force_bm == 64 : rows > (C == 128 ? 24576 : C == 192 ? 16384 : 8192);
     if (C == 128) return tall ? launch_fusion_direct<128, 64, 4, 12>(a, st) : launch_fusion_direct<128, 32, 4, 24>(a, st);
     if (C == 192) return tall ? launch_fusion_direct<192, 64, 6, 12>(a, st) : launch_fusion_direct<192, 32, 6, 24>(a, st);
@@ -499,13 +491,12 @@ static int feature_fusion_impl(const void* z0, const void* z1, void* out, long l
     a.up_h = z1_coarse_h; a.up_w = z1_coarse_w;
     S2M2_REQUIRE((z1_coarse_h == 0 && z1_coarse_w == 0) || (z1_coarse_h > 0 && z1_coarse_w > 0 && rows % (4LL * z1_coarse_h * z1_coarse_w) == 0),
                  "feature_fusion: rows=%lld is not a whole number of (2*%d) x (2*%d) images", rows, z1_coarse_h, z1_coarse_w);
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "feature_fusion: cannot allocate the zero page");
+    if (bind_zero_page(a, "feature_fusion")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // measured end to end (same-box A/B): 32-row tiles (the 64-row tile of C = 128 needs 234 VGPRs for its three accumulator sets
     // and runs one block per CU); 128-byte K chunks (half the barriers of 64-byte chunks, +1.3 %) wherever the tile still fits
-    static const bool narrow = getenv("S2M2_FUSION_CHUNK64") != nullptr;   // A/B switch
-    static const int big = getenv("S2M2_FUSION_BM") ? atoi(getenv("S2M2_FUSION_BM")) : 0;   // experiment: 64- / 128-row tiles at C = 128
+    static const bool narrow = env_flag("S2M2_FUSION_CHUNK64");   // A/B switch
+    static const int big = (int)env_int("S2M2_FUSION_BM", 0);   // experiment: 64- / 128-row tiles at C = 128
     if (dtype == S2M2_F16) {
         if (C == 128 && big == 128 && rows >= 32768) return launch_fusion<half_t, 128, 128, 4, 8>(a, st);
         if (C == 128 && big == 64 && rows >= 32768) return launch_fusion<half_t, 128, 64, 4, 8>(a, st);

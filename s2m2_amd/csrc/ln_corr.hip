@@ -19,6 +19,7 @@
 // Every feature token is read from HBM once and normalised once per strip; the cost volume is written once.
 // Algorithmic traffic per pair: 2*h*w*C*sizeof(T) read + h*w*w*sizeof(TO) written.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include <hip/hip_ext.h>
 #include <stdlib.h>
@@ -459,6 +460,8 @@ struct PrenormOf<LnCorrCfg<T, TO, C, NWCAP, RIF, EB, TPW, false>> { using type =
 template <typename CFG, typename T, typename TO>
 static int launch_ln_corr(const void* feat, const float* g, const float* bta, void* cv, int B, int h, int w, const K1Opt& o, hipStream_t st) {
     auto kern = ln_corr_kernel<CFG, T, TO>;
+    // (this launch stays outside launch.h's helper: it reserves the LDS of the widest block once, whatever width it launches, and its timed form
+    // carries two events on the dispatch)
     static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
     if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::lds_bytes(CFG::NWMAX), lds_granted, "ln_corr")) return 1;
     const int tiles = (w + 31) / 32;                     // 32-pixel row tiles = waves needed per image row
@@ -474,7 +477,7 @@ static int launch_ln_corr(const void* feat, const float* g, const float* bta, vo
     // 19.2 -> 16.8 us back to back and 19.7-20.7 -> 17.7 us inside the forward against the write-back default of rounds 1-3; S2M2_K1_NT=0..4 A/B
     // (only for volume rows on 128-byte lines: a write-through store of a PARTIAL line is a read-modify-write at the memory side -- dense 608-byte
     // rows measured 25.0 us with sc1 against 21.8 with plain stores, profiles/r04/kbench.txt; the engine always allocates aligned rows)
-    static const int k1_env = getenv("S2M2_K1_NT") ? atoi(getenv("S2M2_K1_NT")) : -1;
+    static const int k1_env = (int)env_int("S2M2_K1_NT", -1);
     const int k1_flags = k1_env >= 0 ? k1_env : ((pitch * (int)sizeof(TO)) % 128 == 0 ? 2 : 0);
     if (o.ev_start || o.ev_stop)
         hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(nw * 64), CFG::lds_bytes(nw), st, o.ev_start, o.ev_stop, 0,

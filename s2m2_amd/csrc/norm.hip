@@ -8,6 +8,7 @@
 //    atomicAdd pair per block and group), then the normalise+affine sweep.
 // Both compute in fp32 regardless of the I/O dtype.
 #include "common.h"
+#include "launch.h"
 #include <stdlib.h>
 #include "plan.h"
 
@@ -61,9 +62,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T* __restrict
 template <typename T, int MAXP>
 static int launch_ln(const void* x, void* y, long long rows, int C, long long xs, long long ys, hipStream_t st) {
     const long long threads = rows * 16;
-    hipLaunchKernelGGL((layernorm_rows_kernel<T, MAXP>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
-                       static_cast<const T*>(x), static_cast<T*>(y), rows, C, xs, ys);
-    return check_launch("layernorm");
+    return launch<layernorm_rows_kernel<T, MAXP>>("layernorm", dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, static_cast<const T*>(x),
+                                                  static_cast<T*>(y), rows, C, xs, ys);
 }
 
 template <typename T>
@@ -188,16 +188,14 @@ static int run_groupnorm(const void* x, void* y, const float* gamma, const float
     constexpr int VEC = 16 / sizeof(T);
     const int P = C / VEC;
     if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * N * G * kGnReplicas, st) != hipSuccess) return set_error("groupnorm: memset failed");
-    static const int ppb_env = getenv("S2M2_GN_PPB") ? atoi(getenv("S2M2_GN_PPB")) : 0;      // tuning only
+    static const int ppb_env = (int)env_int("S2M2_GN_PPB", 0);      // tuning only
     const int ppb = ppb_env > 0 ? ppb_env : 512;                   // pixels per block of the statistics pass
     dim3 g1((unsigned)((HW + ppb - 1) / ppb), N);
-    hipLaunchKernelGGL((groupnorm_stats_kernel<T>), g1, dim3(256), 0, st, static_cast<const T*>(x), ws, HW, C, G, ppb);
-    if (int rc = check_launch("groupnorm_stats")) return rc;
+    if (int rc = launch<groupnorm_stats_kernel<T>>("groupnorm_stats", g1, dim3(256), 0, st, static_cast<const T*>(x), ws, HW, C, G, ppb)) return rc;
     long long blocks = (HW * P + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((groupnorm_apply_kernel<T>), dim3((unsigned)blocks, N), dim3(256), 0, st, static_cast<const T*>(x),
-                       static_cast<T*>(y), ws, gamma, beta, HW, C, G, eps);
-    return check_launch("groupnorm_apply");
+    return launch<groupnorm_apply_kernel<T>>("groupnorm_apply", dim3((unsigned)blocks, N), dim3(256), 0, st, static_cast<const T*>(x), static_cast<T*>(y), ws,
+                                             gamma, beta, HW, C, G, eps);
 }
 
 }  // namespace s2m2
@@ -209,9 +207,7 @@ static int layernorm_impl(const void* x, void* y, long long rows, int C, long lo
     S2M2_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && x_stride % 8 == 0 && y_stride % 8 == 0,
                  "layernorm: rows=%lld C=%d strides %lld/%lld (C and strides must be multiples of 8)", rows, C, x_stride, y_stride);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16) return dispatch_ln<half_t>(x, y, rows, C, x_stride, y_stride, st);
-    if (dtype == S2M2_F32) return dispatch_ln<float>(x, y, rows, C, x_stride, y_stride, st);
-    return set_error("layernorm: unsupported dtype %d", dtype);
+    return by_dtype(dtype, "layernorm", [&](auto t) { return dispatch_ln<decltype(t)>(x, y, rows, C, x_stride, y_stride, st); });
 }
 extern "C" int s2m2_layernorm(const void* x, void* y, long long rows, int C, long long x_stride, long long y_stride, int dtype,
                               void* stream) {
@@ -230,9 +226,7 @@ static int groupnorm_nhwc_impl(const void* x, void* y, const float* gamma, const
                  "groupnorm: N=%d HW=%lld C=%d G=%d (C/G must be a multiple of %d, G <= 32)", N, HW, C, G, vec);
     S2M2_REQUIRE(C / vec <= 256, "groupnorm: C=%d too wide", C);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16) return run_groupnorm<half_t>(x, y, gamma, beta, static_cast<double*>(workspace), N, HW, C, G, eps, st);
-    if (dtype == S2M2_F32) return run_groupnorm<float>(x, y, gamma, beta, static_cast<double*>(workspace), N, HW, C, G, eps, st);
-    return set_error("groupnorm: unsupported dtype %d", dtype);
+    return by_dtype(dtype, "groupnorm", [&](auto t) { return run_groupnorm<decltype(t)>(x, y, gamma, beta, static_cast<double*>(workspace), N, HW, C, G, eps, st); });
 }
 extern "C" int s2m2_groupnorm_nhwc(const void* x, void* y, const float* gamma, const float* beta, void* workspace, int N,
                                    long long HW, int C, int G, float eps, int dtype, void* stream) {

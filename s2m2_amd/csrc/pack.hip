@@ -9,6 +9,7 @@
 // row is past the source); the column map of an order is built on the host.  Packing is a one-time, synchronous set-up step (it allocates and
 // frees its map): not for use under stream capture.
 #include "common.h"
+#include "launch.h"
 #include <vector>
 
 namespace s2m2 {
@@ -47,9 +48,8 @@ static int run_plan(const PackPlan& p, half_t* dst, hipStream_t st) {
     if (hipMemcpy(dmap, p.colmap.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) rc = set_error("pack_frag: column map upload failed");
     if (!rc) {
         const long long total = (long long)p.ntiles * p.nsteps * 64;
-        hipLaunchKernelGGL(frag_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.src, p.src_ld, p.src_rows, dmap, dst,
-                           p.tile_stride, p.step0, p.ntiles, p.nsteps);
-        rc = check_launch("pack_frag");
+        rc = launch<frag_pack_kernel>("pack_frag", dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.src, p.src_ld, p.src_rows, dmap, dst, p.tile_stride,
+                                      p.step0, p.ntiles, p.nsteps);
         if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = set_error("pack_frag: kernel failed");
     }
     (void)hipFree(dmap);

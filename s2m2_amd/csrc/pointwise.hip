@@ -7,6 +7,7 @@
 //   unary          tanh of the context features (hidden state init)                 (s2m2.py:166)
 // All maps are (B,h,w) fp32; "small" side inputs are (B,h,w,8) NHWC in the activation dtype with unused channels zero.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
 
@@ -125,17 +126,13 @@ static int image_prep_impl(const void* img0, const void* img1, void* x8, int B, 
     S2M2_REQUIRE(img0 && img1 && x8 && B > 0 && H > 0 && W > 0 && 2LL * B * H * W < (1LL << 31), "image_prep: bad arguments (at most 2^31 pixels per launch)");
     const long long HW = (long long)H * W, n = 2LL * B * HW;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // img_dtype: S2M2_F32 / S2M2_F16 / 2 = uint8
-    #define S2M2_IP(TI, T) hipLaunchKernelGGL((image_prep_kernel<TI, T>), grid1(n), dim3(256), 0, st, (const TI*)img0, (const TI*)img1, (T*)x8, B, HW)
-    if (dtype == S2M2_F16) {
-        if (img_dtype == S2M2_F32) S2M2_IP(float, half_t); else if (img_dtype == S2M2_F16) S2M2_IP(half_t, half_t);
-        else if (img_dtype == 2) S2M2_IP(unsigned char, half_t); else return set_error("image_prep: unsupported image dtype %d", img_dtype);
-    } else if (dtype == S2M2_F32) {
-        if (img_dtype == S2M2_F32) S2M2_IP(float, float); else if (img_dtype == S2M2_F16) S2M2_IP(half_t, float);
-        else if (img_dtype == 2) S2M2_IP(unsigned char, float); else return set_error("image_prep: unsupported image dtype %d", img_dtype);
-    } else return set_error("image_prep: unsupported dtype %d", dtype);
-    #undef S2M2_IP
-    return check_launch("image_prep");
+    return by_dtype(dtype, "image_prep", [&](auto t) {
+        return by_image_dtype(img_dtype, "image_prep", [&](auto ti) {
+            using T = decltype(t);
+            using TI = decltype(ti);
+            return launch<image_prep_kernel<TI, T>>("image_prep", grid1(n), dim3(256), 0, st, (const TI*)img0, (const TI*)img1, (T*)x8, B, HW);
+        });
+    });
 }
 extern "C" int s2m2_image_prep(const void* img0, const void* img1, void* x8, int B, int H, int W, int img_dtype, int dtype, void* stream) {
     return s2m2::plan_dispatch("s2m2_image_prep", &image_prep_impl, stream, img0, img1, x8, B, H, W, img_dtype, dtype);
@@ -147,10 +144,10 @@ static int refine_prep_impl(const float* disp, const float* conf, const float* o
     using namespace s2m2;
     S2M2_REQUIRE(disp && conf && small8 && npix > 0 && (mode == 0 || (mode == 1 && occ)), "refine_prep: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16) hipLaunchKernelGGL((refine_prep_kernel<half_t>), grid1(npix), dim3(256), 0, st, disp, conf, occ, (half_t*)small8, npix, mode);
-    else if (dtype == S2M2_F32) hipLaunchKernelGGL((refine_prep_kernel<float>), grid1(npix), dim3(256), 0, st, disp, conf, occ, (float*)small8, npix, mode);
-    else return set_error("refine_prep: unsupported dtype %d", dtype);
-    return check_launch("refine_prep");
+    return by_dtype(dtype, "refine_prep", [&](auto t) {
+        using T = decltype(t);
+        return launch<refine_prep_kernel<T>>("refine_prep", grid1(npix), dim3(256), 0, st, disp, conf, occ, (T*)small8, npix, mode);
+    });
 }
 extern "C" int s2m2_refine_prep(const float* disp, const float* conf, const float* occ, void* small8, long long npix, int mode, int dtype,
                                 void* stream) {
@@ -163,10 +160,10 @@ static int global_update_impl(const void* upd, int upd_stride, const float* disp
     using namespace s2m2;
     S2M2_REQUIRE(upd && disp && conf && out && npix > 0 && upd_stride > 0, "global_update: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16) hipLaunchKernelGGL((global_update_kernel<half_t>), grid1(npix), dim3(256), 0, st, (const half_t*)upd, upd_stride, disp, conf, out, npix, clamp0);
-    else if (dtype == S2M2_F32) hipLaunchKernelGGL((global_update_kernel<float>), grid1(npix), dim3(256), 0, st, (const float*)upd, upd_stride, disp, conf, out, npix, clamp0);
-    else return set_error("global_update: unsupported dtype %d", dtype);
-    return check_launch("global_update");
+    return by_dtype(dtype, "global_update", [&](auto t) {
+        using T = decltype(t);
+        return launch<global_update_kernel<T>>("global_update", grid1(npix), dim3(256), 0, st, (const T*)upd, upd_stride, disp, conf, out, npix, clamp0);
+    });
 }
 extern "C" int s2m2_global_update(const void* upd, int upd_stride, const float* disp, const float* conf, float* out, long long npix,
                                   int clamp0, int dtype, void* stream) {
@@ -182,14 +179,11 @@ static int refine_update_to_impl(const void* dco, int dco_stride, const float* d
                  "refine_update: bad arguments");
     S2M2_REQUIRE(npix < (1LL << 31), "refine_update: 2^31 or more pixels (the column index is decoded in 32 bits)");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16)
-        hipLaunchKernelGGL((refine_update_kernel<half_t>), grid1(npix), dim3(256), 0, st, (const half_t*)dco, dco_stride, disp, conf, occ,
-                           disp_out, conf_out, occ_out, (half_t*)small8_next, npix, w, use_positivity);
-    else if (dtype == S2M2_F32)
-        hipLaunchKernelGGL((refine_update_kernel<float>), grid1(npix), dim3(256), 0, st, (const float*)dco, dco_stride, disp, conf, occ,
-                           disp_out, conf_out, occ_out, (float*)small8_next, npix, w, use_positivity);
-    else return set_error("refine_update: unsupported dtype %d", dtype);
-    return check_launch("refine_update");
+    return by_dtype(dtype, "refine_update", [&](auto t) {
+        using T = decltype(t);
+        return launch<refine_update_kernel<T>>("refine_update", grid1(npix), dim3(256), 0, st, (const T*)dco, dco_stride, disp, conf, occ, disp_out, conf_out,
+                                               occ_out, (T*)small8_next, npix, w, use_positivity);
+    });
 }
 extern "C" int s2m2_refine_update_to(const void* dco, int dco_stride, const float* disp, const float* conf, const float* occ,
                                      float* disp_out, float* conf_out, float* occ_out, void* small8_next, long long npix, int w,
@@ -291,10 +285,10 @@ static int stem_mlp_impl(const void* x8, const float* w0, const float* b0, const
     S2M2_REQUIRE(x8 && w0 && b0 && w1 && b1 && out && npix > 0, "stem_mlp: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid = grid1((npix + 1) / 2);                                      // two pixels per thread
-    if (dtype == S2M2_F16) hipLaunchKernelGGL((stem_mlp_kernel<half_t>), grid, dim3(256), 0, st, (const half_t*)x8, w0, b0, w1, b1, (half_t*)out, npix);
-    else if (dtype == S2M2_F32) hipLaunchKernelGGL((stem_mlp_kernel<float>), grid, dim3(256), 0, st, (const float*)x8, w0, b0, w1, b1, (float*)out, npix);
-    else return set_error("stem_mlp: unsupported dtype %d", dtype);
-    return check_launch("stem_mlp");
+    return by_dtype(dtype, "stem_mlp", [&](auto t) {
+        using T = decltype(t);
+        return launch<stem_mlp_kernel<T>>("stem_mlp", grid, dim3(256), 0, st, (const T*)x8, w0, b0, w1, b1, (T*)out, npix);
+    });
 }
 extern "C" int s2m2_stem_mlp(const void* x8, const float* w0, const float* b0, const float* w1, const float* b1, void* out, long long npix,
                              int dtype, void* stream) {
@@ -306,10 +300,11 @@ static int tanh_impl(const void* x, void* y, long long n, int dtype, void* strea
     using namespace s2m2;
     S2M2_REQUIRE(x && y && n > 0 && n % 8 == 0, "tanh: bad arguments (n must be a multiple of 8)");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16) hipLaunchKernelGGL((tanh_kernel<half_t>), grid1(n / 8), dim3(256), 0, st, (const half_t*)x, (half_t*)y, n / 8);
-    else if (dtype == S2M2_F32) hipLaunchKernelGGL((tanh_kernel<float>), grid1(n / 4), dim3(256), 0, st, (const float*)x, (float*)y, n / 4);
-    else return set_error("tanh: unsupported dtype %d", dtype);
-    return check_launch("tanh");
+    return by_dtype(dtype, "tanh", [&](auto t) {
+        using T = decltype(t);
+        const long long nvec = n / DT<T>::vec;
+        return launch<tanh_kernel<T>>("tanh", grid1(nvec), dim3(256), 0, st, (const T*)x, (T*)y, nvec);
+    });
 }
 extern "C" int s2m2_tanh(const void* x, void* y, long long n, int dtype, void* stream) {
     return s2m2::plan_dispatch("s2m2_tanh", &tanh_impl, stream, x, y, n, dtype);
@@ -380,15 +375,11 @@ static int image_pad_impl(const void* img, float* pooled, float* out, int B, int
     const int BC = B * C;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long bins = (long long)BC * Ho * Wo, pix = (long long)BC * Hn * Wn;
-    #define S2M2_PAD(TI) do { \
-        hipLaunchKernelGGL((pad_pool_kernel<TI>), grid1(bins * 64), dim3(256), 0, st, (const TI*)img, pooled, BC, H, W, Hn, Wn, Ho, Wo, hs, ws); \
-        hipLaunchKernelGGL((pad_fill_kernel<TI>), grid1(pix), dim3(256), 0, st, (const TI*)img, pooled, out, BC, H, W, Hn, Wn, Ho, Wo, hs, ws); } while (0)
-    if (img_dtype == S2M2_F32) S2M2_PAD(float);
-    else if (img_dtype == S2M2_F16) S2M2_PAD(half_t);
-    else if (img_dtype == 2) S2M2_PAD(unsigned char);
-    else return set_error("image_pad: unsupported image dtype %d", img_dtype);
-    #undef S2M2_PAD
-    return check_launch("image_pad");
+    return by_image_dtype(img_dtype, "image_pad", [&](auto ti) {
+        using TI = decltype(ti);
+        if (launch<pad_pool_kernel<TI>>("image_pad", grid1(bins * 64), dim3(256), 0, st, (const TI*)img, pooled, BC, H, W, Hn, Wn, Ho, Wo, hs, ws)) return 1;
+        return launch<pad_fill_kernel<TI>>("image_pad", grid1(pix), dim3(256), 0, st, (const TI*)img, pooled, out, BC, H, W, Hn, Wn, Ho, Wo, hs, ws);
+    });
 }
 extern "C" int s2m2_image_pad(const void* img, float* pooled, float* out, int B, int C, int H, int W, int factor, int img_dtype,
                               void* stream) {

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
 
@@ -141,13 +142,9 @@ __global__ __launch_bounds__(CFG::NT) void pw_direct_kernel(PwArgs p) {
 template <int KS, int NWN, int NWM>
 static int launch_pw(const PwArgs& a, hipStream_t st) {
     using CFG = PwCfg<KS, NWN, NWM>;
-    auto kern = pw_direct_kernel<CFG>;
-    static size_t lds_granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::LDS_BYTES, lds_granted, "pw_direct")) return 1;
     const long long nblk = (a.rows + CFG::BM - 1) / CFG::BM;
     if (nblk >= (1LL << 31)) return set_error("pw_direct: %lld row tiles do not fit a grid dimension", nblk);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
-    return check_launch("pw_direct");
+    return launch<pw_direct_kernel<CFG>>("pw_direct", dim3((unsigned)nblk), dim3(CFG::NT), CFG::LDS_BYTES, st, a);
 }
 
 // k16 steps the library is instantiated for (K rounded up to 16 must be one of them) and waves per block by cout tiles: up to 2 cout tiles
@@ -221,8 +218,7 @@ static int pw_direct_impl(const s2m2_pw_desc* d, void* stream) {
     a.c1 = cum[0]; a.c2 = cum[1]; a.c3 = cum[2]; a.K = K;
     a.rows = d->rows; a.w = d->weight_frag; a.bias = d->bias; a.out = d->out; a.out_stride = d->out_stride;
     a.Cout = d->Cout; a.act = d->act; a.shuffle2 = d->shuffle2; a.Ho = d->Ho; a.Wo = d->Wo;
-    a.zero = zero_page();
-    S2M2_REQUIRE(a.zero, "pw_direct: cannot allocate the zero page");
+    if (bind_zero_page(a, "pw_direct")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (pw_ks(K)) {
         case 2: return dispatch_pw_n<2>(a, st);

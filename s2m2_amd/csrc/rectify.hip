@@ -10,6 +10,7 @@
 // not by its stores.  Loads never leave the source: tap coordinates are clamped into it and the
 // contribution of an outside tap is selected away, so there is no divergent branch and no out-of-bounds address for any map value (NaN included).
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 
 namespace s2m2 {
@@ -152,10 +153,10 @@ __global__ __launch_bounds__(kRectThreads) void rectify_kernel(const RectParams 
     }
 }
 
-template <int FMT, bool OUT_U8> static void rect_launch(const RectParams& p, bool vec, hipStream_t s) {
+template <int FMT, bool OUT_U8> static int rect_launch(const RectParams& p, bool vec, hipStream_t s) {
     const dim3 grid((unsigned)((long long)p.tiles * p.n_img)), block(kRectThreads);
-    if (vec) hipLaunchKernelGGL((rectify_kernel<FMT, OUT_U8, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((rectify_kernel<FMT, OUT_U8, false>), grid, block, 0, s, p);
+    if (vec) return launch<rectify_kernel<FMT, OUT_U8, true>>("rectify", grid, block, 0, s, p);
+    return launch<rectify_kernel<FMT, OUT_U8, false>>("rectify", grid, block, 0, s, p);
 }
 
 static int rectify_impl(const s2m2_rectify_desc* d, void* stream) {
@@ -196,16 +197,11 @@ static int rectify_impl(const s2m2_rectify_desc* d, void* stream) {
     const bool u8 = d->out_dtype == 2;
     const bool vec = d->Wd % 4 == 0 && ((uintptr_t)d->out & (u8 ? 3 : 15)) == 0 && ((uintptr_t)d->maps & 15) == 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define S2M2_RECT_FMT(F)                       \
-    do {                                       \
-        if (u8) rect_launch<F, true>(p, vec, s); \
-        else rect_launch<F, false>(p, vec, s);   \
-    } while (0)
-    if (d->src_format == S2M2_RECTIFY_SRC_U8_HWC) S2M2_RECT_FMT(S2M2_RECTIFY_SRC_U8_HWC);
-    else if (d->src_format == S2M2_RECTIFY_SRC_U8_CHW) S2M2_RECT_FMT(S2M2_RECTIFY_SRC_U8_CHW);
-    else S2M2_RECT_FMT(S2M2_RECTIFY_SRC_F32_CHW);
+#define S2M2_RECT_FMT(F) (u8 ? rect_launch<F, true>(p, vec, s) : rect_launch<F, false>(p, vec, s))
+    if (d->src_format == S2M2_RECTIFY_SRC_U8_HWC) return S2M2_RECT_FMT(S2M2_RECTIFY_SRC_U8_HWC);
+    if (d->src_format == S2M2_RECTIFY_SRC_U8_CHW) return S2M2_RECT_FMT(S2M2_RECTIFY_SRC_U8_CHW);
+    return S2M2_RECT_FMT(S2M2_RECTIFY_SRC_F32_CHW);
 #undef S2M2_RECT_FMT
-    return check_launch("rectify");
 }
 
 }  // namespace s2m2

@@ -28,6 +28,7 @@
 //
 // fp16, C = 128 (the S model's 1/4 and 1/8 levels), heads 1 or 2, rows of up to 320 tokens.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
 #include <math.h>
@@ -582,19 +583,15 @@ static int row_attn_impl(const s2m2_rowattn_desc* d, void* stream) {
     a.ln_eps = d->ln_eps; a.ln_out_eps = d->ln_out_eps;
     a.scale = 1.0f / sqrtf((float)(128 / d->heads));
     a.zero = nullptr;
-    static const int dbg = getenv("S2M2_RA_DBG") ? atoi(getenv("S2M2_RA_DBG")) : 0;
+    static const int dbg = (int)env_int("S2M2_RA_DBG", 0);
     a.dbg = dbg;
     const int nwv = (d->w + 31) / 32;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(d->nimg * d->h);
-    auto launch = [&](auto kern, size_t* granted) -> int {
-        if (reserve_lds(reinterpret_cast<const void*>(kern), ra::LDS_BYTES, granted, "row_attn")) return 1;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nwv), ra::LDS_BYTES, st, a);
-        return check_launch("row_attn");
-    };
-    static size_t granted[4][kMaxDevices] = {};                      // per instantiation
-    if (nwv <= 5) return d->heads == 1 ? launch(row_attn_kernel<320, 1>, granted[0]) : launch(row_attn_kernel<320, 2>, granted[1]);
-    return d->heads == 1 ? launch(row_attn_kernel<640, 1>, granted[2]) : launch(row_attn_kernel<640, 2>, granted[3]);
+    const dim3 block(64 * nwv);
+    const bool one = d->heads == 1;
+    if (nwv <= 5) return one ? launch<row_attn_kernel<320, 1>>("row_attn", grid, block, ra::LDS_BYTES, st, a) : launch<row_attn_kernel<320, 2>>("row_attn", grid, block, ra::LDS_BYTES, st, a);
+    return one ? launch<row_attn_kernel<640, 1>>("row_attn", grid, block, ra::LDS_BYTES, st, a) : launch<row_attn_kernel<640, 2>>("row_attn", grid, block, ra::LDS_BYTES, st, a);
 }
 extern "C" int s2m2_row_attn(const s2m2_rowattn_desc* d, void* stream) {
     return s2m2::plan_dispatch_desc<s2m2_rowattn_desc>("s2m2_row_attn", &row_attn_impl, d, stream);

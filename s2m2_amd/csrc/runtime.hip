@@ -1,5 +1,6 @@
 // Host-side runtime glue of libs2m2_hip.so: version, thread-local error text, launch checks.
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 
 #include <mutex>
@@ -83,17 +84,13 @@ __global__ void clock_probe_kernel(unsigned long long* out) {
 extern "C" int s2m2_debug_clock_probe(void* out, void* stream) {
     using namespace s2m2;
     S2M2_REQUIRE(out, "debug_clock_probe: null pointer");
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<unsigned long long*>(out));
-    return check_launch("debug_clock_probe");
+    return launch<clock_probe_kernel>("debug_clock_probe", dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<unsigned long long*>(out));
 }
 
 extern "C" int s2m2_debug_poison_lds(void* stream) {
     using namespace s2m2;
     constexpr int kBytes = 160 * 1024;                            // one block owns a CU's whole LDS; 4 blocks per CU's worth of grid
-    static size_t granted[kMaxDevices] = {};
-    if (reserve_lds(reinterpret_cast<const void*>(poison_lds_kernel), kBytes, granted, "debug_poison_lds")) return 1;
-    hipLaunchKernelGGL(poison_lds_kernel, dim3(1024), dim3(256), kBytes, static_cast<hipStream_t>(stream), (unsigned*)nullptr, kBytes / 4);
-    return check_launch("debug_poison_lds");
+    return launch<poison_lds_kernel>("debug_poison_lds", dim3(1024), dim3(256), kBytes, static_cast<hipStream_t>(stream), (unsigned*)nullptr, kBytes / 4);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -258,8 +255,7 @@ int range_collect(const char* name, void* stream) {
         if (slot >= kRangeLog) return 0;                           // log full: later launches are not recorded
         g_range_names.push_back(name);
     }
-    hipLaunchKernelGGL(range_collect_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), buf, slot);
-    return check_launch("range_collect");
+    return launch<range_collect_kernel>("range_collect", dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), buf, slot);
 }
 }  // namespace s2m2
 

@@ -38,6 +38,7 @@
 //   * subtract / row sum / column multiply-add work on register pairs (v_pk_add_f32, v_pk_fma_f32), the 16-lane reductions are
 //     v_max_f32_dpp / v_add_f32_dpp / v_min_i32_dpp (one instruction per butterfly step).
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 #include <stdlib.h>
 
@@ -528,21 +529,18 @@ static int launch_sinkhorn(const void* cv, float* disp, float* conf, float* occ,
     // 16 waves per row block where a lane's state (8 * NCH columns: values + two accumulator words each) fits 128 registers, else 8
     constexpr int NWV = NCH == 1 ? 16 : 8;
     using L = K2Lds<NWV, GL, NCH>;
-    auto kern = sinkhorn_regress_kernel<TI, NWV, GL, NCH, TRI>;
     size_t lds = L::vec_bytes(w);
     if (TRI) {
         constexpr int VEC = 16 / sizeof(TI);
         const size_t tri_bytes = ((lds + 15) & ~(size_t)15) + L::tri_pieces_total(w, VEC) * 16;
-        static const bool off = getenv("S2M2_K2_TRI") != nullptr && atoi(getenv("S2M2_K2_TRI")) == 0;   // A/B switch
+        static const bool off = env_is0("S2M2_K2_TRI");   // A/B switch
         if (!use_pos || off || tri_bytes > 160 * 1024)
             return launch_sinkhorn<TI, GL, NCH, false>(cv, disp, conf, occ, amax, rows, w, ot_iter, use_pos, pitch, st);
         lds = tri_bytes;
     }
     if (lds > 160 * 1024) return set_error("sinkhorn: w=%d needs %zu bytes of LDS (at most about w = 1200)", w, lds);
-    static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
-    if (reserve_lds(reinterpret_cast<const void*>(kern), lds, lds_granted, "sinkhorn")) return 1;
-    hipLaunchKernelGGL(kern, dim3(rows), dim3(NWV * 64), lds, st, static_cast<const TI*>(cv), disp, conf, occ, amax, w, ot_iter, use_pos, pitch);
-    return check_launch("sinkhorn_regress");
+    return launch<sinkhorn_regress_kernel<TI, NWV, GL, NCH, TRI>>("sinkhorn_regress", dim3(rows), dim3(NWV * 64), lds, st, static_cast<const TI*>(cv), disp, conf, occ,
+                                                                  amax, w, ot_iter, use_pos, pitch);
 }
 
 // lanes per row so that a row needs at most 3 chunks of 8 columns per lane: 16 lanes up to w = 384, 32 up to 768, 64 up to 1536.

@@ -7,6 +7,7 @@
 // gathers the 9 low-resolution neighbours from cache.  HBM-bound: ~(logit row + 3*4 B) per output pixel.
 //   out[m][b,Y,X] = scale_m * sum_n softmax_n(logit[b,Y,X,:9]) * x[m][b, clamp(Y/f + n/3 - 1), clamp(X/f + n%3 - 1)]
 #include "common.h"
+#include "launch.h"
 #include "plan.h"
 
 namespace s2m2 {
@@ -157,10 +158,7 @@ static int convex_upsample_impl(const float* const* x, float* const* out, const 
     const long long total = (long long)B * hs * factor * ws * factor;
     hipStream_t st = static_cast<hipStream_t>(stream);
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == S2M2_F16) hipLaunchKernelGGL((convex_upsample_kernel<half_t>), grid, dim3(256), 0, st, a);
-    else if (dtype == S2M2_F32) hipLaunchKernelGGL((convex_upsample_kernel<float>), grid, dim3(256), 0, st, a);
-    else return set_error("convex_upsample: unsupported dtype %d", dtype);
-    return check_launch("convex_upsample");
+    return by_dtype(dtype, "convex_upsample", [&](auto t) { return launch<convex_upsample_kernel<decltype(t)>>("convex_upsample", grid, dim3(256), 0, st, a); });
 }
 // Plans record arguments BY VALUE: the three host arrays of this entry point (device pointers of the maps, scales) are copied into a
 // descriptor whose words the plan scans and patches; the trampoline rebuilds the arrays from it.
@@ -203,12 +201,11 @@ static int resample2x_impl(const void* x, void* y, int N, int H, int W, int C, l
     const long long total = (long long)N * Ho * Wo * (C / vec);
     dim3 grid((unsigned)((total + 255) / 256));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == S2M2_F16 && mode == 0) hipLaunchKernelGGL((resample2x_kernel<half_t, 0>), grid, dim3(256), 0, st, (const half_t*)x, (half_t*)y, N, H, W, C, x_stride, y_stride);
-    else if (dtype == S2M2_F16) hipLaunchKernelGGL((resample2x_kernel<half_t, 1>), grid, dim3(256), 0, st, (const half_t*)x, (half_t*)y, N, H, W, C, x_stride, y_stride);
-    else if (dtype == S2M2_F32 && mode == 0) hipLaunchKernelGGL((resample2x_kernel<float, 0>), grid, dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, x_stride, y_stride);
-    else if (dtype == S2M2_F32) hipLaunchKernelGGL((resample2x_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, (float*)y, N, H, W, C, x_stride, y_stride);
-    else return set_error("resample2x: unsupported dtype %d", dtype);
-    return check_launch("resample2x");
+    return by_dtype(dtype, "resample2x", [&](auto t) {
+        using T = decltype(t);
+        if (mode == 0) return launch<resample2x_kernel<T, 0>>("resample2x", grid, dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, x_stride, y_stride);
+        return launch<resample2x_kernel<T, 1>>("resample2x", grid, dim3(256), 0, st, (const T*)x, (T*)y, N, H, W, C, x_stride, y_stride);
+    });
 }
 extern "C" int s2m2_resample2x(const void* x, void* y, int N, int H, int W, int C, long long x_stride, long long y_stride, int mode,
                                int dtype, void* stream) {
