@@ -457,6 +457,37 @@ int s2m2_conv_block_supported(int C, int H, int W, int dtype);
 int s2m2_conv_block(const s2m2_convblock_desc* desc, void* stream);
 
 /*
+ * K17 -- one ConvGRU half (refinenet.py:7-36) in ONE launch (ABI still 800: additive):
+ *     z = sigmoid(convz([h, x]))   r = sigmoid(convr([h, x]))   q = tanh(convq([r * h, x]))   out = (1 - z) * h + z * q
+ *   with KH x KW = 3 x 1 or 1 x 3 taps (zero padding), hidden and input width C.  Replaces the launch pair s2m2_conv2d (korder 2, the stacked
+ *   z | r layer with epi_cout0 = C and the r * h epilogue) / s2m2_conv2d (the candidate layer with S2M2_EPI_GRU) with the same arithmetic in
+ *   the same order (bit-identical to the pair with the candidate layer in K order 2): a block owns a patch of output pixels, recomputes r on
+ *   the patch's one-pixel ring along the tap axis and keeps z and r * h on the CU.
+ *     h, x, out  (N, H, W, C) fp16, channels contiguous, 16-byte aligned, pixel strides in elements (multiples of 8); out distinct from h and x
+ *     w_zr       [convz | convr] stacked along Cout (2 C rows, z first) over cat(h, x), as s2m2_conv_desc.weight with korder = 2
+ *     w_q        convq over cat(r * h, x), as s2m2_conv_desc.weight with korder = 2
+ *     b_zr, b_q  fp32 (2 C) / (C), or NULL
+ *   fp16, C = 128: ask s2m2_conv_gru_supported.
+ */
+typedef struct s2m2_convgru_desc {
+    const void* h;
+    long long h_stride;
+    const void* x;
+    long long x_stride;
+    void* out;
+    long long out_stride;
+    int N, H, W, C;
+    int KH, KW;
+    const void* w_zr;
+    const void* w_q;
+    const float* b_zr;
+    const float* b_q;
+    int dtype;
+} s2m2_convgru_desc;
+int s2m2_conv_gru_supported(int C, int H, int W, int dtype);
+int s2m2_conv_gru(const s2m2_convgru_desc* desc, void* stream);
+
+/*
  * K11 -- a 1x1 layer with any channel counts in the direct style (fp16; round 4): Conv2d(kernel 1) / Linear / ConvTranspose2d(2, stride 2) on
  *   up to four channel-concatenated sources (reference: LocalRefiner's corr_feat / conf_occ_feat / disp_corr_ctx_cat 1x1 layers,
  *   refinenet.py:87-106,138-146; the up_conv 1x1 layers of Unet / MRT on the coarse grid, unet.py:32-37, stacked_MRT.py:29-34; the

@@ -187,6 +187,9 @@ class Engine:
         self.convblock_c256 = os.environ.get("S2M2_CONVBLOCK_C256", "0") == "1"
         # S2M2_GRU_FRAG=1 (A/B): ConvGRU's candidate layer (two-operand blend epilogue) on K5 v5's 64-pixel blocks instead of the v3 halo tiles
         self.gru_frag = os.environ.get("S2M2_GRU_FRAG", "0") == "1"
+        # S2M2_GRU_FUSE=0 (A/B): every ConvGRU half as two launches (stacked z | r, candidate layer) instead of ONE K17 launch (hip.conv_gru: fp16,
+        # hidden and input width 128 -- the S model; profiles/r08/ab_gru_fuse.txt)
+        self.gru_fuse = os.environ.get("S2M2_GRU_FUSE", "1") != "0"
         self._tokens_normed: Optional[Tensor] = None             # DispInit's LayerNorm of feature_tr_4x, written by the last K9 launch
         self.ln_w = self.p["disp_init.layer_norm.weight"].contiguous()
         self.ln_b = self.p["disp_init.layer_norm.bias"].contiguous()
@@ -443,6 +446,10 @@ class Engine:
         """K12 (hip.conv_narrow) for this spatial layer on a cin-channel tensor"""
         return self.use_k12 and self.supported("conv_narrow", kh, kw, stride, cin, cout)
 
+    def gru_fuse_ok(self, c: int, h: int, w: int) -> bool:
+        """K17 takes a ConvGRU half of this width on this grid (a binding without the entry: no)"""
+        return getattr(hip, "conv_gru_supported", None) is not None and self.supported("conv_gru", c, h, w)
+
     def convblock_ok(self, c: int, h: int, w: int) -> bool:
         """K14 takes a ConvBlock2D of this width on this grid"""
         return self.supported("conv_block", c, h, w)
@@ -635,6 +642,12 @@ class Engine:
         C = h.shape[-1]
         for sfx in ("1", "2"):
             zr = self.merged(f"{p}|zr{sfx}", [(f"{p}.convz{sfx}", 0, 1.0, False), (f"{p}.convr{sfx}", 0, 1.0, False)], h.shape[-1] + x.shape[-1])
+            if self.gru_fuse and zr.korder == 2 and zr.cout == 2 * C and x.shape[-1] == C and h.dim() == 4 and self.gru_fuse_ok(C, h.shape[1], h.shape[2]):
+                q = self.std(f"{p}.convq{sfx}")
+                if q.korder == 2 and q.cout == C and (q.kh, q.kw) == (zr.kh, zr.kw) and (q.kh, q.kw) in ((1, 3), (3, 1)):
+                    # the whole half -- z | r, r * h, the candidate layer, the blend -- as ONE K17 launch: z and r * h never leave the CU
+                    h = hip.conv_gru(h, x, zr.weight, zr.bias, q.weight, q.bias, q.kh, q.kw)
+                    continue
             if zr.korder == 2 and zr.cout == 2 * C and C % 128 == 0:
                 both = self.cconv(zr, [h, x], act=hip.ACT_SIGMOID, epi=hip.EPI_MUL, aux0=h, epi_cout0=C)
                 z, rh = both[..., :C], both[..., C:]

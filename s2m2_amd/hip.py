@@ -60,6 +60,12 @@ class ConvBlockDesc(ctypes.Structure):
                 ("b_1x2", _vp), ("patch_rows", _i), ("dtype", _i)]
 
 
+class ConvGruDesc(ctypes.Structure):
+    """mirror of s2m2_convgru_desc (include/s2m2_hip.h): K17, one ConvGRU half per launch"""
+    _fields_ = [("h", _vp), ("h_stride", _ll), ("x", _vp), ("x_stride", _ll), ("out", _vp), ("out_stride", _ll), ("N", _i), ("H", _i), ("W", _i),
+                ("C", _i), ("KH", _i), ("KW", _i), ("w_zr", _vp), ("w_q", _vp), ("b_zr", _vp), ("b_q", _vp), ("dtype", _i)]
+
+
 class PwDesc(ctypes.Structure):
     """mirror of s2m2_pw_desc (include/s2m2_hip.h)"""
     _fields_ = [("src", _vp * 4), ("src_c", _i * 4), ("src_stride", _ll * 4), ("nsrc", _i), ("rows", _ll), ("weight_frag", _vp), ("bias", _vp),
@@ -162,6 +168,8 @@ SIGNATURES = {
     "s2m2_mlp_chain": (_i, [ctypes.POINTER(ChainDesc), _vp]),
     "s2m2_conv_block_supported": (_i, [_i, _i, _i, _i]),
     "s2m2_conv_block": (_i, [ctypes.POINTER(ConvBlockDesc), _vp]),
+    "s2m2_conv_gru_supported": (_i, [_i, _i, _i, _i]),
+    "s2m2_conv_gru": (_i, [ctypes.POINTER(ConvGruDesc), _vp]),
     "s2m2_row_attn_supported": (_i, [_i, _i, _i, _i]),
     "s2m2_row_attn": (_i, [ctypes.POINTER(RowAttnDesc), _vp]),
     "s2m2_feature_fusion_supported": (_i, [_i, _i]),
@@ -1211,3 +1219,7 @@ def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, map
     d.src_format, d.round, d.order = fmt, int(bool(round)), order
     with torch.cuda.device(records.device):
         _check(load().s2m2_rectify(ctypes.byref(d), _stream()), "s2m2_rectify")
+
+
+# K17 (s2m2_conv_gru): its wrapper lives in hip_gru.py and is re-exported here, so callers write hip.conv_gru like every other launch
+from .hip_gru import conv_gru, conv_gru_supported  # noqa: E402,F401
