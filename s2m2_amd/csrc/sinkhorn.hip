@@ -538,7 +538,8 @@ static int launch_sinkhorn(const void* cv, float* disp, float* conf, float* occ,
             return launch_sinkhorn<TI, GL, NCH, false>(cv, disp, conf, occ, amax, rows, w, ot_iter, use_pos, pitch, st);
         lds = tri_bytes;
     }
-    if (lds > 160 * 1024) return set_error("sinkhorn: w=%d needs %zu bytes of LDS (at most about w = 1200)", w, lds);
+    // (not reached through dispatch_ppl: the vectors of its widest row, w = 1536, take 110 912 bytes)
+    if (lds > 160 * 1024) return set_error("sinkhorn: w=%d needs %zu bytes of LDS, a block has 163840", w, lds);
     return launch<sinkhorn_regress_kernel<TI, NWV, GL, NCH, TRI>>("sinkhorn_regress", dim3(rows), dim3(NWV * 64), lds, st, static_cast<const TI*>(cv), disp, conf, occ,
                                                                   amax, w, ot_iter, use_pos, pitch);
 }
