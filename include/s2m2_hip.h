@@ -42,7 +42,8 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * but engine files record the value and must be exported again); still 800 with s2m2_rectify and s2m2_rectify_desc (K16, the rectifier in front of
  * the forward): purely additive -- no existing struct or entry point changes, engine files do not contain the stage -- so neither callers nor
  * engine files of 800 are invalidated.  A library built before K16 reports 800 as well and lacks the symbol: s2m2_amd/hip.py load() names the
- * missing symbol and asks for a rebuild. */
+ * missing symbol and asks for a rebuild.  Still 800 with s2m2_disp_eval, s2m2_eval_workspace_bytes, s2m2_eval_tile_rows and s2m2_eval_desc (K18, the
+ * evaluation stage behind the forward), added the same way. */
 #define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
@@ -795,6 +796,82 @@ typedef struct s2m2_rectify_desc {
     int order;
 } s2m2_rectify_desc;
 int s2m2_rectify(const s2m2_rectify_desc* desc, void* stream);
+
+/*
+ * K18 -- the evaluation stage behind the forward: disparity error statistics against ground truth, on the device.  The reference has no such
+ *   code (its numbers come from benchmark servers); the semantics are defined here and pinned by the numpy oracle of tests/eval_oracle.py.
+ *   Every output is an integer, so that the result does not depend on the order of any sum.
+ *     disp, occ, conf  (B,1,Hp,Wp) fp32: the padded maps as S2M2.forward / s2m2_engine_run return them; occ and conf come together or not at all
+ *     gt               (B,1,H,W) fp32 ground-truth disparity, UNPADDED.  The crop of image_crop is fused as in K15: GT pixel (v,u) reads map
+ *                      pixel (v + (Hp-H)/2, u + (Wp-W)/2)
+ *     region           (B,1,H,W) uint8 or NULL: a pixel takes part only where region != 0 (the non-occluded mask of a benchmark)
+ *   per pixel, all in fp32:
+ *     in_region = region == NULL || region != 0;       evaluated = in_region && isfinite(gt) && gt > gt_min
+ *     e = disp - gt;   a = |e|;   finite = isfinite(disp)
+ *     a prediction that is not finite is bad at every threshold and in D1, is counted in n_nonfinite, and takes no part in the sums, in the
+ *     histogram or in the sums of the confidence table
+ *     q = (u64) rint(min(a, 1024) * 65536);      s = (u64) rint(min(e * e, 1048576) * 4096)         (round half to even)
+ *       both scalings are exact multiplications by a power of two, so float32 arithmetic on the host reproduces q and s bit for bit.
+ *       q <= 2^26 and s <= 2^32: extents are limited to H * W < 2^31 pixels per pair, so a pair's sums stay below 2^57 and 2^63 and fit in
+ *       64 bits (2^23 pixels, more than any benchmark image, give 2^49 and 2^55)
+ *     bad[t] = !finite || a > thr[t]             (strict; t < nthr)
+ *     d1     = !finite || (a > d1_abs && a > d1_rel * |gt|)                                         (KITTI: 3 px and 0.05)
+ *     hbin   = min(1024, (int) floor(a * 64))    (bins of 1/64 px over [0,16), bin 1024 = everything from 16 px on)
+ *     cbin   = clamp((int) floor(conf * 64), 0, 63), a NaN confidence -> 0
+ *     kept   = conf > conf_min && occ > occ_min  (the rule of K15; false without occ / conf)
+ *   stats: one block of S2M2_EVAL_WORDS 64-bit words per pair:
+ *     ALL   at S2M2_EVAL_ALL:  the S2M2_EVAL_BLOCK_WORDS words  N_REGION (pixels in_region), N_EVAL (evaluated), N_NONFINITE (evaluated, not
+ *           finite), SUM_ABS_Q (sum of q), SUM_SQ_Q (sum of s), D1_BAD, BAD + t (t < 8)
+ *     KEPT  at S2M2_EVAL_KEPT: the same words over the pixels that are also kept (N_REGION: in_region && kept, N_EVAL: evaluated && kept, ...)
+ *     HIST  at S2M2_EVAL_HIST: S2M2_EVAL_HIST_BINS counts of hbin over the evaluated finite pixels
+ *     CONF  at S2M2_EVAL_CONF: S2M2_EVAL_CONF_BINS rows of S2M2_EVAL_CONF_ROW_WORDS words, row cbin = COUNT (evaluated pixels of the bin),
+ *           SUM_ABS_Q (over its finite ones), BAD + t
+ *   EVERY word is written by every call: threshold slots t >= nthr as 0, KEPT and CONF as 0 without occ / conf.
+ *   Two launches, no host step between them, no global atomics, no waiting between blocks, no dependence on what workspace or stats held
+ *   before.  Launch A: a block takes a fixed tile of s2m2_eval_tile_rows(H, W) whole rows of one pair, counts in registers and in LDS (integer
+ *   adds: order independent; sums that can pass 2^32 inside a tile are carried in 64 bits) and stores one partial block per tile
+ *   into the workspace; launch B sums the partial blocks of each pair into stats.  Integer sums of fixed tiles: bit-reproducible.  The maps
+ *   are read with 16-byte loads whenever Wp % 4 == 0 and the map pointers are 16-byte aligned, gt and region with 16- and 4-byte loads where
+ *   a group of four pixels is aligned and gt is 16-byte (region 4-byte) aligned; per pixel otherwise (any W, any crop offset).
+ *   Launch plans: s2m2_disp_eval is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing;
+ *   the stage runs after s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ *   Errors (before any device call): null descriptor / disp / gt / stats / workspace, exactly one of occ and conf, non-positive extents,
+ *   H > Hp, W > Wp, extents too large, nthr outside 0..8, thresholds not strictly increasing or not > 0 (or not finite), d1_abs / d1_rel /
+ *   conf_min / occ_min not finite, gt_min NaN (-inf is allowed: every finite gt is valid), misaligned pointers.
+ */
+#define S2M2_EVAL_MAX_THR   8
+#define S2M2_EVAL_HIST_BINS 1025      /* 1024 bins of 1/64 px over [0,16) + one overflow bin */
+#define S2M2_EVAL_CONF_BINS 64
+enum {
+    S2M2_EVAL_N_REGION = 0, S2M2_EVAL_N_EVAL = 1, S2M2_EVAL_N_NONFINITE = 2, S2M2_EVAL_SUM_ABS_Q = 3, S2M2_EVAL_SUM_SQ_Q = 4,
+    S2M2_EVAL_D1_BAD = 5, S2M2_EVAL_BAD = 6,
+    S2M2_EVAL_BLOCK_WORDS = 14,              /* 6 + S2M2_EVAL_MAX_THR */
+    S2M2_EVAL_CONF_COUNT = 0, S2M2_EVAL_CONF_SUM_ABS_Q = 1, S2M2_EVAL_CONF_BAD = 2,
+    S2M2_EVAL_CONF_ROW_WORDS = 10,           /* 2 + S2M2_EVAL_MAX_THR */
+    S2M2_EVAL_ALL = 0,
+    S2M2_EVAL_KEPT = 14,
+    S2M2_EVAL_HIST = 28,
+    S2M2_EVAL_CONF = 1053,                   /* S2M2_EVAL_HIST + S2M2_EVAL_HIST_BINS */
+    S2M2_EVAL_WORDS = 1693                   /* S2M2_EVAL_CONF + S2M2_EVAL_CONF_BINS * S2M2_EVAL_CONF_ROW_WORDS */
+};
+typedef struct s2m2_eval_desc {
+    const float* disp;            /* (B,1,Hp,Wp) fp32, padded, as forward / s2m2_engine_run return it */
+    const float* occ;             /* (B,1,Hp,Wp) or NULL */
+    const float* conf;            /* (B,1,Hp,Wp) or NULL; occ and conf come together */
+    const float* gt;              /* (B,1,H,W) fp32, UNPADDED ground-truth disparity */
+    const unsigned char* region;  /* (B,1,H,W) uint8 or NULL: a pixel is evaluated only where region != 0 */
+    void* workspace;              /* >= s2m2_eval_workspace_bytes(B,H,W), 8-byte aligned */
+    unsigned long long* stats;    /* (B, S2M2_EVAL_WORDS) */
+    int B, H, W, Hp, Wp;
+    int nthr;                     /* 0 .. S2M2_EVAL_MAX_THR */
+    float thr[S2M2_EVAL_MAX_THR]; /* bad-pixel thresholds in px, strictly increasing, > 0 */
+    float d1_abs, d1_rel;         /* D1: |e| > d1_abs && |e| > d1_rel * |gt|   (KITTI: 3, 0.05) */
+    float gt_min;                 /* gt is valid iff isfinite(gt) && gt > gt_min  (Middlebury / ETH3D: inf = invalid; KITTI: 0 = invalid) */
+    float conf_min, occ_min;      /* the "kept" set: conf > conf_min && occ > occ_min (K15's rule) */
+} s2m2_eval_desc;
+size_t s2m2_eval_workspace_bytes(int B, int H, int W);      /* 0: bad extents */
+int s2m2_eval_tile_rows(int H, int W);                      /* image rows of one tile of launch A; 0: bad extents */
+int s2m2_disp_eval(const s2m2_eval_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

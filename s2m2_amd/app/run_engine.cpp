@@ -1,6 +1,6 @@
 // s2m2_run_engine: runs an engine file (s2m2_amd/export.py: export_engine) with nothing but libs2m2_hip.so and the HIP runtime.
 //
-//   s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N]
+//   s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [3D outputs] [evaluation]
 //
 // LEFT / RIGHT: raw little-endian float32 (B,3,H,W) images in [0,255], the engine's B, H and W (the engine must take float32 images).
 // --out DIR: writes DIR/disp.f32, DIR/occ.f32, DIR/conf.f32, each a raw float32 (B,1,out_h,out_w) map.
@@ -13,8 +13,21 @@
 // --ply: a binary little-endian PLY (x y z float, red green blue alpha uchar; the device records verbatim).  B > 1: one file per pair,
 //   OUT.<b>.ply (a trailing ".ply" of OUT is dropped first).  --depth: raw float32 (B,1,H,W) metric depth, 0 where no point was kept.
 // With --repeat the cloud stage is timed as well (HIP events around N calls) and its microseconds per pair printed on a line of its own.
+//
+// Evaluation against ground truth (s2m2_disp_eval on the device buffers of the run; without --gt nothing below happens):
+//   --gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] [--thresholds a,b,c] [--conf-min X] [--occ-min X] --metrics OUT.json
+// --gt: a greyscale PFM (Pf) of W x (B * H) pixels, H <= out_h and W <= out_w of the engine: the ground truths of the B pairs stacked top to
+//   bottom, pair 0 first (B = 1: the file as a benchmark ships it).  A ground truth smaller than the maps is the centred window image_crop cuts.
+// --gt-region: raw uint8 (B,1,H,W), a pixel is evaluated where the byte is not 0 (a benchmark's non-occluded mask).
+// --gt-min X: ground truth is valid where it is finite and > X (default 0; "-inf": every finite value).  --thresholds: up to 8 bad-pixel
+//   thresholds in px, increasing (default 0.5,1,2,4).  --conf-min / --occ-min: the kept set, as for the cloud.
+// --metrics: JSON -- {"thresholds": [...], "pairs": [{"words": [the S2M2_EVAL_WORDS raw stat words], n_region, n_eval, nonfinite, epe, rmse, d1,
+//   bad_<t>, a50, a90, a95, a99, density, "kept": {the same after the filter}}, ...]}; a ratio of an empty set (0 / 0) or an infinite quantile
+//   is written as null.  The ground-truth files are parsed before the engine is loaded; their extents are compared with the engine's right after.
+// With --repeat the stage is timed (HIP events around N calls) and its microseconds per pair printed on a line of its own.
 #include <hip/hip_runtime.h>
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,7 +38,8 @@
 
 static const char* USAGE =
     "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
-    "[--conf-min X] [--occ-min X] [--unfiltered] --ply OUT.ply [--depth OUT.f32]]";
+    "[--conf-min X] [--occ-min X] [--unfiltered] --ply OUT.ply [--depth OUT.f32]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--thresholds a,b,c] --metrics OUT.json]";
 
 static int fail(const char* what) {
     fprintf(stderr, "s2m2_run_engine: %s\n", what);
@@ -84,6 +98,65 @@ static bool write_ply(const std::string& path, const void* records, long long n)
     return fclose(f) == 0 && ok;
 }
 
+// greyscale PFM: "Pf", "width height", "scale" (negative: little-endian), then the rows bottom to top -> rows top to bottom
+static bool read_pfm(const char* path, std::vector<float>& v, int& width, int& height, const char*& why) {
+    FILE* f = fopen(path, "rb");
+    why = "cannot open the file";
+    if (!f) return false;
+    char magic[3] = {0, 0, 0};
+    double scale = 0.0;
+    bool ok = false;
+    why = "not a greyscale PFM (header Pf, width height, scale)";
+    if (fscanf(f, "%2s %d %d %lf", magic, &width, &height, &scale) == 4 && strcmp(magic, "Pf") == 0 && fgetc(f) == '\n' && width > 0 &&
+        height > 0 && (long long)width * height < (1LL << 31) && scale != 0.0 && scale == scale) {
+        why = "the data is not width * height float32 values";
+        v.resize((size_t)width * height);
+        ok = true;
+        for (int y = height - 1; y >= 0 && ok; --y) ok = fread(v.data() + (size_t)y * width, sizeof(float), width, f) == (size_t)width;
+        ok = ok && fgetc(f) == EOF;
+        if (ok && scale > 0.0) {                                     // big-endian
+            unsigned char* p = reinterpret_cast<unsigned char*>(v.data());
+            for (size_t i = 0; i < v.size(); ++i, p += 4) {
+                const unsigned char a = p[0], b = p[1];
+                p[0] = p[3]; p[1] = p[2]; p[2] = b; p[3] = a;
+            }
+        }
+    }
+    fclose(f);
+    return ok;
+}
+
+static void json_number(FILE* f, const char* key, double x, const char* tail) {
+    if (isfinite(x)) fprintf(f, "\"%s\": %.17g%s", key, x, tail);
+    else fprintf(f, "\"%s\": null%s", key, tail);
+}
+
+// the derived numbers of one ALL / KEPT block (s2m2_amd/evaluate.py: EvalStats, the same arithmetic in double)
+static void json_block(FILE* f, const unsigned long long* blk, const float* thr, int nthr) {
+    const double n = (double)blk[S2M2_EVAL_N_EVAL], fin = (double)(blk[S2M2_EVAL_N_EVAL] - blk[S2M2_EVAL_N_NONFINITE]);
+    fprintf(f, "\"n_region\": %llu, \"n_eval\": %llu, \"nonfinite\": %llu, ", blk[S2M2_EVAL_N_REGION], blk[S2M2_EVAL_N_EVAL], blk[S2M2_EVAL_N_NONFINITE]);
+    json_number(f, "epe", (double)blk[S2M2_EVAL_SUM_ABS_Q] / 65536.0 / fin, ", ");
+    json_number(f, "rmse", sqrt((double)blk[S2M2_EVAL_SUM_SQ_Q] / 4096.0 / fin), ", ");
+    for (int t = 0; t < nthr; ++t) {
+        char key[32];
+        snprintf(key, sizeof key, "bad_%g", (double)thr[t]);
+        json_number(f, key, (double)blk[S2M2_EVAL_BAD + t] / n, ", ");
+    }
+    json_number(f, "d1", (double)blk[S2M2_EVAL_D1_BAD] / n, "");
+}
+
+// upper edge in px of the histogram bin where the cumulative count first reaches p * n; inf for the overflow bin, NaN without pixels
+static double eval_quantile(const unsigned long long* hist, double p) {
+    unsigned long long n = 0, cum = 0;
+    for (int i = 0; i < S2M2_EVAL_HIST_BINS; ++i) n += hist[i];
+    if (n == 0) return NAN;
+    for (int i = 0; i < S2M2_EVAL_HIST_BINS; ++i) {
+        cum += hist[i];
+        if ((double)cum >= p * (double)n) return i == S2M2_EVAL_HIST_BINS - 1 ? INFINITY : (double)(i + 1) / 64.0;
+    }
+    return INFINITY;
+}
+
 #define HIP_OK(x, what)                              \
     do {                                             \
         if ((x) != hipSuccess) return fail(what);    \
@@ -96,6 +169,8 @@ int main(int argc, char** argv) {
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5;
     int unfiltered = 0;
     int repeat = 0, npos = 0;
+    const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr;
+    double gt_min = 0.0;
     for (int i = 1; i < argc; ++i) {
         if (strcmp(argv[i], "--out") == 0 && i + 1 < argc) out_dir = argv[++i];
         else if (strcmp(argv[i], "--calib") == 0 && i + 1 < argc) calib_path = argv[++i];
@@ -107,6 +182,11 @@ int main(int argc, char** argv) {
         else if (strcmp(argv[i], "--conf-min") == 0 && i + 1 < argc) conf_min = atof(argv[++i]);
         else if (strcmp(argv[i], "--occ-min") == 0 && i + 1 < argc) occ_min = atof(argv[++i]);
         else if (strcmp(argv[i], "--unfiltered") == 0) unfiltered = 1;
+        else if (strcmp(argv[i], "--gt") == 0 && i + 1 < argc) gt_path = argv[++i];
+        else if (strcmp(argv[i], "--gt-region") == 0 && i + 1 < argc) region_path = argv[++i];
+        else if (strcmp(argv[i], "--gt-min") == 0 && i + 1 < argc) gt_min = atof(argv[++i]);
+        else if (strcmp(argv[i], "--thresholds") == 0 && i + 1 < argc) thr_arg = argv[++i];
+        else if (strcmp(argv[i], "--metrics") == 0 && i + 1 < argc) metrics_path = argv[++i];
         else if (strcmp(argv[i], "--repeat") == 0 && i + 1 < argc) repeat = atoi(argv[++i]);
         else if (npos < 3 && argv[i][0] != '-') pos[npos++] = argv[i];
         else return fail(USAGE);
@@ -114,6 +194,42 @@ int main(int argc, char** argv) {
     if (npos != 3 || repeat < 0) return fail(USAGE);
     if ((calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
     if (!calib_path && (image_path || depth_path)) return fail("--image and --depth need --calib and --ply");
+    if ((gt_path == nullptr) != (metrics_path == nullptr)) return fail("--gt and --metrics come together");
+    if (!gt_path && (region_path || thr_arg)) return fail("--gt-region and --thresholds need --gt and --metrics");
+    // the ground truth is parsed and validated here, before the engine is loaded and anything touches the device
+    std::vector<float> hgt;
+    std::vector<unsigned char> hregion;
+    int gt_w = 0, gt_rows = 0, nthr = 4;
+    float thr[S2M2_EVAL_MAX_THR] = {0.5f, 1.f, 2.f, 4.f, 0.f, 0.f, 0.f, 0.f};
+    if (gt_path) {
+        const char* why = "";
+        if (!read_pfm(gt_path, hgt, gt_w, gt_rows, why)) {
+            fprintf(stderr, "s2m2_run_engine: --gt %s: %s\n", gt_path, why);
+            return 1;
+        }
+        if (region_path) {
+            hregion.resize(hgt.size());
+            FILE* f = fopen(region_path, "rb");
+            const bool ok = f && fread(hregion.data(), 1, hregion.size(), f) == hregion.size() && fgetc(f) == EOF;
+            if (f) fclose(f);
+            if (!ok) {
+                fprintf(stderr, "s2m2_run_engine: --gt-region must be a raw uint8 file of the ground truth's %d x %d pixels\n", gt_w, gt_rows);
+                return 1;
+            }
+        }
+        if (thr_arg) {
+            nthr = 0;
+            for (const char* c = thr_arg; *c;) {
+                char* end = nullptr;
+                const float t = strtof(c, &end);
+                if (end == c || nthr == S2M2_EVAL_MAX_THR || !(t > (nthr ? thr[nthr - 1] : 0.f)) || !isfinite(t) || (*end && *end != ','))
+                    return fail("--thresholds: up to 8 numbers > 0, strictly increasing, separated by commas");
+                thr[nthr++] = t;
+                c = *end ? end + 1 : end;
+            }
+        }
+        if (gt_min != gt_min) return fail("--gt-min: not a number");
+    }
     if (s2m2_version() != S2M2_ABI_VERSION) return fail("libs2m2_hip.so was built from another ABI version than this program");
 
     s2m2_engine* eng = nullptr;
@@ -121,6 +237,11 @@ int main(int argc, char** argv) {
     s2m2_engine_info m;
     s2m2_engine_meta(eng, &m);
     if (m.image_dtype != S2M2_F32) return fail("this program feeds float32 images; the engine takes another image dtype");
+    if (gt_path && (gt_rows % m.B != 0 || gt_rows / m.B > m.out_h || gt_w > m.out_w)) {
+        fprintf(stderr, "s2m2_run_engine: --gt is %d x %d pixels; the engine needs B = %d stacked ground truths of at most %d x %d\n", gt_w, gt_rows,
+                m.B, m.out_w, m.out_h);
+        return 1;
+    }
     const size_t img = (size_t)m.B * 3 * m.H * m.W, map = (size_t)m.B * m.out_h * m.out_w;
     std::vector<float> hl(img), hr(img);
     if (!read_raw(pos[1], hl) || !read_raw(pos[2], hr)) {
@@ -239,6 +360,81 @@ int main(int argc, char** argv) {
         (void)hipFree(dws);
         (void)hipFree(dcount);
         (void)hipFree(ddepth);
+    }
+    if (gt_path) {
+        const int gt_h = gt_rows / m.B;
+        float* dgt = nullptr;
+        unsigned char* dregion = nullptr;
+        void* dws = nullptr;
+        unsigned long long* dstats = nullptr;
+        const size_t ws_bytes = s2m2_eval_workspace_bytes(m.B, gt_h, gt_w), nwords = (size_t)m.B * S2M2_EVAL_WORDS;
+        if (ws_bytes == 0) return fail("--gt: extents too large");
+        HIP_OK(hipMalloc((void**)&dgt, hgt.size() * sizeof(float)), "hipMalloc");
+        HIP_OK(hipMemcpy(dgt, hgt.data(), hgt.size() * sizeof(float), hipMemcpyHostToDevice), "upload");
+        if (region_path) {
+            HIP_OK(hipMalloc((void**)&dregion, hregion.size()), "hipMalloc");
+            HIP_OK(hipMemcpy(dregion, hregion.data(), hregion.size(), hipMemcpyHostToDevice), "upload");
+        }
+        HIP_OK(hipMalloc(&dws, ws_bytes), "hipMalloc");
+        HIP_OK(hipMalloc((void**)&dstats, nwords * sizeof(unsigned long long)), "hipMalloc");
+        s2m2_eval_desc ed;
+        memset(&ed, 0, sizeof ed);
+        ed.disp = dout[0]; ed.occ = dout[1]; ed.conf = dout[2];
+        ed.gt = dgt; ed.region = dregion; ed.workspace = dws; ed.stats = dstats;
+        ed.B = m.B; ed.H = gt_h; ed.W = gt_w; ed.Hp = m.out_h; ed.Wp = m.out_w;
+        ed.nthr = nthr;
+        for (int t = 0; t < nthr; ++t) ed.thr[t] = thr[t];
+        ed.d1_abs = 3.f; ed.d1_rel = 0.05f;
+        ed.gt_min = (float)gt_min; ed.conf_min = (float)conf_min; ed.occ_min = (float)occ_min;
+        if (s2m2_disp_eval(&ed, s) != 0) return fail_lib("s2m2_disp_eval failed");
+        HIP_OK(hipStreamSynchronize(s), "s2m2_disp_eval");
+        std::vector<unsigned long long> hs(nwords);
+        HIP_OK(hipMemcpy(hs.data(), dstats, nwords * sizeof(unsigned long long), hipMemcpyDeviceToHost), "download");
+        FILE* f = fopen(metrics_path, "w");
+        if (!f) return fail("cannot write the metrics");
+        fprintf(f, "{\"B\": %d, \"H\": %d, \"W\": %d, \"gt_min\": ", m.B, gt_h, gt_w);
+        if (isfinite(gt_min)) fprintf(f, "%.9g", gt_min);
+        else fprintf(f, "null");
+        fprintf(f, ", \"conf_min\": %.9g, \"occ_min\": %.9g, \"thresholds\": [", conf_min, occ_min);
+        for (int t = 0; t < nthr; ++t) fprintf(f, "%s%.9g", t ? ", " : "", (double)thr[t]);
+        fprintf(f, "],\n \"pairs\": [");
+        for (int b = 0; b < m.B; ++b) {
+            const unsigned long long* w = hs.data() + (size_t)b * S2M2_EVAL_WORDS;
+            fprintf(f, "%s\n  {", b ? "," : "");
+            json_block(f, w + S2M2_EVAL_ALL, thr, nthr);
+            fprintf(f, ", ");
+            json_number(f, "a50", eval_quantile(w + S2M2_EVAL_HIST, 0.5), ", ");
+            json_number(f, "a90", eval_quantile(w + S2M2_EVAL_HIST, 0.9), ", ");
+            json_number(f, "a95", eval_quantile(w + S2M2_EVAL_HIST, 0.95), ", ");
+            json_number(f, "a99", eval_quantile(w + S2M2_EVAL_HIST, 0.99), ", ");
+            json_number(f, "density", (double)w[S2M2_EVAL_KEPT + S2M2_EVAL_N_EVAL] / (double)w[S2M2_EVAL_ALL + S2M2_EVAL_N_EVAL], ",\n   ");
+            fprintf(f, "\"kept\": {");
+            json_block(f, w + S2M2_EVAL_KEPT, thr, nthr);
+            fprintf(f, "},\n   \"words\": [");
+            for (int i = 0; i < S2M2_EVAL_WORDS; ++i) fprintf(f, "%s%llu", i ? ", " : "", w[i]);
+            fprintf(f, "]}");
+        }
+        fprintf(f, "\n ]}\n");
+        if (fclose(f) != 0) return fail("cannot write the metrics");
+        if (repeat > 0) {
+            hipEvent_t t0, t1;
+            HIP_OK(hipEventCreate(&t0), "hipEventCreate");
+            HIP_OK(hipEventCreate(&t1), "hipEventCreate");
+            HIP_OK(hipEventRecord(t0, s), "hipEventRecord");
+            for (int i = 0; i < repeat; ++i)
+                if (s2m2_disp_eval(&ed, s) != 0) return fail_lib("s2m2_disp_eval failed");
+            HIP_OK(hipEventRecord(t1, s), "hipEventRecord");
+            HIP_OK(hipEventSynchronize(t1), "timed evaluation runs");
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, t0, t1), "hipEventElapsedTime");
+            printf("{\"eval_pixels\": %llu, \"repeat\": %d, \"eval_us_per_pair\": %.2f}\n", hs[S2M2_EVAL_N_EVAL], repeat, 1000.f * ms / repeat / m.B);
+            (void)hipEventDestroy(t0);
+            (void)hipEventDestroy(t1);
+        }
+        (void)hipFree(dgt);
+        (void)hipFree(dregion);
+        (void)hipFree(dws);
+        (void)hipFree(dstats);
     }
     s2m2_engine_destroy(eng);
     for (auto& p : dout) (void)hipFree(p);

@@ -128,6 +128,23 @@ RECTIFY_SRC_U8_HWC, RECTIFY_SRC_U8_CHW, RECTIFY_SRC_F32_CHW = 0, 1, 2
 RECTIFY_ORDER_SAMPLE, RECTIFY_ORDER_TILE = 0, 1
 RECTIFY_REC_SRC, RECTIFY_REC_IR, RECTIFY_REC_FX, RECTIFY_REC_K1, RECTIFY_RECORD_FLOATS = 0, 1, 10, 14, 20
 
+EVAL_MAX_THR, EVAL_HIST_BINS, EVAL_CONF_BINS = 8, 1025, 64
+
+
+class EvalDesc(ctypes.Structure):
+    """mirror of s2m2_eval_desc (include/s2m2_hip.h): K18, disparity error statistics against ground truth"""
+    _fields_ = [("disp", _vp), ("occ", _vp), ("conf", _vp), ("gt", _vp), ("region", _vp), ("workspace", _vp), ("stats", _vp),
+                ("B", _i), ("H", _i), ("W", _i), ("Hp", _i), ("Wp", _i), ("nthr", _i), ("thr", ctypes.c_float * EVAL_MAX_THR),
+                ("d1_abs", ctypes.c_float), ("d1_rel", ctypes.c_float), ("gt_min", ctypes.c_float), ("conf_min", ctypes.c_float),
+                ("occ_min", ctypes.c_float)]
+
+
+# the stat block of s2m2_disp_eval in 64-bit words (include/s2m2_hip.h: S2M2_EVAL_*): word offsets inside the ALL / KEPT blocks and inside a
+# row of the confidence table, then the offsets of the four blocks
+EVAL_N_REGION, EVAL_N_EVAL, EVAL_N_NONFINITE, EVAL_SUM_ABS_Q, EVAL_SUM_SQ_Q, EVAL_D1_BAD, EVAL_BAD, EVAL_BLOCK_WORDS = 0, 1, 2, 3, 4, 5, 6, 14
+EVAL_CONF_COUNT, EVAL_CONF_SUM_ABS_Q, EVAL_CONF_BAD, EVAL_CONF_ROW_WORDS = 0, 1, 2, 10
+EVAL_ALL, EVAL_KEPT, EVAL_HIST, EVAL_CONF, EVAL_WORDS = 0, 14, 28, 1053, 1693
+
 # name -> (restype, argtypes); must list every symbol declared in include/s2m2_hip.h
 ABI_VERSION = 800                     # include/s2m2_hip.h: S2M2_ABI_VERSION (checked in load())
 
@@ -197,6 +214,9 @@ SIGNATURES = {
     "s2m2_cloud_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_cloud": (_i, [ctypes.POINTER(CloudDesc), _vp]),
     "s2m2_rectify": (_i, [ctypes.POINTER(RectifyDesc), _vp]),
+    "s2m2_eval_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_eval_tile_rows": (_i, [_i, _i]),
+    "s2m2_disp_eval": (_i, [ctypes.POINTER(EvalDesc), _vp]),
 }
 
 
@@ -1223,3 +1243,5 @@ def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, map
 
 # K17 (s2m2_conv_gru): its wrapper lives in hip_gru.py and is re-exported here, so callers write hip.conv_gru like every other launch
 from .hip_gru import conv_gru, conv_gru_supported  # noqa: E402,F401
+# K18 (s2m2_disp_eval): likewise in hip_eval.py
+from .hip_eval import disp_eval, eval_tile_rows, eval_workspace_bytes  # noqa: E402,F401

@@ -14,6 +14,8 @@ image_utils.py) -- SURVEY.md section 8f rows 1-2: same names, arguments and retu
   ``create_delta_rotation``, ``apply_delta_rotation``, ``build_camera_matrix``, ``compute_stereo_rectification`` (calib_utils.py),
   ``rectify_images`` (image_utils.py:108-136), ``evaluate_sample`` (calibration/base.py), ``cem_calibration`` (calibration/cem.py) and
   ``rectify_population`` -- lives in ``s2m2_amd.rectify`` (HIP kernel ``s2m2_rectify``) and is re-exported here
+* ``evaluate``             no counterpart in the reference (its numbers come from benchmark servers): disparity error statistics against
+  ground truth on the device -- lives in ``s2m2_amd.evaluate`` (HIP kernel ``s2m2_disp_eval``) and is re-exported here
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import hip
+from .evaluate import evaluate  # noqa: F401  (re-export)
 from .model import S2M2
 from .rectify import (apply_delta_rotation, build_camera_matrix, cem_calibration, compute_stereo_rectification,  # noqa: F401  (re-exports)
                       create_delta_rotation, euler_to_rotation_matrix, evaluate_sample, load_calibration_data, parse_xml_calibration,
