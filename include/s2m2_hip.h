@@ -489,6 +489,40 @@ int s2m2_conv_gru_supported(int C, int H, int W, int dtype);
 int s2m2_conv_gru(const s2m2_convgru_desc* desc, void* stream);
 
 /*
+ * K19 -- the second half of a ConvBlock2D (attentions.py:255-281) in ONE launch, for the grids K14 does not take (ABI still 800: additive):
+ *     out = fp16( fp16(convs.2(t) + b_conv2) + fp16(convs_1x.2( fp16(ReLU(convs_1x.0(z) + b_1x0)) ) + b_1x2) )
+ *   t = GELU(convs.0(z)) comes from the unchanged s2m2_conv2d launch.  Replaces the launch pair s2m2_mlp_chain (the two-stage 1x1 branch,
+ *   weight_frag = 1) / s2m2_conv2d (korder 2, S2M2_EPI_ADD on the chain's output) with the same arithmetic in the same order (bit-identical):
+ *   the 1x1 branch needs no halo, so the block that will add it computes it on its own patch in front of the 3x3 layer's K loop.
+ *     t, z, out   (N, H, W, C) fp16, channels contiguous, 16-byte aligned, pixel strides in elements (at least C, multiples of 8); out must
+ *                 not overlap t or z
+ *     w_conv2     the 3x3 layer as s2m2_conv_desc.weight with korder = 2 (s2m2_pack_frag S2M2_PACK_CONV_FRAG, 128-channel chunks)
+ *     w_1x0/2     the 1x1 layers as s2m2_chain_desc.weight with weight_frag = 1 (S2M2_PACK_ROWS)
+ *     b_*         fp32 (C) or NULL
+ *     patch_rows x patch_cols   0 x 0 = the library's choice (csrc/convtail_select.h); 2 x 32, 4 x 32, 4 x 40 force the block's pixel patch
+ *   fp16, C = 128 / 256: ask s2m2_conv_block_tail_supported.
+ */
+typedef struct s2m2_convtail_desc {
+    const void* t;
+    long long t_stride;
+    const void* z;
+    long long z_stride;
+    void* out;
+    long long out_stride;
+    int N, H, W, C;
+    const void* w_conv2;
+    const void* w_1x0;
+    const void* w_1x2;
+    const float* b_conv2;
+    const float* b_1x0;
+    const float* b_1x2;
+    int patch_rows, patch_cols;
+    int dtype;
+} s2m2_convtail_desc;
+int s2m2_conv_block_tail_supported(int C, int H, int W, int dtype);
+int s2m2_conv_block_tail(const s2m2_convtail_desc* desc, void* stream);
+
+/*
  * K11 -- a 1x1 layer with any channel counts in the direct style (fp16; round 4): Conv2d(kernel 1) / Linear / ConvTranspose2d(2, stride 2) on
  *   up to four channel-concatenated sources (reference: LocalRefiner's corr_feat / conf_occ_feat / disp_corr_ctx_cat 1x1 layers,
  *   refinenet.py:87-106,138-146; the up_conv 1x1 layers of Unet / MRT on the coarse grid, unet.py:32-37, stacked_MRT.py:29-34; the

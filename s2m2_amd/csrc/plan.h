@@ -129,6 +129,9 @@ S2M2_PLAN_PTRS(s2m2_convblock_desc, S2M2_OFF(s2m2_convblock_desc, x), S2M2_OFF(s
 S2M2_PLAN_PTRS(s2m2_convgru_desc, S2M2_OFF(s2m2_convgru_desc, h), S2M2_OFF(s2m2_convgru_desc, x), S2M2_OFF(s2m2_convgru_desc, out),
                S2M2_OFF(s2m2_convgru_desc, w_zr), S2M2_OFF(s2m2_convgru_desc, w_q), S2M2_OFF(s2m2_convgru_desc, b_zr),
                S2M2_OFF(s2m2_convgru_desc, b_q))
+S2M2_PLAN_PTRS(s2m2_convtail_desc, S2M2_OFF(s2m2_convtail_desc, t), S2M2_OFF(s2m2_convtail_desc, z), S2M2_OFF(s2m2_convtail_desc, out),
+               S2M2_OFF(s2m2_convtail_desc, w_conv2), S2M2_OFF(s2m2_convtail_desc, w_1x0), S2M2_OFF(s2m2_convtail_desc, w_1x2),
+               S2M2_OFF(s2m2_convtail_desc, b_conv2), S2M2_OFF(s2m2_convtail_desc, b_1x0), S2M2_OFF(s2m2_convtail_desc, b_1x2))
 S2M2_PLAN_PTRS(s2m2_pw_desc, S2M2_OFF_I(s2m2_pw_desc, src, 0), S2M2_OFF_I(s2m2_pw_desc, src, 1), S2M2_OFF_I(s2m2_pw_desc, src, 2),
                S2M2_OFF_I(s2m2_pw_desc, src, 3), S2M2_OFF(s2m2_pw_desc, weight_frag), S2M2_OFF(s2m2_pw_desc, bias), S2M2_OFF(s2m2_pw_desc, out))
 S2M2_PLAN_PTRS(s2m2_narrow_desc, S2M2_OFF(s2m2_narrow_desc, x), S2M2_OFF(s2m2_narrow_desc, x1), S2M2_OFF(s2m2_narrow_desc, weight_frag),

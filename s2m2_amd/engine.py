@@ -190,6 +190,11 @@ class Engine:
         # S2M2_GRU_FUSE=0 (A/B): every ConvGRU half as two launches (stacked z | r, candidate layer) instead of ONE K17 launch (hip.conv_gru: fp16,
         # hidden and input width 128 -- the S model; profiles/r08/ab_gru_fuse.txt)
         self.gru_fuse = os.environ.get("S2M2_GRU_FUSE", "1") != "0"
+        # S2M2_CB_TAIL=0 (A/B): a ConvBlock2D above K14's grids as three launches (K9 chain, convs.0, convs.2 + residual) instead of convs.0 and
+        # ONE K19 launch for the rest (hip.conv_block_tail: fp16, C = 128 / 256; profiles/r09/ab_cb_tail.txt)
+        self.cb_tail = os.environ.get("S2M2_CB_TAIL", "1") != "0"
+        # S2M2_CB_TAIL_C256=1 (A/B): K19 at C = 256 too (the 1/16 level: a wash inside the forward, profiles/r09/README.md)
+        self.cb_tail_c256 = os.environ.get("S2M2_CB_TAIL_C256", "0") == "1"
         self._tokens_normed: Optional[Tensor] = None             # DispInit's LayerNorm of feature_tr_4x, written by the last K9 launch
         self.ln_w = self.p["disp_init.layer_norm.weight"].contiguous()
         self.ln_b = self.p["disp_init.layer_norm.bias"].contiguous()
@@ -352,6 +357,13 @@ class Engine:
             if k0.frag_3x3(c) and k2.frag_3x3(c) and c0.plain_1x1(c, c) and c2.plain_1x1(c, c):
                 # the whole block -- 1x1 branch, 3x3 - GELU - 3x3, the final add -- as ONE K14 launch (the coarse grids: latency chains)
                 return hip.conv_block(z, k0.weight, k0.bias, k2.weight, k2.bias, c0.chain_frag, c0.bias, c2.chain_frag, c2.bias)
+        if (self.cb_tail and same and z.dim() == 4 and (c == 128 or self.cb_tail_c256) and self.chain_frag_ok(c)
+                and self.cb_tail_ok(c, z.shape[1], z.shape[2])):
+            k0, k2 = self.std(p + ".convs.0"), self.std(p + ".convs.2")
+            if k0.frag_3x3(c) and k2.frag_3x3(c) and c0.plain_1x1(c, c) and c2.plain_1x1(c, c):
+                # convs.0 as it was; the 1x1 branch in front of convs.2's K loop, ONE K19 launch: its output never exists in memory
+                t = self.cconv(k0, [z], act=hip.ACT_GELU)
+                return hip.conv_block_tail(t, z, k2.weight, k2.bias, c0.chain_frag, c0.bias, c2.chain_frag, c2.bias)
         if same and self.chain_frag_ok(c):                         # the 1x1 branch as one K9 launch (direct form)
             b = hip.mlp_chain(z, [c0.stage(hip.ACT_RELU), c2.stage(hip.ACT_NONE)], frag=True)
         elif same and self.chain_ok(c):
@@ -449,6 +461,10 @@ class Engine:
     def gru_fuse_ok(self, c: int, h: int, w: int) -> bool:
         """K17 takes a ConvGRU half of this width on this grid (a binding without the entry: no)"""
         return getattr(hip, "conv_gru_supported", None) is not None and self.supported("conv_gru", c, h, w)
+
+    def cb_tail_ok(self, c: int, h: int, w: int) -> bool:
+        """K19 takes the second half of a ConvBlock2D of this width on this grid (a binding without the entry: no)"""
+        return getattr(hip, "conv_block_tail_supported", None) is not None and self.supported("conv_block_tail", c, h, w)
 
     def convblock_ok(self, c: int, h: int, w: int) -> bool:
         """K14 takes a ConvBlock2D of this width on this grid"""

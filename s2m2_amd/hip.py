@@ -66,6 +66,13 @@ class ConvGruDesc(ctypes.Structure):
                 ("C", _i), ("KH", _i), ("KW", _i), ("w_zr", _vp), ("w_q", _vp), ("b_zr", _vp), ("b_q", _vp), ("dtype", _i)]
 
 
+class ConvTailDesc(ctypes.Structure):
+    """mirror of s2m2_convtail_desc (include/s2m2_hip.h): K19, the second half of a ConvBlock2D per launch"""
+    _fields_ = [("t", _vp), ("t_stride", _ll), ("z", _vp), ("z_stride", _ll), ("out", _vp), ("out_stride", _ll), ("N", _i), ("H", _i), ("W", _i),
+                ("C", _i), ("w_conv2", _vp), ("w_1x0", _vp), ("w_1x2", _vp), ("b_conv2", _vp), ("b_1x0", _vp), ("b_1x2", _vp), ("patch_rows", _i),
+                ("patch_cols", _i), ("dtype", _i)]
+
+
 class PwDesc(ctypes.Structure):
     """mirror of s2m2_pw_desc (include/s2m2_hip.h)"""
     _fields_ = [("src", _vp * 4), ("src_c", _i * 4), ("src_stride", _ll * 4), ("nsrc", _i), ("rows", _ll), ("weight_frag", _vp), ("bias", _vp),
@@ -187,6 +194,8 @@ SIGNATURES = {
     "s2m2_conv_block": (_i, [ctypes.POINTER(ConvBlockDesc), _vp]),
     "s2m2_conv_gru_supported": (_i, [_i, _i, _i, _i]),
     "s2m2_conv_gru": (_i, [ctypes.POINTER(ConvGruDesc), _vp]),
+    "s2m2_conv_block_tail_supported": (_i, [_i, _i, _i, _i]),
+    "s2m2_conv_block_tail": (_i, [ctypes.POINTER(ConvTailDesc), _vp]),
     "s2m2_row_attn_supported": (_i, [_i, _i, _i, _i]),
     "s2m2_row_attn": (_i, [ctypes.POINTER(RowAttnDesc), _vp]),
     "s2m2_feature_fusion_supported": (_i, [_i, _i]),
@@ -1245,3 +1254,6 @@ def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, map
 from .hip_gru import conv_gru, conv_gru_supported  # noqa: E402,F401
 # K18 (s2m2_disp_eval): likewise in hip_eval.py
 from .hip_eval import disp_eval, eval_tile_rows, eval_workspace_bytes  # noqa: E402,F401
+
+# K19 (s2m2_conv_block_tail): likewise, from hip_tail.py
+from .hip_tail import conv_block_tail, conv_block_tail_supported  # noqa: E402,F401

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build-time guard of the scheduling assumptions behind K5 v5 (conv_frag_kernel, s2m2_amd/csrc/conv.hip), K14 (conv_block_kernel, convblock.hip: the
-same ring, check_ring_kernel), K17 (conv_gru_kernel, convgru.hip: likewise), the direct form of K10
+same ring, check_ring_kernel), K17 (conv_gru_kernel, convgru.hip: likewise), K19 (conv_tail_kernel, convtail.hip: likewise), the direct form of K10
 (feature_fusion_direct_kernel, s2m2_amd/csrc/fusion.hip) and the shipped K1 (ln_corr_kernel<PRENORM>, s2m2_amd/csrc/ln_corr.hip: s2m2_corr).
 
 The kernel prefetches its weight fragments with loads the compiler does NOT track (common.h: global_load16_async) and waits for them with
@@ -299,7 +299,8 @@ def main() -> int:
         ntext = compile_asm(os.path.join(ROOT, "s2m2_amd", "csrc", "conv_narrow.hip"), os.path.join(td, "conv_narrow.s"))
         btext = compile_asm(os.path.join(ROOT, "s2m2_amd", "csrc", "convblock.hip"), os.path.join(td, "convblock.s"))
         gtext = compile_asm(os.path.join(ROOT, "s2m2_amd", "csrc", "convgru.hip"), os.path.join(td, "convgru.s"))
-        if text is None or ftext is None or ktext is None or ntext is None or btext is None or gtext is None:
+        ttext = compile_asm(os.path.join(ROOT, "s2m2_amd", "csrc", "convtail.hip"), os.path.join(td, "convtail.s"))
+        if text is None or ftext is None or ktext is None or ntext is None or btext is None or gtext is None or ttext is None:
             return 2
     bad = check_ln_corr(ktext)
     bfuncs = functions(btext, "_ZN4s2m217conv_block_kernel")
@@ -319,6 +320,15 @@ def main() -> int:
         p1, nloops, starts = check_ring_kernel(name, lines)
         taps = "3x1" if "GruCfgILb1E" in name else "1x3"
         print(f"check_isa: conv_gru_kernel<{taps}>: {starts} ring (re)start window(s), {len(p1)} problem(s) (its K loops are held bit for bit against K5 v5 by tests/test_hip_conv_gru.py)")
+        bad += p1
+    tfuncs = functions(ttext, "_ZN4s2m216conv_tail_kernel")
+    if not tfuncs:
+        print("check_isa: no conv_tail_kernel instantiation found in the assembly")
+        return 1
+    for name, lines in tfuncs.items():
+        p1, nloops, starts = check_ring_kernel(name, lines)
+        m = re.search(r"CtCfgILi(\d+)ELi(\d+)ELi(\d+)E", name)
+        print(f"check_isa: conv_tail_kernel<C {m.group(1)}, {m.group(2)}x{m.group(3)}>: {starts} ring (re)start window(s), {len(p1)} problem(s) (its K loop is held bit for bit against K5 v5 by tests/test_hip_convtail.py)")
         bad += p1
     nfuncs = functions(ntext, "_ZN4s2m218conv_narrow_kernel")
     if not nfuncs:
