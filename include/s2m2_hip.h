@@ -43,7 +43,8 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * the forward): purely additive -- no existing struct or entry point changes, engine files do not contain the stage -- so neither callers nor
  * engine files of 800 are invalidated.  A library built before K16 reports 800 as well and lacks the symbol: s2m2_amd/hip.py load() names the
  * missing symbol and asks for a rebuild.  Still 800 with s2m2_disp_eval, s2m2_eval_workspace_bytes, s2m2_eval_tile_rows and s2m2_eval_desc (K18, the
- * evaluation stage behind the forward), added the same way. */
+ * evaluation stage behind the forward), added the same way, and with s2m2_mesh, s2m2_mesh_workspace_bytes, s2m2_mesh_tile_rows and s2m2_mesh_desc
+ * (K20, the surface mesh behind the 3D stage). */
 #define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
@@ -906,6 +907,59 @@ typedef struct s2m2_eval_desc {
 size_t s2m2_eval_workspace_bytes(int B, int H, int W);      /* 0: bad extents */
 int s2m2_eval_tile_rows(int H, int W);                      /* image rows of one tile of launch A; 0: bad extents */
 int s2m2_disp_eval(const s2m2_eval_desc* desc, void* stream);
+
+/*
+ * K20 -- the surface mesh behind the 3D stage: K15's point cloud plus the triangles that connect neighbouring pixels, on the device.  The
+ *   reference's demos stop at open3d point clouds (demo/visualize_3d_middlebury.py:32-52,97-107, demo/visualize_3d_booster.py); like K18 this
+ *   stage has no counterpart there: the semantics are defined here and pinned by the numpy oracle of tests/mesh_oracle.py.
+ *   `cloud` holds exactly the fields of s2m2_cloud, with their meaning: the padded maps, the unpadded image, the fused crop, camera and filter
+ *   parameters, depth, mask, records, count, capacity, workspace.  keep, z, x, y and the colour bytes of a pixel are K15's, formula for formula.
+ *   Vertices: the vertices of pair b are its kept pixels in raster order.  records and count are BYTE-IDENTICAL to what s2m2_cloud writes for
+ *     the same descriptor fields (both kernels compile the same device functions).  Every kept pixel is a vertex, also one no face references.
+ *   Edges: with d the value of the disp map at a pixel (the map's own value, not the filter's -1), two pixels p, q are JOINED iff
+ *       keep(p) && keep(q) && fabsf(d_p - d_q) <= (float)max_jump
+ *     one fp32 subtraction: exact, and contraction cannot touch it.  A comparison with NaN is false (inf - inf is NaN: not joined).  max_jump
+ *     is in full-resolution pixels.
+ *   Faces: every quad with top-left pixel (v,u), 0 <= v < H-1, 0 <= u < W-1, and corners a=(v,u), b=(v,u+1), c=(v+1,u), e=(v+1,u+1):
+ *     all four kept:  if fabsf(d_a - d_e) <= fabsf(d_b - d_c) (a tie goes this way; false with a NaN) the diagonal is a-e and the candidates
+ *                     are (a,c,e) then (a,e,b); otherwise the diagonal is b-c and the candidates are (a,c,b) then (b,c,e)
+ *     exactly three kept: one candidate, the triangle of those three in the winding above: e missing (a,c,b), a missing (b,c,e), b missing
+ *                     (a,c,e), c missing (a,e,b)
+ *     fewer than three kept: none
+ *     A candidate is emitted iff all three of its edges are joined.  All listed windings face the camera: the normal points towards -z in the
+ *     camera frame (x right, y down).  Faces of a pair are stored in raster order of their quad, within a quad in the order listed; a face is
+ *     three int32 vertex ranks (indices into the pair's records).
+ *   outputs, beyond K15's depth, mask, records and count (unchanged in meaning):
+ *     face_count (B) int32: the number of faces of every pair -- ALWAYS the true number, also above face_capacity.  Non-NULL requests the mesh
+ *                and requires count, image and workspace (>= s2m2_mesh_workspace_bytes(B, H, W) bytes, 4-byte aligned).  NULL: the call is
+ *                s2m2_cloud(&desc->cloud, stream) and faces / index are ignored
+ *     faces      (B, face_capacity, 3) int32 at faces + b * face_capacity * 3.  Faces with rank >= face_capacity are not stored; memory beyond
+ *                min(face_count, face_capacity) faces is left untouched.  May be NULL with face_capacity = 0.  The indices are true vertex
+ *                ranks even when count > capacity (they then reference vertices that were not stored: the caller compares)
+ *     index      optional (B,1,H,W) int32: the vertex rank of a kept pixel, -1 otherwise
+ *   Three launches, no host step, no atomics, no waiting between blocks: bit-reproducible.  Launch A: a block takes a fixed tile of
+ *   s2m2_mesh_tile_rows(H, W) whole image rows and reads one halo row below it, writes the dense outputs, one vertex count and one face count
+ *   per tile into the workspace.  Launch B: K15's scatter, which also stores the rank of every pixel into the dense rank map (index, or the
+ *   workspace).  Launch C: a block sums the face counts of the tiles before its own, applies the face rule again to disp and the rank map,
+ *   ranks the two candidate slots of every quad with wave ballots and stores each face as one 12-byte record: ranks run by lane, then by
+ *   quad and slot inside a lane, so a thread writes its up to eight faces back to back and the faces of a wave's step fill one contiguous
+ *   range (as K15's records do).  Thread -> pixel map and 16-byte map loads as in K15.
+ *   Launch plans: s2m2_mesh is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing; the
+ *   stage runs after s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ *   Errors (before any device call): everything s2m2_cloud checks, face_count without count, H * W >= 2^30, negative face_capacity, faces NULL
+ *   with face_capacity > 0, faces / face_count / index not 4-byte aligned, max_jump negative or NaN (+inf is allowed: every kept pair is joined).
+ */
+typedef struct s2m2_mesh_desc {
+    s2m2_cloud_desc cloud;
+    void* faces;
+    int32_t* face_count;
+    int32_t* index;
+    long long face_capacity;   /* faces per pair */
+    double max_jump;
+} s2m2_mesh_desc;
+size_t s2m2_mesh_workspace_bytes(int B, int H, int W);      /* 0: bad extents */
+int s2m2_mesh_tile_rows(int H, int W);                      /* image rows of one tile of all three launches; 0: bad extents */
+int s2m2_mesh(const s2m2_mesh_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

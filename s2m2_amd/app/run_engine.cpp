@@ -13,6 +13,10 @@
 // --ply: a binary little-endian PLY (x y z float, red green blue alpha uchar; the device records verbatim).  B > 1: one file per pair,
 //   OUT.<b>.ply (a trailing ".ply" of OUT is dropped first).  --depth: raw float32 (B,1,H,W) metric depth, 0 where no point was kept.
 // With --repeat the cloud stage is timed as well (HIP events around N calls) and its microseconds per pair printed on a line of its own.
+// --mesh OUT.ply [--max-jump X]: the surface mesh (s2m2_mesh) -- the same vertices plus "element face" / "property list uchar int vertex_indices":
+//   the triangles between neighbouring kept pixels whose disparities differ by at most X px (default 1; "inf": every kept neighbour).  Needs
+//   --calib, honours every option above, names its files like --ply for B > 1, and may be given next to --ply or instead of it.  With
+//   --repeat: {"mesh_vertices", "mesh_faces", "repeat", "mesh_us_per_pair"} on a line of its own.
 //
 // Evaluation against ground truth (s2m2_disp_eval on the device buffers of the run; without --gt nothing below happens):
 //   --gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] [--thresholds a,b,c] [--conf-min X] [--occ-min X] --metrics OUT.json
@@ -38,7 +42,7 @@
 
 static const char* USAGE =
     "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
-    "[--conf-min X] [--occ-min X] [--unfiltered] --ply OUT.ply [--depth OUT.f32]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]";
 
 static int fail(const char* what) {
@@ -96,6 +100,30 @@ static bool write_ply(const std::string& path, const void* records, long long n)
                "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nend_header\n", n);
     const bool ok = fwrite(records, 16, (size_t)n, f) == (size_t)n;
     return fclose(f) == 0 && ok;
+}
+
+// the same vertices, then every face as a count byte (3) and three little-endian int32 vertex indices: 13 bytes
+static bool write_ply_mesh(const std::string& path, const void* records, long long n, const int32_t* faces, long long nf) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face %lld\n"
+               "property list uchar int vertex_indices\nend_header\n", n, nf);
+    std::vector<unsigned char> disk((size_t)nf * 13);
+    for (long long i = 0; i < nf; ++i) {
+        disk[(size_t)i * 13] = 3;
+        memcpy(&disk[(size_t)i * 13 + 1], faces + i * 3, 12);
+    }
+    const bool ok = fwrite(records, 16, (size_t)n, f) == (size_t)n && fwrite(disk.data(), 13, (size_t)nf, f) == (size_t)nf;
+    return fclose(f) == 0 && ok;
+}
+
+// OUT.ply, or OUT.<b>.ply for engines of more than one pair (a trailing ".ply" of OUT is dropped first)
+static std::string pair_path(const char* out, int B, int b) {
+    std::string stem = out;
+    if (B <= 1) return stem;
+    if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".ply") == 0) stem.resize(stem.size() - 4);
+    return stem + "." + std::to_string(b) + ".ply";
 }
 
 // greyscale PFM: "Pf", "width height", "scale" (negative: little-endian), then the rows bottom to top -> rows top to bottom
@@ -165,7 +193,9 @@ static double eval_quantile(const unsigned long long* hist, double p) {
 int main(int argc, char** argv) {
     const char* pos[3] = {nullptr, nullptr, nullptr};
     const char* out_dir = nullptr;
-    const char *calib_path = nullptr, *image_path = nullptr, *ply_path = nullptr, *depth_path = nullptr;
+    const char *calib_path = nullptr, *image_path = nullptr, *ply_path = nullptr, *depth_path = nullptr, *mesh_path = nullptr;
+    const char* max_jump_arg = nullptr;
+    double max_jump = 1.0;
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5;
     int unfiltered = 0;
     int repeat = 0, npos = 0;
@@ -176,6 +206,8 @@ int main(int argc, char** argv) {
         else if (strcmp(argv[i], "--calib") == 0 && i + 1 < argc) calib_path = argv[++i];
         else if (strcmp(argv[i], "--image") == 0 && i + 1 < argc) image_path = argv[++i];
         else if (strcmp(argv[i], "--ply") == 0 && i + 1 < argc) ply_path = argv[++i];
+        else if (strcmp(argv[i], "--mesh") == 0 && i + 1 < argc) mesh_path = argv[++i];
+        else if (strcmp(argv[i], "--max-jump") == 0 && i + 1 < argc) max_jump_arg = argv[++i];
         else if (strcmp(argv[i], "--depth") == 0 && i + 1 < argc) depth_path = argv[++i];
         else if (strcmp(argv[i], "--depth-trunc") == 0 && i + 1 < argc) depth_trunc = atof(argv[++i]);
         else if (strcmp(argv[i], "--depth-scale") == 0 && i + 1 < argc) depth_scale = atof(argv[++i]);
@@ -192,7 +224,14 @@ int main(int argc, char** argv) {
         else return fail(USAGE);
     }
     if (npos != 3 || repeat < 0) return fail(USAGE);
-    if ((calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
+    if (mesh_path && !calib_path) return fail("--calib and --mesh come together");
+    if (!mesh_path && (calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
+    if (max_jump_arg && !mesh_path) return fail("--max-jump needs --mesh");
+    if (max_jump_arg) {
+        char* end = nullptr;
+        max_jump = strtod(max_jump_arg, &end);
+        if (end == max_jump_arg || *end || !(max_jump >= 0.0)) return fail("--max-jump: a number >= 0 (inf is allowed)");
+    }
     if (!calib_path && (image_path || depth_path)) return fail("--image and --depth need --calib and --ply");
     if ((gt_path == nullptr) != (metrics_path == nullptr)) return fail("--gt and --metrics come together");
     if (!gt_path && (region_path || thr_arg)) return fail("--gt-region and --thresholds need --gt and --metrics");
@@ -291,8 +330,9 @@ int main(int argc, char** argv) {
         if (!read_calib(calib_path, cal)) return fail("--calib: cannot read cam0 and baseline from the file");
         if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
         const size_t npix = (size_t)m.H * m.W;
-        void *dimg = nullptr, *drec = nullptr, *dws = nullptr;
-        int32_t* dcount = nullptr;
+        void *dimg = nullptr, *drec = nullptr, *dws = nullptr, *dfaces = nullptr;
+        int32_t *dcount = nullptr, *dfcount = nullptr;
+        const long long fcap = 2LL * (m.H - 1) * (m.W - 1);
         float* ddepth = nullptr;
         if (image_path) {
             std::vector<unsigned char> hi(img);
@@ -306,13 +346,19 @@ int main(int argc, char** argv) {
             HIP_OK(hipMalloc(&dimg, img), "hipMalloc");
             HIP_OK(hipMemcpy(dimg, hi.data(), img, hipMemcpyHostToDevice), "upload");
         }
-        const size_t ws_bytes = s2m2_cloud_workspace_bytes(m.B, m.H, m.W);
+        const size_t ws_bytes = mesh_path ? s2m2_mesh_workspace_bytes(m.B, m.H, m.W) : s2m2_cloud_workspace_bytes(m.B, m.H, m.W);
+        if (ws_bytes == 0) return fail("the 3D outputs: extents too large");
+        if (mesh_path) {
+            HIP_OK(hipMalloc(&dfaces, (size_t)m.B * (fcap > 0 ? fcap : 1) * 12), "hipMalloc");
+            HIP_OK(hipMalloc((void**)&dfcount, m.B * sizeof(int32_t)), "hipMalloc");
+        }
         HIP_OK(hipMalloc(&drec, (size_t)m.B * npix * 16), "hipMalloc");
         HIP_OK(hipMalloc(&dws, ws_bytes), "hipMalloc");
         HIP_OK(hipMalloc((void**)&dcount, m.B * sizeof(int32_t)), "hipMalloc");
         if (depth_path) HIP_OK(hipMalloc((void**)&ddepth, (size_t)m.B * npix * sizeof(float)), "hipMalloc");
-        s2m2_cloud_desc cd;
-        memset(&cd, 0, sizeof cd);
+        s2m2_mesh_desc md;                                   // --mesh: one s2m2_mesh call writes the vertices (the --ply records) and the faces
+        memset(&md, 0, sizeof md);
+        s2m2_cloud_desc& cd = md.cloud;
         cd.disp = dout[0]; cd.occ = dout[1]; cd.conf = dout[2];
         cd.image = image_path ? dimg : dl;
         cd.image_dtype = image_path ? 2 : S2M2_F32;
@@ -322,25 +368,49 @@ int main(int argc, char** argv) {
         cd.capacity = (long long)npix;
         cd.fx = cal.fx; cd.fy = cal.fy; cd.cx = cal.cx; cd.cy = cal.cy; cd.baseline = cal.baseline; cd.doffs = cal.doffs;
         cd.depth_scale = depth_scale; cd.depth_trunc = depth_trunc; cd.conf_min = conf_min; cd.occ_min = occ_min;
-        if (s2m2_cloud(&cd, s) != 0) return fail_lib("s2m2_cloud failed");
+        md.faces = dfaces; md.face_count = dfcount; md.face_capacity = fcap; md.max_jump = max_jump;
+        if (mesh_path) {
+            if (s2m2_mesh(&md, s) != 0) return fail_lib("s2m2_mesh failed");
+        } else if (s2m2_cloud(&cd, s) != 0) return fail_lib("s2m2_cloud failed");
         HIP_OK(hipStreamSynchronize(s), "s2m2_cloud");
-        std::vector<int32_t> hcount(m.B);
+        std::vector<int32_t> hcount(m.B), hfcount(m.B, 0);
         HIP_OK(hipMemcpy(hcount.data(), dcount, m.B * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
-        std::string stem = ply_path;
-        if (m.B > 1 && stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".ply") == 0) stem.resize(stem.size() - 4);
+        if (mesh_path) HIP_OK(hipMemcpy(hfcount.data(), dfcount, m.B * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
         std::vector<unsigned char> hrec;
+        std::vector<int32_t> hfaces;
         for (int b = 0; b < m.B; ++b) {
             hrec.resize((size_t)hcount[b] * 16);
             HIP_OK(hipMemcpy(hrec.data(), (const char*)drec + (size_t)b * npix * 16, hrec.size(), hipMemcpyDeviceToHost), "download");
-            const std::string path = m.B > 1 ? stem + "." + std::to_string(b) + ".ply" : stem;
-            if (!write_ply(path, hrec.data(), hcount[b])) return fail("cannot write the PLY file");
+            if (ply_path && !write_ply(pair_path(ply_path, m.B, b), hrec.data(), hcount[b])) return fail("cannot write the PLY file");
+            if (mesh_path) {
+                hfaces.resize((size_t)hfcount[b] * 3);
+                HIP_OK(hipMemcpy(hfaces.data(), (const char*)dfaces + (size_t)b * fcap * 12, hfaces.size() * 4, hipMemcpyDeviceToHost), "download");
+                if (!write_ply_mesh(pair_path(mesh_path, m.B, b), hrec.data(), hcount[b], hfaces.data(), hfcount[b]))
+                    return fail("cannot write the mesh PLY file");
+            }
         }
         if (depth_path) {
             std::vector<float> hd((size_t)m.B * npix);
             HIP_OK(hipMemcpy(hd.data(), ddepth, hd.size() * sizeof(float), hipMemcpyDeviceToHost), "download");
             if (!write_raw(depth_path, hd)) return fail("cannot write the depth map");
         }
-        if (repeat > 0) {
+        if (repeat > 0 && mesh_path) {
+            hipEvent_t t0, t1;
+            HIP_OK(hipEventCreate(&t0), "hipEventCreate");
+            HIP_OK(hipEventCreate(&t1), "hipEventCreate");
+            HIP_OK(hipEventRecord(t0, s), "hipEventRecord");
+            for (int i = 0; i < repeat; ++i)
+                if (s2m2_mesh(&md, s) != 0) return fail_lib("s2m2_mesh failed");
+            HIP_OK(hipEventRecord(t1, s), "hipEventRecord");
+            HIP_OK(hipEventSynchronize(t1), "timed mesh runs");
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, t0, t1), "hipEventElapsedTime");
+            printf("{\"mesh_vertices\": %d, \"mesh_faces\": %d, \"repeat\": %d, \"mesh_us_per_pair\": %.2f}\n", hcount[0], hfcount[0], repeat,
+                   1000.f * ms / repeat / m.B);
+            (void)hipEventDestroy(t0);
+            (void)hipEventDestroy(t1);
+        }
+        if (repeat > 0 && ply_path) {
             hipEvent_t t0, t1;
             HIP_OK(hipEventCreate(&t0), "hipEventCreate");
             HIP_OK(hipEventCreate(&t1), "hipEventCreate");
@@ -360,6 +430,8 @@ int main(int argc, char** argv) {
         (void)hipFree(dws);
         (void)hipFree(dcount);
         (void)hipFree(ddepth);
+        (void)hipFree(dfaces);
+        (void)hipFree(dfcount);
     }
     if (gt_path) {
         const int gt_h = gt_rows / m.B;

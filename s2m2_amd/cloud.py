@@ -5,6 +5,10 @@ src/s2m2/core/utils/model_utils.py:111-136, the mask of vis_utils.py:62).  Here 
 and the unpadded left image, and leaves everything on the device: two kernel launches, no synchronisation, capturable in a hipGraph.  Between
 its inputs and its outputs this module only allocates; the host reads ``count`` in ``PointCloud.points`` / ``colors`` / ``write_ply`` alone.
 
+``mesh`` (K20, ``s2m2_mesh``) adds the surface: the same vertices plus the triangles that connect neighbouring kept pixels whose disparities
+differ by at most ``max_jump``, as int32 vertex ranks in raster order of their quads (the rule: include/s2m2_hip.h, K20).  Three launches, no
+synchronisation, capturable; the host reads the counts in the accessors of ``Mesh`` alone.
+
 A record is 16 bytes -- ``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
@@ -19,6 +23,8 @@ from . import hip
 
 PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
               "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nend_header\n")
+PLY_MESH_HEADER = PLY_HEADER.replace("end_header\n", "element face %d\nproperty list uchar int vertex_indices\nend_header\n")
+FACE_DISK_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])        # 13 bytes per face on disk
 RECORD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
 
 
@@ -48,6 +54,49 @@ def read_ply_records(path: str) -> np.ndarray:
     if len(body) != 16 * n[0]:
         raise ValueError(f"{path}: {n[0]} vertices declared, {len(body)} bytes of vertex data")
     return np.frombuffer(body, dtype=RECORD_DTYPE)
+
+
+def write_ply_mesh(path: str, records, faces) -> tuple:
+    """Host function: n vertex records (as for ``write_ply_records``) and an (m,3) integer array of vertex indices -> binary little-endian
+    PLY with ``element face m`` / ``property list uchar int vertex_indices``; returns (n, m)."""
+    raw = records if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records).tobytes()
+    if len(raw) % 16:
+        raise ValueError("write_ply_mesh: the vertex buffer is not a whole number of 16-byte records")
+    faces = np.asarray(faces)
+    if faces.size == 0:
+        faces = faces.reshape(0, 3)
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
+        raise ValueError("write_ply_mesh: faces must be an (m,3) integer array")
+    n, m = len(raw) // 16, faces.shape[0]
+    if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
+        raise ValueError(f"write_ply_mesh: a face references a vertex outside 0..{n - 1}")
+    disk = np.empty(m, dtype=FACE_DISK_DTYPE)
+    disk["n"], disk["v"] = 3, faces
+    with open(path, "wb") as f:
+        f.write((PLY_MESH_HEADER % (n, m)).encode("ascii"))
+        f.write(raw)
+        f.write(disk.tobytes())
+    return n, m
+
+
+def read_ply_mesh(path: str) -> tuple:
+    """The inverse of ``write_ply_mesh`` for files with exactly that layout -> (``RECORD_DTYPE`` array, (m,3) int32 array)."""
+    raw = open(path, "rb").read()
+    end = raw.find(b"end_header\n")
+    if not raw.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    head = raw[:end + len(b"end_header\n")].decode("ascii")
+    counts = [int(line.split()[2]) for line in head.split("\n") if line.startswith("element")]
+    if len(counts) != 2 or head != PLY_MESH_HEADER % tuple(counts):
+        raise ValueError(f"{path}: not the vertex + triangle layout of write_ply_mesh")
+    n, m = counts
+    body = raw[len(head):]
+    if len(body) != 16 * n + 13 * m:
+        raise ValueError(f"{path}: {n} vertices and {m} faces declared, {len(body)} bytes of data")
+    disk = np.frombuffer(body, dtype=FACE_DISK_DTYPE, offset=16 * n)
+    if m and not (disk["n"] == 3).all():
+        raise ValueError(f"{path}: a face is not a triangle")
+    return np.frombuffer(body, dtype=RECORD_DTYPE, count=n), np.ascontiguousarray(disk["v"])
 
 
 def read_calib_file(path: str) -> Dict[str, object]:
@@ -115,3 +164,63 @@ def reproject(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: 
               depth_scale=depth_scale, depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min,
               unfiltered=not filtered, records=records, count=count, workspace=workspace, depth=depth, mask=mask)
     return PointCloud(records, count, depth, mask)
+
+
+class Mesh(PointCloud):
+    """What ``mesh`` returns: a ``PointCloud`` (the vertices) plus ``faces_buf`` (B, face_capacity, 3) int32 vertex ranks in raster order of
+    their quads, ``face_count`` (B) int32 on the device (the true number of faces, also above face_capacity) and the optional dense rank map
+    ``index`` (B,1,H,W) int32 (-1: not a vertex)."""
+
+    def __init__(self, records: torch.Tensor, count: torch.Tensor, faces_buf: torch.Tensor, face_count: torch.Tensor,
+                 index: Optional[torch.Tensor] = None, depth: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+        super().__init__(records, count, depth, mask)
+        self.faces_buf, self.face_count, self.index = faces_buf, face_count, index
+
+    @property
+    def face_capacity(self) -> int:
+        return self.faces_buf.shape[1]
+
+    def face_size(self, b: int = 0) -> int:
+        """faces stored for pair b: min(face_count, face_capacity) -- reads ``face_count`` on the host (synchronises)"""
+        return min(int(self.face_count[b].item()), self.face_capacity)
+
+    def faces(self, b: int = 0) -> torch.Tensor:
+        """(n,3) int32 view of the stored faces of pair b.  Raises when the vertices overflowed: the faces hold true ranks and would reference
+        vertices that were not stored."""
+        n = int(self.count[b].item())
+        if n > self.capacity:
+            raise ValueError(f"Mesh.faces: pair {b} has {n} vertices but a capacity of {self.capacity}: the faces reference unstored vertices")
+        return self.faces_buf[b, :self.face_size(b)]
+
+    def write_ply(self, path: str, b: int = 0) -> tuple:
+        faces = self.faces(b).cpu().numpy()
+        return write_ply_mesh(path, self.records[b, :self.size(b)].cpu().numpy(), faces)
+
+
+def mesh(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, cx: float, cy: float, baseline: float,
+         doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0, depth_trunc: Optional[float] = None,
+         conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True, max_jump: float = 1.0, capacity: Optional[int] = None,
+         face_capacity: Optional[int] = None, want_depth: bool = False, want_mask: bool = False, want_index: bool = False) -> Mesh:
+    """``reproject``'s operands and conventions -> Mesh.  Neighbouring kept pixels are connected where their disparities differ by at most
+    ``max_jump`` (full-resolution pixels; inf connects every kept neighbour).  capacity None = H*W vertices, face_capacity None =
+    2*(H-1)*(W-1) faces per pair: nothing can overflow."""
+    B = disp.shape[0]
+    H, W = image.shape[-2:]
+    cap = H * W if capacity is None else int(capacity)
+    fcap = 2 * (H - 1) * (W - 1) if face_capacity is None else int(face_capacity)
+    if cap < 0 or fcap < 0:
+        raise ValueError("mesh: negative capacity")
+    dev = disp.device
+    records = torch.empty((B, cap, 4), device=dev, dtype=torch.int32)
+    count = torch.empty((B,), device=dev, dtype=torch.int32)
+    faces = torch.empty((B, fcap, 3), device=dev, dtype=torch.int32)
+    face_count = torch.empty((B,), device=dev, dtype=torch.int32)
+    workspace = torch.empty((hip.mesh_workspace_bytes(B, H, W),), device=dev, dtype=torch.uint8)
+    index = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_index else None
+    depth = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if want_depth else None
+    mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.uint8) if want_mask else None
+    hip.mesh(disp, occ, conf, image, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs, depth_scale=depth_scale,
+             depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min, unfiltered=not filtered,
+             max_jump=max_jump, records=records, count=count, faces=faces, face_count=face_count, workspace=workspace, index=index, depth=depth,
+             mask=mask)
+    return Mesh(records, count, faces, face_count, index, depth, mask)

@@ -3,90 +3,13 @@
 //   cloud_count_kernel    a block owns a tile of whole image rows: dense depth / mask, one count per tile into the workspace
 //   cloud_scatter_kernel  a block sums the counts of the tiles before its own (strided over the block, wave + block reduction), recomputes
 //                         keep, ranks its pixels (wave ballots + mbcnt, a prefix over the four waves through LDS) and stores the records
-// Pixel -> thread map: a thread owns four consecutive pixels of one row, placed so that their MAP column is a multiple of four whatever the crop
-// offset is (the first group of a row starts (Wp-W)/2 % 4 pixels left of the image): with Wp % 4 == 0 every map read is one aligned 16-byte
-// load that stays inside the padded row.  Image reads and the dense stores follow the unpadded rows and are per pixel unless a group is aligned.
-#include "common.h"
+// The per-pixel chain, the pixel -> thread map and the record live in cloud_device.h, which K20 (mesh.hip) compiles as well.  Image reads and
+// the dense stores follow the unpadded rows and are per pixel unless a group is aligned.
+#include "cloud_device.h"
 #include "launch.h"
 #include "plan.h"
 
 namespace s2m2 {
-
-constexpr int kCloudThreads = 256;                       // four waves
-constexpr int kCloudChunk = kCloudThreads * 4;           // pixels of one block step
-constexpr int kCloudTilePixels = 4096;                   // a tile: as many whole rows as fit (at least one)
-
-static inline int cloud_tile_rows(int W) { return W >= kCloudTilePixels ? 1 : kCloudTilePixels / W; }
-
-typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
-typedef unsigned char uchar4_t __attribute__((ext_vector_type(4)));
-
-struct CloudParams {
-    const float* disp;
-    const float* occ;
-    const float* conf;
-    const void* image;
-    float* depth;
-    unsigned char* mask;
-    uint4_t* records;
-    int* count;
-    int* tile_counts;
-    int H, W, Hp, Wp;
-    int oy, ox;                 // crop offsets
-    int rows_per_tile, tiles;   // tiles per pair
-    int unfiltered;
-    long long capacity;
-    float bf, doffs, depth_scale, depth_trunc, conf_min, occ_min;
-    float fx, fy, cx, cy;
-};
-
-// z of one pixel, or 0 when it is not kept (keep <=> z > 0): the arithmetic of the header, one fp32 rounding per operation
-__device__ __forceinline__ float cloud_z(const CloudParams& p, float disp, float occ, float conf) {
-    const bool valid = p.unfiltered || (conf > p.conf_min && occ > p.occ_min);
-    const float d = valid ? disp : -1.f;
-    const float depth = d <= 0.f ? 1e9f : p.bf / (d + p.doffs);
-    const float z = depth / p.depth_scale;
-    return (z > 0.f && z < p.depth_trunc) ? z : 0.f;
-}
-
-// the four pixels of this thread in image row v, first column u0 (may be < 0 or reach beyond W: those pixels give z = 0)
-template <bool VEC>
-__device__ __forceinline__ void cloud_eval4(const CloudParams& p, int b, int v, int u0, float z[4]) {
-    const size_t m = ((size_t)b * p.Hp + (v + p.oy)) * (size_t)p.Wp + (size_t)(p.ox + u0);      // p.ox + u0 >= 0 by construction
-    float d[4], o[4], c[4];
-    if constexpr (VEC) {                                 // aligned and inside the padded row: see the head of the file
-        const raw16_t dv = global_load16(p.disp + m), ov = global_load16(p.occ + m), cv = global_load16(p.conf + m);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { d[j] = dv[j]; o[j] = ov[j]; c[j] = cv[j]; }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool in = u0 + j >= 0 && u0 + j < p.W;
-            d[j] = in ? p.disp[m + j] : 0.f;
-            o[j] = in ? p.occ[m + j] : 0.f;
-            c[j] = in ? p.conf[m + j] : 0.f;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) z[j] = (u0 + j >= 0 && u0 + j < p.W) ? cloud_z(p, d[j], o[j], c[j]) : 0.f;
-}
-
-__device__ __forceinline__ int wave_sum_int(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// sum over the block of one int per thread, result in every thread (red: kCloudThreads / 64 ints of LDS)
-__device__ __forceinline__ int block_sum_int(int x, int* red) {
-    x = wave_sum_int(x);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < kCloudThreads / 64; ++w) s += red[w];
-    return s;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kCloudThreads) void cloud_count_kernel(const CloudParams p) {
@@ -131,11 +54,6 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_count_kernel(const CloudP
     }
 }
 
-template <typename IT> __device__ __forceinline__ unsigned cloud_byte(IT x);
-template <> __device__ __forceinline__ unsigned cloud_byte<unsigned char>(unsigned char x) { return x; }
-template <> __device__ __forceinline__ unsigned cloud_byte<float>(float x) { return (unsigned)__float2int_rn(fminf(fmaxf(x, 0.f), 255.f)); }
-template <> __device__ __forceinline__ unsigned cloud_byte<half_t>(half_t x) { return cloud_byte<float>((float)x); }
-
 template <bool VEC, typename IT>
 __global__ __launch_bounds__(kCloudThreads) void cloud_scatter_kernel(const CloudParams p) {
     __shared__ int red[kCloudThreads / 64];
@@ -155,8 +73,6 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_scatter_kernel(const Clou
     const int v_end = min(p.H, (tile + 1) * p.rows_per_tile);
     int step = 0;
     for (int v = tile * p.rows_per_tile; v < v_end; ++v) {
-        const size_t row = (size_t)v * p.W;
-        const float fv = (float)v - p.cy;
         for (int c0 = -shift; c0 < p.W; c0 += kCloudChunk, ++step) {       // block-uniform: every wave takes every step (barrier inside)
             const int u0 = c0 + (int)threadIdx.x * 4;
             float z[4] = {0.f, 0.f, 0.f, 0.f};
@@ -184,16 +100,7 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_scatter_kernel(const Clou
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (z[j] > 0.f) {
-                    if (r < p.capacity) {
-                        const int u = u0 + j;
-                        const size_t px = row + u;
-                        const unsigned cr = cloud_byte<IT>(img[px]), cg = cloud_byte<IT>(img[plane + px]), cb = cloud_byte<IT>(img[2 * plane + px]);
-                        const float x = ((float)u - p.cx) * z[j] / p.fx;
-                        const float y = fv * z[j] / p.fy;
-                        uint4_t o = {__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, y), __builtin_bit_cast(unsigned, z[j]),
-                                     cr | (cg << 8) | (cb << 16) | 0xff000000u};
-                        rec[r] = o;
-                    }
+                    if (r < p.capacity) rec[r] = cloud_record<IT>(p, img, plane, v, u0 + j, z[j]);
                     ++r;
                 }
             }
@@ -202,35 +109,32 @@ __global__ __launch_bounds__(kCloudThreads) void cloud_scatter_kernel(const Clou
     if (tile == p.tiles - 1 && threadIdx.x == 0) p.count[b] = (int)base;
 }
 
-static bool cloud_extents_ok(int B, int H, int W) {
-    return B > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && B <= 65535;
-}
-
-static int cloud_impl(const s2m2_cloud_desc* d, void* stream) {
-    S2M2_REQUIRE(d != nullptr, "cloud: null descriptor");
-    S2M2_REQUIRE(!plan_recording(), "cloud: s2m2_cloud is not recorded in launch plans -- call it after s2m2_plan_end, behind s2m2_plan_run / "
-                                    "s2m2_engine_run on the same stream");
-    S2M2_REQUIRE(d->disp && d->occ && d->conf, "cloud: null pointer (disp / occ / conf)");
-    S2M2_REQUIRE(d->depth || d->mask || d->count, "cloud: no output requested (depth, mask and count are all null pointers)");
-    S2M2_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Hp > 0 && d->Wp > 0, "cloud: non-positive extents B=%d H=%d W=%d Hp=%d Wp=%d", d->B, d->H,
-                 d->W, d->Hp, d->Wp);
-    S2M2_REQUIRE(d->H <= d->Hp && d->W <= d->Wp, "cloud: the image (H=%d, W=%d) is larger than the maps (Hp=%d, Wp=%d)", d->H, d->W, d->Hp, d->Wp);
-    S2M2_REQUIRE(cloud_extents_ok(d->B, d->H, d->W) && (long long)d->Hp * d->Wp < (1LL << 31), "cloud: extents too large (B <= 65535, H*W < 2^31)");
-    S2M2_REQUIRE(d->fx > 0.0 && d->fy > 0.0, "cloud: fx and fy must be positive (fx=%g fy=%g)", d->fx, d->fy);
-    S2M2_REQUIRE(d->depth_scale > 0.0, "cloud: depth_scale must be positive (%g)", d->depth_scale);
-    S2M2_REQUIRE(d->capacity >= 0, "cloud: negative capacity %lld", d->capacity);
-    S2M2_REQUIRE(d->image_dtype == S2M2_F32 || d->image_dtype == S2M2_F16 || d->image_dtype == 2, "cloud: unsupported image dtype %d", d->image_dtype);
+// every check of a s2m2_cloud_desc that include/s2m2_hip.h lists, then the kernel parameters: shared with s2m2_mesh (mesh.hip), which takes the
+// same descriptor fields (`what` prefixes the messages)
+int cloud_validate(const s2m2_cloud_desc* d, const char* what, CloudParams& p, bool& vec) {
+    S2M2_REQUIRE(d->disp && d->occ && d->conf, "%s: null pointer (disp / occ / conf)", what);
+    S2M2_REQUIRE(d->depth || d->mask || d->count, "%s: no output requested (depth, mask and count are all null pointers)", what);
+    S2M2_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Hp > 0 && d->Wp > 0, "%s: non-positive extents B=%d H=%d W=%d Hp=%d Wp=%d", what, d->B,
+                 d->H, d->W, d->Hp, d->Wp);
+    S2M2_REQUIRE(d->H <= d->Hp && d->W <= d->Wp, "%s: the image (H=%d, W=%d) is larger than the maps (Hp=%d, Wp=%d)", what, d->H, d->W, d->Hp,
+                 d->Wp);
+    S2M2_REQUIRE(cloud_extents_ok(d->B, d->H, d->W) && (long long)d->Hp * d->Wp < (1LL << 31), "%s: extents too large (B <= 65535, H*W < 2^31)",
+                 what);
+    S2M2_REQUIRE(d->fx > 0.0 && d->fy > 0.0, "%s: fx and fy must be positive (fx=%g fy=%g)", what, d->fx, d->fy);
+    S2M2_REQUIRE(d->depth_scale > 0.0, "%s: depth_scale must be positive (%g)", what, d->depth_scale);
+    S2M2_REQUIRE(d->capacity >= 0, "%s: negative capacity %lld", what, d->capacity);
+    S2M2_REQUIRE(d->image_dtype == S2M2_F32 || d->image_dtype == S2M2_F16 || d->image_dtype == 2, "%s: unsupported image dtype %d", what,
+                 d->image_dtype);
     if (d->count) {
-        S2M2_REQUIRE(d->image != nullptr, "cloud: null pointer (image) while a cloud is requested");
-        S2M2_REQUIRE(d->workspace != nullptr, "cloud: null workspace while a cloud is requested (s2m2_cloud_workspace_bytes)");
-        S2M2_REQUIRE(((uintptr_t)d->workspace & 3) == 0, "cloud: the workspace must be 4-byte aligned");
-        S2M2_REQUIRE(d->records != nullptr || d->capacity == 0, "cloud: null pointer (records) with capacity %lld", d->capacity);
-        S2M2_REQUIRE(((uintptr_t)d->records & 15) == 0, "cloud: records must be 16-byte aligned");
+        S2M2_REQUIRE(d->image != nullptr, "%s: null pointer (image) while a cloud is requested", what);
+        S2M2_REQUIRE(d->workspace != nullptr, "%s: null workspace while a cloud is requested (s2m2_%s_workspace_bytes)", what, what);
+        S2M2_REQUIRE(((uintptr_t)d->workspace & 3) == 0, "%s: the workspace must be 4-byte aligned", what);
+        S2M2_REQUIRE(d->records != nullptr || d->capacity == 0, "%s: null pointer (records) with capacity %lld", what, d->capacity);
+        S2M2_REQUIRE(((uintptr_t)d->records & 15) == 0, "%s: records must be 16-byte aligned", what);
     }
     S2M2_REQUIRE(((uintptr_t)d->depth & 3) == 0 && ((uintptr_t)d->disp & 3) == 0 && ((uintptr_t)d->occ & 3) == 0 && ((uintptr_t)d->conf & 3) == 0,
-                 "cloud: fp32 tensors must be 4-byte aligned");
+                 "%s: fp32 tensors must be 4-byte aligned", what);
 
-    CloudParams p;
     p.disp = d->disp; p.occ = d->occ; p.conf = d->conf; p.image = d->image;
     p.depth = d->depth; p.mask = d->mask;
     p.records = static_cast<uint4_t*>(d->records);
@@ -248,11 +152,21 @@ static int cloud_impl(const s2m2_cloud_desc* d, void* stream) {
     p.depth_trunc = d->depth_trunc > 0.0 ? (float)d->depth_trunc : 1e9f;
     p.conf_min = (float)d->conf_min; p.occ_min = (float)d->occ_min;
     p.fx = (float)d->fx; p.fy = (float)d->fy; p.cx = (float)d->cx; p.cy = (float)d->cy;
-    S2M2_REQUIRE(p.fx > 0.f && p.fy > 0.f && p.depth_scale > 0.f, "cloud: fx, fy and depth_scale must be positive in fp32");
+    S2M2_REQUIRE(p.fx > 0.f && p.fy > 0.f && p.depth_scale > 0.f, "%s: fx, fy and depth_scale must be positive in fp32", what);
     // the aligned form: 16-byte map loads.  The dense outputs take 16-byte / 4-byte group stores only where their own address allows it
     // (checked per group in the kernel against the element index: that needs the base pointers aligned too, else the per-pixel form)
-    const bool vec = d->Wp % 4 == 0 && (((uintptr_t)d->disp | (uintptr_t)d->occ | (uintptr_t)d->conf) & 15) == 0 &&
-                     ((uintptr_t)d->depth & 15) == 0 && ((uintptr_t)d->mask & 3) == 0;
+    vec = d->Wp % 4 == 0 && (((uintptr_t)d->disp | (uintptr_t)d->occ | (uintptr_t)d->conf) & 15) == 0 && ((uintptr_t)d->depth & 15) == 0 &&
+          ((uintptr_t)d->mask & 3) == 0;
+    return 0;
+}
+
+static int cloud_impl(const s2m2_cloud_desc* d, void* stream) {
+    S2M2_REQUIRE(d != nullptr, "cloud: null descriptor");
+    S2M2_REQUIRE(!plan_recording(), "cloud: s2m2_cloud is not recorded in launch plans -- call it after s2m2_plan_end, behind s2m2_plan_run / "
+                                    "s2m2_engine_run on the same stream");
+    CloudParams p;
+    bool vec = false;
+    if (int rc = cloud_validate(d, "cloud", p, vec)) return rc;
     const dim3 grid(p.tiles, d->B), block(kCloudThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = vec ? launch<cloud_count_kernel<true>>("cloud (count)", grid, block, 0, s, p) : launch<cloud_count_kernel<false>>("cloud (count)", grid, block, 0, s, p))

@@ -124,6 +124,11 @@ class CloudDesc(ctypes.Structure):
                 ("conf_min", ctypes.c_double), ("occ_min", ctypes.c_double)]
 
 
+class MeshDesc(ctypes.Structure):
+    """mirror of s2m2_mesh_desc (include/s2m2_hip.h): K20, the surface mesh behind the 3D stage"""
+    _fields_ = [("cloud", CloudDesc), ("faces", _vp), ("face_count", _vp), ("index", _vp), ("face_capacity", _ll), ("max_jump", ctypes.c_double)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -226,6 +231,9 @@ SIGNATURES = {
     "s2m2_eval_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_eval_tile_rows": (_i, [_i, _i]),
     "s2m2_disp_eval": (_i, [ctypes.POINTER(EvalDesc), _vp]),
+    "s2m2_mesh_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_mesh_tile_rows": (_i, [_i, _i]),
+    "s2m2_mesh": (_i, [ctypes.POINTER(MeshDesc), _vp]),
 }
 
 
@@ -1155,6 +1163,43 @@ def image_pad(img: torch.Tensor, factor: int = 32) -> torch.Tensor:
     return out
 
 
+def _cloud_desc(what: str, d: CloudDesc, need, disp, occ, conf, image, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min,
+                occ_min, unfiltered, records, count, workspace, depth, mask) -> None:
+    """fills ``d`` for s2m2_cloud / s2m2_mesh from validated operands; ``need(B, H, W)``: the workspace bytes that ``count`` requires (asked
+    behind the shape checks, as ever)"""
+    if disp.dtype != torch.float32 or occ.dtype != torch.float32 or conf.dtype != torch.float32 or disp.dim() != 4 or disp.shape[1] != 1:
+        raise ValueError(f"{what}: disp / occ / conf must be (B,1,Hp,Wp) fp32 tensors")
+    if occ.shape != disp.shape or conf.shape != disp.shape:
+        raise ValueError(f"{what}: disp, occ and conf must have one shape")
+    if image.dtype not in _IMG_DT or image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != disp.shape[0]:
+        raise ValueError(f"{what}: image must be a (B,3,H,W) uint8 / fp16 / fp32 tensor")
+    B, _, Hp, Wp = disp.shape
+    H, W = image.shape[-2:]
+    d.disp, d.occ, d.conf, d.image = disp.data_ptr(), occ.data_ptr(), conf.data_ptr(), image.data_ptr()
+    d.B, d.H, d.W, d.Hp, d.Wp, d.image_dtype, d.unfiltered = B, H, W, Hp, Wp, _IMG_DT[image.dtype], int(unfiltered)
+    if depth is not None:
+        _mat(depth, (B, 1, H, W), torch.float32, f"{what}: depth")
+        d.depth = depth.data_ptr()
+    if mask is not None:
+        _mat(mask, (B, 1, H, W), torch.uint8, f"{what}: mask")
+        d.mask = mask.data_ptr()
+    if count is not None:
+        _vec(count, B, f"{what}: count", dtype=torch.int32)
+        need = need(B, H, W)
+        if workspace is None or workspace.nbytes < need:
+            raise ValueError(f"{what}: a workspace of {need} bytes is required with count")
+        d.count, d.workspace = count.data_ptr(), workspace.data_ptr()
+        if records is not None:
+            if records.dtype != torch.int32 or records.dim() != 3 or records.shape[0] != B or records.shape[2] != 4:
+                raise ValueError(f"{what}: records must be a (B, capacity, 4) int32 tensor")
+            d.capacity = records.shape[1]
+            d.records = records.data_ptr() if records.shape[1] > 0 else None
+    elif records is not None:
+        raise ValueError(f"{what}: records come with count")
+    d.fx, d.fy, d.cx, d.cy, d.baseline, d.doffs = fx, fy, cx, cy, baseline, doffs
+    d.depth_scale, d.depth_trunc, d.conf_min, d.occ_min = depth_scale, depth_trunc, conf_min, occ_min
+
+
 def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, fy: float, cx: float, cy: float,
           baseline: float, doffs: float = 0.0, depth_scale: float = 1000.0, depth_trunc: float = 0.0, conf_min: float = 0.1,
           occ_min: float = 0.5, unfiltered: bool = False, records: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
@@ -1164,38 +1209,9 @@ def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torc
     ``cloud_workspace_bytes`` bytes, ``depth`` (B,1,H,W) fp32, ``mask`` (B,1,H,W) uint8.  Thin: no allocation, no synchronisation."""
     _resident("cloud", disp, occ, conf, image, records, count, workspace, depth, mask)
     _contig("cloud", disp, occ, conf, image, records, count, workspace, depth, mask)
-    if disp.dtype != torch.float32 or occ.dtype != torch.float32 or conf.dtype != torch.float32 or disp.dim() != 4 or disp.shape[1] != 1:
-        raise ValueError("cloud: disp / occ / conf must be (B,1,Hp,Wp) fp32 tensors")
-    if occ.shape != disp.shape or conf.shape != disp.shape:
-        raise ValueError("cloud: disp, occ and conf must have one shape")
-    if image.dtype not in _IMG_DT or image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != disp.shape[0]:
-        raise ValueError("cloud: image must be a (B,3,H,W) uint8 / fp16 / fp32 tensor")
-    B, _, Hp, Wp = disp.shape
-    H, W = image.shape[-2:]
     d = CloudDesc()
-    d.disp, d.occ, d.conf, d.image = disp.data_ptr(), occ.data_ptr(), conf.data_ptr(), image.data_ptr()
-    d.B, d.H, d.W, d.Hp, d.Wp, d.image_dtype, d.unfiltered = B, H, W, Hp, Wp, _IMG_DT[image.dtype], int(unfiltered)
-    if depth is not None:
-        _mat(depth, (B, 1, H, W), torch.float32, "cloud: depth")
-        d.depth = depth.data_ptr()
-    if mask is not None:
-        _mat(mask, (B, 1, H, W), torch.uint8, "cloud: mask")
-        d.mask = mask.data_ptr()
-    if count is not None:
-        _vec(count, B, "cloud: count", dtype=torch.int32)
-        need = cloud_workspace_bytes(B, H, W)
-        if workspace is None or workspace.nbytes < need:
-            raise ValueError(f"cloud: a workspace of {need} bytes is required with count")
-        d.count, d.workspace = count.data_ptr(), workspace.data_ptr()
-        if records is not None:
-            if records.dtype != torch.int32 or records.dim() != 3 or records.shape[0] != B or records.shape[2] != 4:
-                raise ValueError("cloud: records must be a (B, capacity, 4) int32 tensor")
-            d.capacity = records.shape[1]
-            d.records = records.data_ptr() if records.shape[1] > 0 else None
-    elif records is not None:
-        raise ValueError("cloud: records come with count")
-    d.fx, d.fy, d.cx, d.cy, d.baseline, d.doffs = fx, fy, cx, cy, baseline, doffs
-    d.depth_scale, d.depth_trunc, d.conf_min, d.occ_min = depth_scale, depth_trunc, conf_min, occ_min
+    _cloud_desc("cloud", d, cloud_workspace_bytes, disp, occ, conf, image, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min,
+                unfiltered, records, count, workspace, depth, mask)
     with torch.cuda.device(disp.device):
         _check(load().s2m2_cloud(ctypes.byref(d), _stream()), "s2m2_cloud")
 
@@ -1257,3 +1273,6 @@ from .hip_eval import disp_eval, eval_tile_rows, eval_workspace_bytes  # noqa: E
 
 # K19 (s2m2_conv_block_tail): likewise, from hip_tail.py
 from .hip_tail import conv_block_tail, conv_block_tail_supported  # noqa: E402,F401
+
+# K20 (s2m2_mesh): likewise, from hip_mesh.py
+from .hip_mesh import mesh, mesh_tile_rows, mesh_workspace_bytes  # noqa: E402,F401

@@ -7,6 +7,8 @@ image_utils.py) -- SURVEY.md section 8f rows 1-2: same names, arguments and retu
 * ``run_stereo_matching``  model_utils.py:51-95 (pad -> autocast fp16 forward -> crop -> average confidence)
 * ``compute_confidence_score``   model_utils.py:98-101
 * ``get_pointcloud``       model_utils.py:111-136 (depth from disparity + open3d's RGBD -> point cloud conversion; HIP kernels ``s2m2_cloud``)
+* ``get_mesh``             no counterpart in the reference: ``get_pointcloud``'s arguments -> the surface mesh that connects neighbouring
+  pixels of similar disparity (HIP kernels ``s2m2_mesh``; ``s2m2_amd.cloud.mesh``)
 * ``compute_confidence_scores``  the calibration objective (calibration/base.py:15-36 called 20 x 5 times one pair at a time by
   calibration/cem.py:66-72) for a whole population of rectified pairs at once: one batched forward, or sharded over the ranks of a
   ``torch.distributed`` group
@@ -165,3 +167,18 @@ def get_pointcloud(rgb, disp, calib, depth_trunc=None):
     with torch.cuda.device(device):
         return cloud.reproject(disp_t, disp_t, disp_t, image, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
                                baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False)
+
+
+def get_mesh(rgb, disp, calib, depth_trunc=None, max_jump=1.0):
+    """``get_pointcloud``'s arguments and conventions (halved intrinsics, fx for both focal lengths, no confidence filter) -> a ``cloud.Mesh`` on
+    the device: the same vertices plus the triangles between neighbouring pixels whose disparities differ by at most ``max_jump`` px."""
+    from . import cloud
+    disp_t = torch.as_tensor(disp)
+    device = disp_t.device if disp_t.is_cuda else torch.device("cuda")
+    disp_t = disp_t.to(device=device, dtype=torch.float32).contiguous()[None, None]
+    image = torch.as_tensor(rgb).to(device).permute(2, 0, 1).contiguous()[None]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(device):
+        return cloud.mesh(disp_t, disp_t, disp_t, image, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
+                          baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
+                          max_jump=max_jump)
