@@ -431,7 +431,8 @@ int s2m2_row_attn(const s2m2_rowattn_desc* desc, void* stream);
  *   Replaces the launch triple s2m2_mlp_chain (1x1 branch) / s2m2_conv2d (korder 2) / s2m2_conv2d (korder 2, EPI_ADD) with the same arithmetic
  *   in the same order (bit-identical): a block owns a patch of output pixels and all C channels, recomputes the one-pixel ring of the first
  *   3x3 layer and keeps the GELU tensor in LDS.  Meant for grids whose launches are latency chains (1/8 ... 1/32 resolution).
- *     x, out     (N, H, W, C) fp16, channels contiguous, pixel strides in elements (x: multiple of 8, out: multiple of 4); out != x
+ *     x, out     (N, H, W, C) fp16, channels contiguous, x 16-byte and out 8-byte aligned, pixel strides in elements (at least C; x: multiple
+ *                of 8, out: multiple of 4); out must not overlap x
  *     w_conv0/2  the 3x3 layers as s2m2_conv_desc.weight with korder = 2 (s2m2_pack_frag S2M2_PACK_CONV_FRAG, 128-channel chunks)
  *     w_1x0/2    the 1x1 layers as s2m2_chain_desc.weight with weight_frag = 1 (S2M2_PACK_ROWS)
  *     b_*        fp32 (C) or NULL
@@ -465,7 +466,8 @@ int s2m2_conv_block(const s2m2_convblock_desc* desc, void* stream);
  *   z | r layer with epi_cout0 = C and the r * h epilogue) / s2m2_conv2d (the candidate layer with S2M2_EPI_GRU) with the same arithmetic in
  *   the same order (bit-identical to the pair with the candidate layer in K order 2): a block owns a patch of output pixels, recomputes r on
  *   the patch's one-pixel ring along the tap axis and keeps z and r * h on the CU.
- *     h, x, out  (N, H, W, C) fp16, channels contiguous, 16-byte aligned, pixel strides in elements (multiples of 8); out distinct from h and x
+ *     h, x, out  (N, H, W, C) fp16, channels contiguous, 16-byte aligned, pixel strides in elements (at least C, multiples of 8); out must
+ *                not overlap h or x
  *     w_zr       [convz | convr] stacked along Cout (2 C rows, z first) over cat(h, x), as s2m2_conv_desc.weight with korder = 2
  *     w_q        convq over cat(r * h, x), as s2m2_conv_desc.weight with korder = 2
  *     b_zr, b_q  fp32 (2 C) / (C), or NULL

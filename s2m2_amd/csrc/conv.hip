@@ -28,6 +28,7 @@
 #define S2M2_CONV_DBG 0
 #endif
 #include "epilogue.h"
+#include "frag_ring.h"
 
 // which K loops use untracked loads + counted waits (common.h): bit 0 the halo kernel (ring variants), bit 1 the v1 kernel
 #ifndef S2M2_ASYNC_LOADS
@@ -1117,19 +1118,16 @@ struct ConvCfgF {
     static constexpr int BM = PW_ * PH_, BN = BN_, PH = PH_, PW = PW_, WGM = 1, WGN = BN_ / 32;
     static constexpr int NWAVES = WGN, NT = 64 * NWAVES;
     static constexpr int VEC = 8, CH = CH_, KS = CH_ / 16;       // channels per chunk, k16 steps per tap
-    static constexpr int RS = CH + VEC;                  // LDS row stride (elements): 16 bytes of padding per halo pixel
     static constexpr int WM = BM, WN = 32, MT = BM / 32, NTL = 1;
     static_assert(BM % 32 == 0, "a patch is a whole number of 32-pixel MFMA tiles");
     static constexpr int MAXHALO = (PH + 2) * (PW + 2);
-    static constexpr int PPX = CH / VEC;                 // 16-byte pieces per halo pixel
-    static constexpr int RPI = NT / PPX;                 // halo pixels covered by one pass of the loader threads
-    static constexpr int A_IT = (MAXHALO + RPI - 1) / RPI;
+    using Halo = HaloGeom<NT, CH, MAXHALO>;              // the halo tile of one channel chunk and its loader (frag_ring.h)
+    static constexpr int RS = Halo::RS, PPX = Halo::PPX, RPI = Halo::RPI, A_IT = Halo::A_IT, AROWS = Halo::AROWS;
     static constexpr int CRS = BN + VEC;
-    static constexpr int AROWS = A_IT * RPI;             // LDS rows: every loader thread stashes all of its pieces, no exec-masked tail
-    static constexpr size_t A_BYTES = (size_t)AROWS * RS * sizeof(T);
+    static constexpr size_t A_BYTES = Halo::A_BYTES;
     static constexpr size_t STAGE_BYTES = (size_t)BM * CRS * sizeof(T);
     static constexpr size_t LDS_BYTES = A_BYTES > STAGE_BYTES ? A_BYTES : STAGE_BYTES;
-    static_assert(NT % PPX == 0 && KS >= 2 && KS % 2 == 0, "loader geometry");
+    static_assert(KS >= 2 && KS % 2 == 0, "ring geometry");
 };
 
 // AUX: epilogue operands parked in registers through the K loop: 0 none (epi == NONE), 1 one (add / mul), 2 two (GRU blend, gate mix)
@@ -1247,33 +1245,11 @@ __global__ __launch_bounds__(CFG::NT) void conv_frag_kernel(ConvArgs p, int tile
         if constexpr (PW == 32) poff[i] = (i * HW_ + l31) * RS;
         else { const int q = 32 * i + l31, qy = q / PW; poff[i] = (qy * HW_ + (q - qy * PW)) * RS; }
     }
-    auto tap_steps = [&](int ky, int kx) __attribute__((always_inline)) {          // the KS k16 steps of one tap
+    // the KS k16 steps of one tap: frag_ring.h.  (Through a local lambda: called directly, the same text allocates this kernel's registers
+    // differently -- tools/compare_code_objects.py.)
+    auto one_tap = [&](int ky, int kx) __attribute__((always_inline)) {
         const T* a = Ah + (size_t)(ky * HW_ + kx) * RS + hi * 8;
-        Frag<T> xf[2][CFG::MT];                                   // pixel fragments, double buffered across k16 steps
-#pragma unroll
-        for (int i = 0; i < CFG::MT; ++i) load_frag(xf[0][i], a + poff[i]);
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-            if (kk + 1 < KS) {
-#pragma unroll
-                for (int i = 0; i < CFG::MT; ++i) load_frag(xf[(kk + 1) & 1][i], a + poff[i] + (kk + 1) * 16);
-            }
-            // fragment g (slot kk) was requested KS - 1 steps ago; the KS - 2 requests made since then may still be in flight
-            wait_vmcnt<KS - 2>();
-            settle(ring[kk]);
-            Frag<T> wfr;
-            wfr.v = __builtin_bit_cast(half8_t, ring[kk]);
-#pragma unroll
-            for (int i = 0; i < CFG::MT; ++i) mma32(acc[i][0], wfr, xf[kk & 1][i]);   // D[cout][pixel]
-            // refill the slot consumed one step ago (its MFMAs have long read their operands) with fragment g + KS - 1.
-            // UNCONDITIONAL: a branch around an untracked load makes the compiler merge the two register states with copies
-            // that read the slot while its load is in flight.  (Step 0 re-requests fragment KS - 1 into its own slot.)
-            {
-                const int f = g + KS - 1;
-                global_load16_async(ring[(kk + KS - 1) % KS], wf + (size_t)(f < nfrag ? f : nfrag - 1) * 64);
-            }
-            ++g;
-        }
+        cb_steps<CFG::MT, KS>(reinterpret_cast<float16_t (&)[CFG::MT]>(acc), a, poff, ring, wf, g, nfrag);
     };
     for (int chunk = 0; chunk < nchunk; ++chunk) {
         if (chunk > 0) {
@@ -1285,11 +1261,11 @@ __global__ __launch_bounds__(CFG::NT) void conv_frag_kernel(ConvArgs p, int tile
         int ky = 0, kx = 0;
 #pragma unroll 1
         for (int tap = 0; tap < ntap; ++tap) {
-            tap_steps(ky, kx);
+            one_tap(ky, kx);
             if (++kx == p.KW) { kx = 0; ++ky; }
         }
     }
-    wait_vmcnt<0>();                                              // drain the tail requests before their registers are reused
+    wait_vmcnt<0>();                                              // frag_ring.h: ring_drain, kept inline (the call moves this kernel's code object)
 #pragma unroll
     for (int s = 0; s < KS; ++s) settle(ring[s]);
 

@@ -40,14 +40,14 @@ struct CbCfg {
     static constexpr int C = C_, PH = PH_, PW = 32, NW = C_ / 32, NT = 64 * NW, KS = 8, CH = 128, NCHUNK = C_ / 128;
     static constexpr int IH = PH + 2, IW = PW + 2, NI = IH * IW, MT1 = (NI + 31) / 32;      // intermediate grid (convs.0 output)
     static constexpr int HH = PH + 4, HW = PW + 4, NHALO = HH * HW;                          // input tile
-    static constexpr int RS = CH + 8, TRS = C + 8;                                           // LDS row strides (elements)
-    static constexpr int PPX = CH / 8, RPI = NT / PPX, A_IT = (NHALO + RPI - 1) / RPI, AROWS = A_IT * RPI;
-    static constexpr size_t A_BYTES = (size_t)AROWS * RS * 2;                                // input tile (one 128-channel chunk)
+    using Halo = HaloGeom<NT, CH, NHALO>;                                                    // one 128-channel chunk of it and its loader (frag_ring.h)
+    static constexpr int RS = Halo::RS, TRS = C + 8, PPX = Halo::PPX, RPI = Halo::RPI, A_IT = Halo::A_IT, AROWS = Halo::AROWS;
+    static constexpr size_t A_BYTES = Halo::A_BYTES;
     static constexpr size_t R_BYTES = (size_t)PH * 32 * TRS * 2;                             // ReLU tile of the 1x1 branch (aliases the input tile)
     static constexpr size_t T_BYTES = (size_t)MT1 * 32 * TRS * 2;                            // intermediate
     static constexpr size_t A_REGION = A_BYTES > R_BYTES ? A_BYTES : R_BYTES;
     static constexpr size_t OFF_T = (A_REGION + 15) / 16 * 16, OFF_B = OFF_T + T_BYTES, LDS_BYTES = OFF_B + 4 * C * 4;
-    static_assert(LDS_BYTES <= 160 * 1024 && NT % PPX == 0, "conv block tile");
+    static_assert(LDS_BYTES <= 160 * 1024, "conv block tile");
 };
 
 template <typename CFG>
@@ -113,10 +113,7 @@ __global__ __launch_bounds__(CFG::NT) void conv_block_kernel(CbArgs p) {
     }
 #pragma unroll
     for (int i = 0; i < PH; ++i) poffA[i] = ((i + 2) * HW + l31 + 2) * RS + hi * 8;
-    // slots 0 .. KS-2 only: slot KS-1 gets its first request from step 0 (a request whose value is never consumed leaves its destination
-    // registers free for the allocator while the load is in flight -- the hazard common.h describes)
-#pragma unroll
-    for (int s = 0; s < KS - 1; ++s) global_load16_async(ring[s], wf1 + (size_t)s * 64);
+    ring_start(ring, wf1);
     int g = 0;
 #pragma unroll 1
     for (int chunk = 0; chunk < NCHUNK; ++chunk) {
@@ -151,10 +148,7 @@ __global__ __launch_bounds__(CFG::NT) void conv_block_kernel(CbArgs p) {
             }
         }
     }
-    // the ring now holds re-requests of the stream's tail (cb_steps clamps): drain, then start convs.2's stream under the epilogues
-    wait_vmcnt<0>();
-#pragma unroll
-    for (int s = 0; s < KS; ++s) settle(ring[s]);
+    ring_drain(ring);                                            // convs.2's stream starts under the epilogues, below
     const int nfrag2 = NCHUNK * 9 * KS;
     const raw16_t* wf2 = p.w2 + (size_t)wv * nfrag2 * 64 + lane;
     __syncthreads();                                             // every wave is done with the input tile (the ReLU tile aliases it)
@@ -190,15 +184,14 @@ __global__ __launch_bounds__(CFG::NT) void conv_block_kernel(CbArgs p) {
             *reinterpret_cast<half4_t*>(rrow + 8 * gq) = h;
         }
     }
-#pragma unroll
-    for (int s = 0; s < KS - 1; ++s) global_load16_async(ring[s], wf2 + (size_t)s * 64);
+    ring_start(ring, wf2);
     __syncthreads();
     // ---- phase 2: convs.2 on the patch from the intermediate; convs_1x.2 from the ReLU tile
     float16_t acc2[PH], accB[PH];
 #pragma unroll
     for (int i = 0; i < PH; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { acc2[i][r] = 0.f; accB[i][r] = 0.f; }
+        for (int r = 0; r < 16; ++r) acc2[i][r] = 0.f;
     int poff2[PH];
 #pragma unroll
     for (int i = 0; i < PH; ++i) poff2[i] = (i * IW + l31) * TRS + hi * 8;
@@ -212,29 +205,8 @@ __global__ __launch_bounds__(CFG::NT) void conv_block_kernel(CbArgs p) {
             if (++kx == 3) { kx = 0; ++ky; }
         }
     }
-    wait_vmcnt<0>();
-#pragma unroll
-    for (int s = 0; s < KS; ++s) settle(ring[s]);
-    {
-        const raw16_t* wfb = p.wb + (size_t)wv * (C / 16) * 64 + lane;
-#pragma unroll 1
-        for (int c8 = 0; c8 < C / 16; c8 += KS) {
-            raw16_t wr[KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s) wr[s] = global_load16(wfb + (size_t)(c8 + s) * 64);
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                Frag<half_t> wfr;
-                wfr.v = __builtin_bit_cast(half8_t, wr[s]);
-#pragma unroll
-                for (int i = 0; i < PH; ++i) {
-                    Frag<half_t> xf;
-                    load_frag(xf, Rt + (size_t)(32 * i + l31) * TRS + hi * 8 + (c8 + s) * 16);
-                    mma32(accB[i], wfr, xf);
-                }
-            }
-        }
-    }
+    ring_drain(ring);
+    tile_1x1<PH, KS, C, TRS>(accB, Rt, p.wb + (size_t)wv * (C / 16) * 64 + lane, l31, hi);
     // ---- out = fp16(fp16(convs.2 + b2) + fp16(convs_1x.2 + bb)): K5's EPI_ADD on K9's output
 #pragma unroll
     for (int i = 0; i < PH; ++i) {
@@ -277,10 +249,14 @@ static int conv_block_impl(const s2m2_convblock_desc* d, void* stream) {
     using namespace s2m2;
     S2M2_REQUIRE(d, "conv_block: null descriptor");
     S2M2_REQUIRE(d->dtype == S2M2_F16 && (d->C == 128 || d->C == 256), "conv_block: C=%d dtype=%d (fp16, C = 128 / 256)", d->C, d->dtype);
-    S2M2_REQUIRE(d->x && d->out && d->x != d->out, "conv_block: x / out must be distinct non-null tensors");
     S2M2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && (long long)d->N * d->H * d->W < (1LL << 24), "conv_block: bad shape");
-    S2M2_REQUIRE(d->x_stride >= d->C && d->x_stride % 8 == 0 && d->out_stride >= d->C && d->out_stride % 4 == 0, "conv_block: pixel strides");
-    S2M2_REQUIRE(d->w_conv0 && d->w_conv2 && d->w_1x0 && d->w_1x2, "conv_block: null weight");
+    const long long pixels = (long long)d->N * d->H * d->W;
+    constexpr const char* E = "conv_block";
+    // x is loaded in 16-byte pieces, out is stored 8 bytes at a time
+    if (check_activation(E, "x", d->x, d->x_stride, pixels, d->C) || check_activation(E, "out", d->out, d->out_stride, pixels, d->C, 8)) return 1;
+    if (check_weight_stream(E, "w_conv0", d->w_conv0) || check_weight_stream(E, "w_conv2", d->w_conv2) || check_weight_stream(E, "w_1x0", d->w_1x0) ||
+        check_weight_stream(E, "w_1x2", d->w_1x2)) return 1;
+    if (check_disjoint(E, "x", d->x, d->x_stride, d->out, d->out_stride, pixels, d->C)) return 1;
     CbArgs a;
     a.x = static_cast<const half_t*>(d->x); a.out = static_cast<half_t*>(d->out); a.xs = d->x_stride; a.os = d->out_stride;
     a.N = d->N; a.H = d->H; a.W = d->W;
@@ -294,9 +270,9 @@ static int conv_block_impl(const s2m2_convblock_desc* d, void* stream) {
     const long long b4 = (long long)d->N * ((d->W + 31) / 32) * ((d->H + 3) / 4);
     return (d->patch_rows == 4 || (d->patch_rows != 2 && b4 >= 128)) ? launch_cb<128, 4>(a, st) : launch_cb<128, 2>(a, st);
 }
+// the name a recording stores for this call and the name the loader's table maps back (plan.h): one constant, so the two cannot drift apart
+static constexpr char kConvBlockEntry[] = "s2m2_conv_block";
 extern "C" int s2m2_conv_block(const s2m2_convblock_desc* d, void* stream) {
-    return s2m2::plan_dispatch_desc<s2m2_convblock_desc>("s2m2_conv_block", &conv_block_impl, d, stream);
+    return s2m2::plan_dispatch_desc<s2m2_convblock_desc>(kConvBlockEntry, &conv_block_impl, d, stream);
 }
-
-// recordable entry points of this file (plan.h: the table engine files are loaded through)
-S2M2_PLAN_DESC_ENTRY("s2m2_conv_block", conv_block_impl)
+S2M2_PLAN_DESC_ENTRY(kConvBlockEntry, conv_block_impl)

@@ -45,9 +45,9 @@ struct GruCfg {
     static constexpr int RH = VERT ? PH + 2 : PH, RW = VERT ? PW : PW + 2, NR = RH * RW, MTR = (NR + 31) / 32;   // patch + ring (r * h)
     static constexpr int TH = VERT ? PH + 4 : PH, TW = VERT ? PW : PW + 4, NTILE = TH * TW;             // input tiles
     static constexpr int TAPS = VERT ? TW : 1;                                                          // tile pixels between two taps
-    static constexpr int RS = C + 8, CRS = C + 8;                                                       // LDS row strides (elements)
-    static constexpr int PPX = C / 8, RPI = NT / PPX, A_IT = (NTILE + RPI - 1) / RPI, AROWS = A_IT * RPI;
-    static constexpr size_t A_BYTES = (size_t)AROWS * RS * 2;                                           // one input tile
+    using Halo = HaloGeom<NT, C, NTILE>;                                                                // one input tile and its loader (frag_ring.h)
+    static constexpr int RS = Halo::RS, CRS = C + 8, PPX = Halo::PPX, RPI = Halo::RPI, A_IT = Halo::A_IT, AROWS = Halo::AROWS;
+    static constexpr size_t A_BYTES = Halo::A_BYTES;
     static constexpr size_t STAGE_BYTES = (size_t)NP * CRS * 2;                                         // z / tanh staging (alias the tiles)
     static constexpr size_t OFF_X = A_BYTES, OFF_B = 2 * A_BYTES, LDS_BYTES = OFF_B + 3 * C * 4;
     static constexpr int PCR = C / 8, SP = NP * PCR / NT;                                               // staged pieces per thread
@@ -63,9 +63,7 @@ __device__ __forceinline__ void gru_layer(float16_t (&acc)[MT], const half_t* t0
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    // slots 0 .. KS-2 only: slot KS-1 gets its first request from step 0 (convblock.hip)
-#pragma unroll
-    for (int s = 0; s < KS - 1; ++s) global_load16_async(ring[s], wf + (size_t)s * 64);
+    ring_start(ring, wf);
     int g = 0;
 #pragma unroll 1
     for (int chunk = 0; chunk < 2; ++chunk) {
@@ -73,9 +71,7 @@ __device__ __forceinline__ void gru_layer(float16_t (&acc)[MT], const half_t* t0
 #pragma unroll 1
         for (int tap = 0; tap < CFG::NTAP; ++tap) cb_steps<MT, KS>(acc, t + tap * CFG::TAPS * CFG::RS, poff, ring, wf, g, CFG::NFRAG);
     }
-    wait_vmcnt<0>();                                             // the ring holds re-requests of the stream's tail: drain
-#pragma unroll
-    for (int s = 0; s < KS; ++s) settle(ring[s]);
+    ring_drain(ring);
 }
 
 // fp16(ACT(acc + bias)) of one accumulator tile, packed as the lane holds it (quad gq: couts 8 gq + 4 hi .. + 3 of the wave's 32).  The empty
@@ -252,12 +248,14 @@ static int conv_gru_impl(const s2m2_convgru_desc* d, void* stream) {
     S2M2_REQUIRE(d, "conv_gru: null descriptor");
     S2M2_REQUIRE(d->dtype == S2M2_F16 && d->C == 128, "conv_gru: C=%d dtype=%d (fp16, C = 128)", d->C, d->dtype);
     S2M2_REQUIRE((d->KH == 3 && d->KW == 1) || (d->KH == 1 && d->KW == 3), "conv_gru: %d x %d taps (3 x 1 or 1 x 3)", d->KH, d->KW);
-    S2M2_REQUIRE(d->h && d->x && d->out && d->out != d->h && d->out != d->x, "conv_gru: h / x / out must be non-null, out distinct from both");
     S2M2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && (long long)d->N * d->H * d->W < (1LL << 24), "conv_gru: bad shape");
-    S2M2_REQUIRE(d->h_stride >= d->C && d->h_stride % 8 == 0 && d->x_stride >= d->C && d->x_stride % 8 == 0 && d->out_stride >= d->C &&
-                 d->out_stride % 8 == 0, "conv_gru: pixel strides (at least C, multiples of 8)");
-    S2M2_REQUIRE(((uintptr_t)d->h | (uintptr_t)d->x | (uintptr_t)d->out) % 16 == 0, "conv_gru: h / x / out must be 16-byte aligned");
-    S2M2_REQUIRE(d->w_zr && d->w_q, "conv_gru: null weight");
+    const long long pixels = (long long)d->N * d->H * d->W;
+    constexpr const char* E = "conv_gru";
+    if (check_activation(E, "h", d->h, d->h_stride, pixels, d->C) || check_activation(E, "x", d->x, d->x_stride, pixels, d->C) ||
+        check_activation(E, "out", d->out, d->out_stride, pixels, d->C)) return 1;
+    if (check_weight_stream(E, "w_zr", d->w_zr) || check_weight_stream(E, "w_q", d->w_q)) return 1;
+    if (check_disjoint(E, "h", d->h, d->h_stride, d->out, d->out_stride, pixels, d->C) ||
+        check_disjoint(E, "x", d->x, d->x_stride, d->out, d->out_stride, pixels, d->C)) return 1;
     GruArgs a;
     a.h = static_cast<const half_t*>(d->h); a.x = static_cast<const half_t*>(d->x); a.out = static_cast<half_t*>(d->out);
     a.hs = d->h_stride; a.xs = d->x_stride; a.os = d->out_stride;

@@ -38,42 +38,15 @@ struct CtCfg {
     static constexpr int C = C_, PH = PH_, PW = PW_, NW = C_ / 32, NT = 64 * NW, KS = 8, CH = 128, NCHUNK = C_ / 128;
     static constexpr int NP = PH * PW, MT = NP / 32;                                         // output patch, MFMA pixel tiles (raster order)
     static constexpr int HH = PH + 2, HW = PW + 2, NHALO = HH * HW;                          // halo tile of t
-    static constexpr int RS = CH + 8, TRS = C + 8;                                           // LDS row strides (elements)
-    static constexpr int PPX = CH / 8, RPI = NT / PPX, A_IT = (NHALO + RPI - 1) / RPI, AROWS = A_IT * RPI;
-    static constexpr size_t A_BYTES = (size_t)AROWS * RS * 2;                                // halo tile (one 128-channel chunk)
+    using Halo = HaloGeom<NT, CH, NHALO>;                                                    // one 128-channel chunk of it and its loader (frag_ring.h)
+    static constexpr int RS = Halo::RS, TRS = C + 8, PPX = Halo::PPX, RPI = Halo::RPI, A_IT = Halo::A_IT, AROWS = Halo::AROWS;
+    static constexpr size_t A_BYTES = Halo::A_BYTES;
     static constexpr size_t Z_BYTES = (size_t)NP * TRS * 2;                                  // z tile = ReLU tile = staging tile: [NP][TRS]
     static constexpr size_t OFF_B = ((A_BYTES > Z_BYTES ? A_BYTES : Z_BYTES) + 15) / 16 * 16, LDS_BYTES = OFF_B + 3 * C * 4;
     static constexpr int ZP = C / 8, SP = NP * ZP / NT;                                      // 16-byte pieces per pixel / per thread (z tile, store)
-    static_assert(NP % 32 == 0 && NP * ZP % NT == 0 && NT % PPX == 0 && LDS_BYTES <= 160 * 1024, "conv block tail tile");
+    static_assert(NP % 32 == 0 && NP * ZP % NT == 0 && LDS_BYTES <= 160 * 1024, "conv block tail tile");
     static_assert(C != 128 || LDS_BYTES <= 80 * 1024, "C = 128: two blocks per CU");
 };
-
-// a 1x1 layer on the patch: MT pixel tiles of `tile` ([NP][TRS]) against this wave's K9 fragments, eight at a time as ordinary tracked loads
-template <typename CFG>
-__device__ __forceinline__ void tail_1x1(float16_t (&acc)[CFG::MT], const half_t* tile, const raw16_t* wf, int l31, int hi) {
-    constexpr int KS = CFG::KS, MT = CFG::MT;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll 1
-    for (int c8 = 0; c8 < CFG::C / 16; c8 += KS) {
-        raw16_t wr[KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s) wr[s] = global_load16(wf + (size_t)(c8 + s) * 64);
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            Frag<half_t> wfr;
-            wfr.v = __builtin_bit_cast(half8_t, wr[s]);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                Frag<half_t> xf;
-                load_frag(xf, tile + (size_t)(32 * i + l31) * CFG::TRS + hi * 8 + (c8 + s) * 16);
-                mma32(acc[i], wfr, xf);
-            }
-        }
-    }
-}
 
 template <typename CFG>
 __global__ __launch_bounds__(CFG::NT, 2) void conv_tail_kernel(CtArgs p) {
@@ -125,7 +98,7 @@ __global__ __launch_bounds__(CFG::NT, 2) void conv_tail_kernel(CtArgs p) {
     unsigned s1[MT][8];
     {
         float16_t accA[MT];
-        tail_1x1<CFG>(accA, Zt, p.wa + (size_t)wv * (C / 16) * 64 + lane, l31, hi);
+        tile_1x1<MT, KS, C, TRS>(accA, Zt, p.wa + (size_t)wv * (C / 16) * 64 + lane, l31, hi);
         __syncthreads();                                         // every wave is done with the z tile (the ReLU tile aliases it)
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -141,7 +114,7 @@ __global__ __launch_bounds__(CFG::NT, 2) void conv_tail_kernel(CtArgs p) {
         }
         __syncthreads();
         float16_t accB[MT];
-        tail_1x1<CFG>(accB, Zt, p.wb + (size_t)wv * (C / 16) * 64 + lane, l31, hi);
+        tile_1x1<MT, KS, C, TRS>(accB, Zt, p.wb + (size_t)wv * (C / 16) * 64 + lane, l31, hi);
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -181,7 +154,7 @@ __global__ __launch_bounds__(CFG::NT, 2) void conv_tail_kernel(CtArgs p) {
     const int nfrag = NCHUNK * 9 * KS;
     const raw16_t* wf = p.w2 + (size_t)wv * nfrag * 64 + lane;
     raw16_t ring[KS];
-    // slots 0 .. KS-2 only: slot KS-1 gets its first request from step 0 (convblock.hip).  The halo tile's tracked loads are younger, so the
+    // frag_ring.h: ring_start, kept inline (the call moves this kernel's code object).  The halo tile's tracked loads are younger, so the
     // compiler's waits at the stash cover the ring as well (conv.hip)
 #pragma unroll
     for (int s = 0; s < KS - 1; ++s) global_load16_async(ring[s], wf + (size_t)s * 64);
@@ -214,9 +187,7 @@ __global__ __launch_bounds__(CFG::NT, 2) void conv_tail_kernel(CtArgs p) {
             if (++kx == 3) { kx = 0; ++ky; }
         }
     }
-    wait_vmcnt<0>();                                             // the ring holds re-requests of the stream's tail: drain
-#pragma unroll
-    for (int s = 0; s < KS; ++s) settle(ring[s]);
+    ring_drain(ring);
     __syncthreads();                                             // the staging tile aliases the halo tile
 
     // ---- epilogue: out = fp16(fp16(convs.2 + b2) + s1): K5's EPI_ADD on K9's output, staged for coalesced 16-byte stores
@@ -262,27 +233,6 @@ static int launch_ct_patch(const CtArgs& a, hipStream_t st, ConvTailPatch pt) {
     return pt.ph == 4 ? launch_ct<C, 4, 32>(a, st) : launch_ct<C, 2, 32>(a, st);
 }
 
-// one validator per operand kind.  An activation tensor: non-null, 16-byte aligned, a pixel stride the 16-byte loaders can take
-static int tail_tensor(const char* name, const void* ptr, long long stride, long long pixels, int C) {
-    S2M2_REQUIRE(ptr, "conv_block_tail: %s is null", name);
-    S2M2_REQUIRE((uintptr_t)ptr % 16 == 0, "conv_block_tail: %s must be 16-byte aligned", name);
-    S2M2_REQUIRE(stride >= C && stride % 8 == 0, "conv_block_tail: %s_stride=%lld (at least C = %d and a multiple of 8)", name, stride, C);
-    S2M2_REQUIRE(pixels * stride < (1LL << 31), "conv_block_tail: %s spans 2^31 elements or more", name);
-    return 0;
-}
-static int tail_weight(const char* name, const void* ptr) {
-    S2M2_REQUIRE(ptr, "conv_block_tail: %s is null", name);
-    S2M2_REQUIRE((uintptr_t)ptr % 16 == 0, "conv_block_tail: %s must be 16-byte aligned", name);
-    return 0;
-}
-// out shares no byte with the input `name` (blocks read the halo of t / the patch of z that other blocks write)
-static int tail_disjoint(const char* name, const void* in, long long in_stride, const void* out, long long out_stride, long long pixels, int C) {
-    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)((pixels - 1) * in_stride + C) * 2;
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)((pixels - 1) * out_stride + C) * 2;
-    S2M2_REQUIRE(o1 <= a0 || a1 <= o0, "conv_block_tail: out aliases %s", name);
-    return 0;
-}
-
 }  // namespace s2m2
 
 extern "C" int s2m2_conv_block_tail_supported(int C, int H, int W, int dtype) {
@@ -296,11 +246,12 @@ static int conv_block_tail_impl(const s2m2_convtail_desc* d, void* stream) {
     S2M2_REQUIRE(d->C == 128 || d->C == 256, "conv_block_tail: C=%d (128 or 256)", d->C);
     S2M2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && (long long)d->N * d->H * d->W < (1LL << 24), "conv_block_tail: bad shape");
     const long long pixels = (long long)d->N * d->H * d->W;
-    if (tail_tensor("t", d->t, d->t_stride, pixels, d->C) || tail_tensor("z", d->z, d->z_stride, pixels, d->C) ||
-        tail_tensor("out", d->out, d->out_stride, pixels, d->C)) return 1;
-    if (tail_weight("w_conv2", d->w_conv2) || tail_weight("w_1x0", d->w_1x0) || tail_weight("w_1x2", d->w_1x2)) return 1;
-    if (tail_disjoint("t", d->t, d->t_stride, d->out, d->out_stride, pixels, d->C) ||
-        tail_disjoint("z", d->z, d->z_stride, d->out, d->out_stride, pixels, d->C)) return 1;
+    constexpr const char* E = "conv_block_tail";
+    if (check_activation(E, "t", d->t, d->t_stride, pixels, d->C, 16, true) || check_activation(E, "z", d->z, d->z_stride, pixels, d->C, 16, true) ||
+        check_activation(E, "out", d->out, d->out_stride, pixels, d->C, 16, true)) return 1;
+    if (check_weight_stream(E, "w_conv2", d->w_conv2) || check_weight_stream(E, "w_1x0", d->w_1x0) || check_weight_stream(E, "w_1x2", d->w_1x2)) return 1;
+    if (check_disjoint(E, "t", d->t, d->t_stride, d->out, d->out_stride, pixels, d->C) ||
+        check_disjoint(E, "z", d->z, d->z_stride, d->out, d->out_stride, pixels, d->C)) return 1;
     const bool forced = d->patch_rows != 0 || d->patch_cols != 0;
     const ConvTailPatch pt = conv_tail_patch(d->N, d->H, d->W, d->C, d->patch_rows, d->patch_cols);
     S2M2_REQUIRE(!forced || (pt.ph == d->patch_rows && pt.pw == d->patch_cols), "conv_block_tail: patch %d x %d (2 x 32, 4 x 32 or 4 x 40)",

@@ -52,4 +52,33 @@ static int bind_zero_page(Args& a, const char* what) {
     return 0;
 }
 
+// One validator per operand kind of the fused convolution entry points (K14, K17, K19): the C ABI is their boundary, engine files reach it with
+// no binding in front.  `entry` prefixes the message: "<entry>: <operand> ...".
+// An activation tensor of `pixels` pixels x C fp16 channels, `stride` elements from pixel to pixel: non-null; `align`-byte aligned with a pixel
+// stride that keeps every pixel so (16 for what the kernel moves in 16-byte pieces, 8 for K14's 8-byte stores); with offsets32, a span below
+// 2^31 elements (the kernel indexes it with 32-bit offsets).
+static inline int check_activation(const char* entry, const char* name, const void* ptr, long long stride, long long pixels, int C, int align = 16,
+                                   bool offsets32 = false) {
+    S2M2_REQUIRE(ptr, "%s: %s is null", entry, name);
+    S2M2_REQUIRE((uintptr_t)ptr % align == 0, "%s: %s must be %d-byte aligned", entry, name, align);
+    S2M2_REQUIRE(stride >= C && stride % (align / 2) == 0, "%s: %s_stride=%lld (at least C = %d and a multiple of %d)", entry, name, stride, C, align / 2);
+    S2M2_REQUIRE(!offsets32 || pixels * stride < (1LL << 31), "%s: %s spans 2^31 elements or more", entry, name);
+    return 0;
+}
+// A weight fragment stream: read in 16-byte pieces
+static inline int check_weight_stream(const char* entry, const char* name, const void* ptr) {
+    S2M2_REQUIRE(ptr, "%s: %s is null", entry, name);
+    S2M2_REQUIRE((uintptr_t)ptr % 16 == 0, "%s: %s must be 16-byte aligned", entry, name);
+    return 0;
+}
+// out shares no byte with the input `name`: a block reads halo pixels of the input that another block's patch covers, so even a partial overlap
+// is a race between blocks
+static inline int check_disjoint(const char* entry, const char* name, const void* in, long long in_stride, const void* out, long long out_stride,
+                                 long long pixels, int C) {
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)((pixels - 1) * in_stride + C) * 2;
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)((pixels - 1) * out_stride + C) * 2;
+    S2M2_REQUIRE(o1 <= a0 || a1 <= o0, "%s: out aliases %s", entry, name);
+    return 0;
+}
+
 }  // namespace s2m2

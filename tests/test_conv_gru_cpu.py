@@ -36,9 +36,13 @@ def test_descriptor_has_the_layout_of_the_header(tmp_path):
     assert out[1:] == [getattr(hip.ConvGruDesc, f).offset for f in fields]
 
 
+HP, XP, OUT = 1 << 20, 2 << 20, 3 << 20                            # far enough apart for the byte ranges of 8 x 20 x 128 tensors
+SPAN = 8 * 20 * 128 * 2
+
+
 def _desc(**kw):
     d = hip.ConvGruDesc()
-    d.h, d.x, d.out, d.w_zr, d.w_q = 4096, 8192, 12288, 4096, 4096
+    d.h, d.x, d.out, d.w_zr, d.w_q = HP, XP, OUT, 4096, 4096
     d.h_stride = d.x_stride = d.out_stride = 128
     d.N, d.H, d.W, d.C, d.KH, d.KW, d.dtype = 1, 8, 20, 128, 3, 1, hip.F16
     for k, v in kw.items():
@@ -52,9 +56,12 @@ def test_argument_validation_runs_before_any_device_call(lib):
     assert lib.s2m2_conv_gru_supported(128, 0, 304, hip.F16) == 0
     assert lib.s2m2_conv_gru(None, None) != 0 and b"null descriptor" in lib.s2m2_last_error()
     for kw, msg in (({"C": 64}, b"C=64"), ({"dtype": hip.F32}, b"fp16"), ({"KH": 3, "KW": 3}, b"3 x 1 or 1 x 3"), ({"KH": 1, "KW": 1}, b"3 x 1 or 1 x 3"),
-                    ({"x": None}, b"non-null"), ({"out": 4096}, b"distinct"), ({"out": 8192}, b"distinct"), ({"H": 0}, b"bad shape"),
-                    ({"N": 1 << 12, "H": 1 << 6, "W": 1 << 6}, b"bad shape"), ({"h_stride": 120}, b"pixel strides"), ({"x_stride": 132}, b"pixel strides"),
-                    ({"out_stride": 64}, b"pixel strides"), ({"h": 4100}, b"16-byte aligned"), ({"w_q": None}, b"null weight"), ({"w_zr": None}, b"null weight")):
+                    ({"x": None}, b"x is null"), ({"out": HP}, b"out aliases h"), ({"out": XP}, b"out aliases x"), ({"H": 0}, b"bad shape"),
+                    ({"N": 1 << 12, "H": 1 << 6, "W": 1 << 6}, b"bad shape"), ({"h_stride": 120}, b"h_stride=120"), ({"x_stride": 132}, b"x_stride=132"),
+                    ({"out_stride": 64}, b"out_stride=64"), ({"h": HP + 4}, b"h must be 16-byte aligned"), ({"w_q": None}, b"w_q is null"),
+                    ({"w_zr": None}, b"w_zr is null"),
+                    ({"out": HP + SPAN - 16}, b"out aliases h"),          # out starts on the last 16 bytes of h
+                    ({"out": XP - SPAN + 16}, b"out aliases x")):         # out ends 16 bytes into x
         assert lib.s2m2_conv_gru(ctypes.byref(_desc(**kw)), None) != 0, kw
         assert msg in lib.s2m2_last_error(), (kw, lib.s2m2_last_error())
 

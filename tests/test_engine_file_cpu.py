@@ -90,7 +90,7 @@ def test_every_recorded_entry_point_is_in_the_loader_table():
                 registered.append(name)
                 assert re.search(rf'plan_dispatch(?:_desc)?(?:<\w+>)?\("{name}", &{impl}\b', src), (f, name, impl)
     assert sorted(registered) == _recorded_names()
-    assert len(registered) == 23
+    assert len(registered) == 22                                      # K14, K17 and K19 register through a constant: their own *_cpu.py tests
 
 
 def test_engine_structs_have_the_layout_of_the_header(tmp_path):

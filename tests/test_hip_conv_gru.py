@@ -111,11 +111,11 @@ def test_conv_gru_refuses_what_it_does_not_take(hip):
         hip.conv_gru(h64, h64.clone(), w64, None, w64[:64 * 64 * 3 * 2], None, 1, 3)
     with pytest.raises(RuntimeError, match="3 x 1 or 1 x 3"):
         _raw(hip, h, x, w_zr, w_q, KH=1, KW=1)
-    with pytest.raises(RuntimeError, match="non-null"):
+    with pytest.raises(RuntimeError, match="x is null"):
         _raw(hip, h, None, w_zr, w_q)
-    with pytest.raises(RuntimeError, match="null weight"):
+    with pytest.raises(RuntimeError, match="w_q is null"):
         _raw(hip, h, x, w_zr, None)
-    with pytest.raises(RuntimeError, match="distinct"):
+    with pytest.raises(RuntimeError, match="out aliases h"):
         _raw(hip, h, x, w_zr, w_q, out=h)
 
 

@@ -65,6 +65,28 @@ def test_conv_block_equals_the_three_launches_bit_for_bit(hip, case):
     assert torch.equal(got, ref), float((got.float() - ref.float()).abs().max())
 
 
+@pytest.mark.parametrize("ph", [2, 4])
+def test_conv_block_on_a_channel_slice_and_replayed_from_a_plan(hip, ph):
+    """x as channels 8:136 of a 136-channel tensor (pixel stride 136, not C), no biases; 5 x 33 pixels: partial patches in both directions, one
+    full and one partial 32-column tile.  Then the same call from a recorded plan."""
+    C = 128
+    k0, k2, p0, p2, bs = _layers(C, 11, bias=False)
+    wide = (torch.randn(1, 5, 33, C + 8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(ph)) * 1.3 + 0.2).half()
+    x = wide[..., 8:]
+    assert x.stride(2) == C + 8 and not x.is_contiguous()
+    ref, (w0, w2, a0, a2) = _triple(hip, x.contiguous(), k0, k2, p0, p2, bs)
+    got = hip.conv_block(x, w0, None, w2, None, a0, None, a2, None, patch_rows=ph)
+    assert torch.equal(got, ref), float((got.float() - ref.float()).abs().max())
+    plan = hip.Plan()
+    with plan.record([x]):
+        y = hip.conv_block(x, w0, None, w2, None, a0, None, a2, None, patch_rows=ph)
+    assert plan.launches == 1 and plan.patches(0) == 1
+    assert torch.equal(y, got)
+    y.zero_()
+    plan.run([x])
+    assert torch.equal(y, got)
+
+
 def test_conv_block_vs_torch(hip):
     N, H, W, C = 1, 30, 41, 128
     k0, k2, p0, p2, bs = _layers(C, 3)
