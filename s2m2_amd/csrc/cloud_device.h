@@ -1,22 +1,15 @@
-// Device functions shared by K15 (cloud.hip) and K20 (mesh.hip): the per-pixel chain of include/s2m2_hip.h (keep, z, x, y, colour bytes), the
-// pixel -> thread map and the block reductions.  Both kernels compile THESE functions, so that the vertex records of s2m2_mesh are byte-identical
-// to the records of s2m2_cloud whatever the compiler does with the arithmetic.
-// Pixel -> thread map: a thread owns four consecutive pixels of one row, placed so that their MAP column is a multiple of four whatever the crop
-// offset is (the first group of a row starts (Wp-W)/2 % 4 pixels left of the image): with Wp % 4 == 0 every map read is one aligned 16-byte
-// load that stays inside the padded row.
+// Device functions shared by K15 (cloud.hip) and K20 (mesh.hip): the per-pixel chain of include/s2m2_hip.h (keep, z, x, y, colour bytes) and the
+// record.  Both kernels compile THESE functions, so that the vertex records of s2m2_mesh are byte-identical to the records of s2m2_cloud
+// whatever the compiler does with the arithmetic.  The pixel -> thread map, the loads and stores of a thread's four pixels, the block
+// reductions and the rank step are raster_tiles.h's, which K18 shares.
 #pragma once
-#include "common.h"
+#include "raster_tiles.h"
 
 namespace s2m2 {
 
-constexpr int kCloudThreads = 256;                       // four waves
-constexpr int kCloudChunk = kCloudThreads * 4;           // pixels of one block step
-constexpr int kCloudTilePixels = 4096;                   // a tile: as many whole rows as fit (at least one)
-
-static inline int cloud_tile_rows(int W) { return W >= kCloudTilePixels ? 1 : kCloudTilePixels / W; }
+constexpr int kCloudTilePixels = 4096;                   // K15's tile (raster_host.h: tile_rows)
 
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
-typedef unsigned char uchar4_t __attribute__((ext_vector_type(4)));
 
 struct CloudParams {
     const float* disp;
@@ -39,7 +32,7 @@ struct CloudParams {
 
 // z of one pixel, or 0 when it is not kept (keep <=> z > 0): the arithmetic of the header, one fp32 rounding per operation
 __device__ __forceinline__ float cloud_z(const CloudParams& p, float disp, float occ, float conf) {
-    const bool valid = p.unfiltered || (conf > p.conf_min && occ > p.occ_min);
+    const bool valid = p.unfiltered || cloud_valid(conf, occ, p.conf_min, p.occ_min);
     const float d = valid ? disp : -1.f;
     const float depth = d <= 0.f ? 1e9f : p.bf / (d + p.doffs);
     const float z = depth / p.depth_scale;
@@ -50,21 +43,11 @@ __device__ __forceinline__ float cloud_z(const CloudParams& p, float disp, float
 // map's disparity d
 template <bool VEC>
 __device__ __forceinline__ void cloud_eval4d(const CloudParams& p, int b, int v, int u0, float z[4], float d[4]) {
-    const size_t m = ((size_t)b * p.Hp + (v + p.oy)) * (size_t)p.Wp + (size_t)(p.ox + u0);      // p.ox + u0 >= 0 by construction
+    const size_t m = raster_map_index(p, b, v, u0);
     float o[4], c[4];
-    if constexpr (VEC) {                                 // aligned and inside the padded row: see the head of the file
-        const raw16_t dv = global_load16(p.disp + m), ov = global_load16(p.occ + m), cv = global_load16(p.conf + m);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { d[j] = dv[j]; o[j] = ov[j]; c[j] = cv[j]; }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool in = u0 + j >= 0 && u0 + j < p.W;
-            d[j] = in ? p.disp[m + j] : 0.f;
-            o[j] = in ? p.occ[m + j] : 0.f;
-            c[j] = in ? p.conf[m + j] : 0.f;
-        }
-    }
+    map_load4<VEC>(p.disp, m, u0, p.W, d);
+    map_load4<VEC>(p.occ, m, u0, p.W, o);
+    map_load4<VEC>(p.conf, m, u0, p.W, c);
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] = (u0 + j >= 0 && u0 + j < p.W) ? cloud_z(p, d[j], o[j], c[j]) : 0.f;
 }
@@ -93,28 +76,34 @@ __device__ __forceinline__ uint4_t cloud_record(const CloudParams& p, const IT* 
     return o;
 }
 
-__device__ __forceinline__ int wave_sum_int(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
+// The dense outputs of the count launches of K15 and K20: z and keep of the thread's four pixels of row v (u0 < W).  VEC carries the alignment
+// of both bases (cloud_validate).
+template <bool VEC>
+__device__ __forceinline__ void cloud_store_dense(const CloudParams& p, int b, int v, int u0, const float z[4]) {
+    const size_t row = raster_dense_row(p, b, v);
+    if (p.depth) dense_store4(p.depth, row, u0, p.W, VEC, z);
+    if (p.mask) {
+        const unsigned char k[4] = {(unsigned char)(z[0] > 0.f), (unsigned char)(z[1] > 0.f), (unsigned char)(z[2] > 0.f), (unsigned char)(z[3] > 0.f)};
+        dense_store4(p.mask, row, u0, p.W, VEC, k);
+    }
 }
 
-// sum over the block of one int per thread, result in every thread (red: kCloudThreads / 64 ints of LDS, not reused before the next barrier)
-__device__ __forceinline__ int block_sum_int(int x, int* red) {
-    x = wave_sum_int(x);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < kCloudThreads / 64; ++w) s += red[w];
-    return s;
-}
+// K20's parameters: K15's, the faces and the dense rank map that K15's scatter kernel fills for it
+struct MeshParams {
+    CloudParams c;
+    int* faces;                 // (B, face_capacity, 3)
+    int* face_count;
+    int* rank;                  // (B, H, W): the dense rank map
+    int* tile_faces;            // faces per tile, behind the vertex counts in the workspace
+    long long face_capacity;
+    float max_jump;
+    int rank_vec;               // the rank map is 16-byte aligned: aligned groups of four take one load / store
+};
 
-// the header's checks of a s2m2_cloud_desc, shared by s2m2_cloud and s2m2_mesh (`what` prefixes the messages); fills p
-int cloud_validate(const s2m2_cloud_desc* d, const char* what, CloudParams& p, bool& vec);
-
-static inline bool cloud_extents_ok(int B, int H, int W) {
-    return B > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && B <= 65535;
-}
+// cloud.hip.  The header's checks of a s2m2_cloud_desc, shared by s2m2_cloud and s2m2_mesh (`what` prefixes the messages); fills p, with the
+// tile geometry of tile_pixels
+int cloud_validate(const s2m2_cloud_desc* d, const char* what, int tile_pixels, CloudParams& p, bool& vec);
+// K20's vertex launch: cloud_scatter_kernel with the rank-map option on mp's tile geometry
+int mesh_vertices(const MeshParams& mp, bool vec, int image_dtype, dim3 grid, hipStream_t stream);
 
 }  // namespace s2m2

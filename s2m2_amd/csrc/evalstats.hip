@@ -11,12 +11,10 @@
 // In LDS the confidence table is kept as LEVELS: level k = the number of thresholds a pixel's error exceeds (thresholds increase strictly, so
 // bad[t] <=> k > t; a non-finite prediction has k = nthr).  One add per pixel stands for the count and all eight bad counters of the row; the
 // block turns levels into count / bad[t] when it stores its partial block.
-// Pixel -> thread map: as in K15 (cloud.hip) a thread owns four consecutive pixels of one row, placed so that their MAP column is a multiple of
-// four whatever the crop offset is: with Wp % 4 == 0 every map read is one aligned 16-byte load that stays inside the padded row.  gt and region
-// follow the unpadded rows: one 16-byte / 4-byte load where a whole group is aligned, per pixel otherwise.
+// Pixel -> thread map, map loads and the loads of gt and region (which follow the unpadded rows): raster_tiles.h, shared with K15 and K20.
 #include <math.h>
 
-#include "common.h"
+#include "raster_tiles.h"
 #include "launch.h"
 #include "plan.h"
 
@@ -24,10 +22,8 @@ namespace s2m2 {
 
 typedef unsigned long long u64;
 
-constexpr int kEvalThreads = 256;                        // four waves
-constexpr int kEvalChunk = kEvalThreads * 4;             // pixels of one block step
-constexpr int kEvalTilePixels = 4096;                    // a tile: as many whole rows as fit (at least one) ...
-constexpr int kEvalMaxTiles = 1024;                      // ... and more of them where a pair would have more tiles than this (launch B's loop)
+constexpr int kEvalTilePixels = 4096;                    // a tile (raster_host.h: tile_rows_capped) ...
+constexpr int kEvalMaxTiles = 1024;                      // ... with more rows where a pair would have more tiles than this (launch B's loop)
 constexpr int kEvalLevels = S2M2_EVAL_MAX_THR + 1;
 constexpr int kEvalWide = 4 + S2M2_EVAL_CONF_BINS;       // ALL and KEPT: SUM_ABS_Q, SUM_SQ_Q; CONF: SUM_ABS_Q of every row
 constexpr int kEvalPartLo = S2M2_EVAL_WORDS;
@@ -39,15 +35,7 @@ static_assert(S2M2_EVAL_KEPT == S2M2_EVAL_ALL + S2M2_EVAL_BLOCK_WORDS && S2M2_EV
 static_assert(S2M2_EVAL_CONF == S2M2_EVAL_HIST + S2M2_EVAL_HIST_BINS, "stat block layout");
 static_assert(S2M2_EVAL_WORDS == S2M2_EVAL_CONF + S2M2_EVAL_CONF_BINS * S2M2_EVAL_CONF_ROW_WORDS, "stat block layout");
 
-static inline bool eval_extents_ok(int B, int H, int W) {
-    return B > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && B <= 65535;
-}
-
-static inline int eval_tile_rows(int H, int W) {
-    int rows = W >= kEvalTilePixels ? 1 : kEvalTilePixels / W;
-    if ((H + rows - 1) / rows > kEvalMaxTiles) rows = (H + kEvalMaxTiles - 1) / kEvalMaxTiles;
-    return rows;
-}
+static inline int eval_tile_rows(int H, int W) { return tile_rows_capped(H, W, kEvalTilePixels, kEvalMaxTiles); }
 
 // index of stat word w among the high halves of a partial block, or -1: the word is a count
 __host__ __device__ __forceinline__ int eval_wide_index(int w) {
@@ -75,12 +63,6 @@ struct EvalParams {
     float thr[S2M2_EVAL_MAX_THR];       // slots t >= nthr hold +inf: never exceeded
     float d1_abs, d1_rel, gt_min, conf_min, occ_min;
 };
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 __device__ __forceinline__ bool eval_finite(float x) { return fabsf(x) < INFINITY; }      // false for NaN
 
@@ -140,75 +122,44 @@ __device__ __forceinline__ void eval_load(const EvalParams& p, int b, int v, int
 #pragma unroll
     for (int j = 0; j < 4; ++j) { x.d[j] = 0.f; x.o[j] = 0.f; x.c[j] = 0.f; x.g[j] = 0.f; x.r[j] = 1u; }
     if (u0 >= p.W) return;
-    const size_t row = ((size_t)b * p.H + v) * (size_t)p.W;                                // of gt and region
-    const size_t mrow = ((size_t)b * p.Hp + (v + p.oy)) * (size_t)p.Wp + (size_t)p.ox;     // of the maps, at image column 0
-    if constexpr (VEC) {                                 // aligned and inside the padded row: see the head of the file (mrow + u0 >= 0)
-        const raw16_t dv = global_load16(p.disp + (mrow + u0));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x.d[j] = dv[j];
-        if constexpr (CONF) {
-            const raw16_t ov = global_load16(p.occ + (mrow + u0)), cv = global_load16(p.conf + (mrow + u0));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { x.o[j] = ov[j]; x.c[j] = cv[j]; }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (u0 + j >= 0 && u0 + j < p.W) {
-                x.d[j] = p.disp[mrow + u0 + j];
-                if constexpr (CONF) { x.o[j] = p.occ[mrow + u0 + j]; x.c[j] = p.conf[mrow + u0 + j]; }
-            }
-        }
+    const size_t row = raster_dense_row(p, b, v), m = raster_map_index(p, b, v, u0);
+    map_load4<VEC>(p.disp, m, u0, p.W, x.d);
+    if constexpr (CONF) {
+        map_load4<VEC>(p.occ, m, u0, p.W, x.o);
+        map_load4<VEC>(p.conf, m, u0, p.W, x.c);
     }
-    const bool whole = u0 >= 0 && u0 + 3 < p.W && ((row + u0) & 3) == 0;
-    if (whole && p.gt_vec) {
-        const raw16_t gv = global_load16(p.gt + (row + u0));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x.g[j] = gv[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (u0 + j >= 0 && u0 + j < p.W) x.g[j] = p.gt[row + u0 + j];
-    }
+    dense_load4(p.gt, row, u0, p.W, p.gt_vec != 0, x.g);
     if (p.region) {
-        if (whole && p.region_vec) {
-            const unsigned rv = *reinterpret_cast<const unsigned*>(p.region + (row + u0));
+        unsigned char r[4] = {1, 1, 1, 1};
+        dense_load4(p.region, row, u0, p.W, p.region_vec != 0, r);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) x.r[j] = (rv >> (8 * j)) & 0xffu;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (u0 + j >= 0 && u0 + j < p.W) x.r[j] = p.region[row + u0 + j];
-        }
+        for (int j = 0; j < 4; ++j) x.r[j] = r[j];
     }
 }
 
 template <bool VEC, bool CONF>
-__global__ __launch_bounds__(kEvalThreads) void eval_tile_kernel(const EvalParams p) {
+__global__ __launch_bounds__(kRasterThreads) void eval_tile_kernel(const EvalParams p) {
     __shared__ unsigned hist[S2M2_EVAL_HIST_BINS];
     __shared__ unsigned levels[S2M2_EVAL_CONF_BINS * kEvalLevels];
     __shared__ u64 conf_sum[S2M2_EVAL_CONF_BINS];
     __shared__ u64 words[2 * S2M2_EVAL_BLOCK_WORDS];         // ALL, KEPT
     const int tid = threadIdx.x;
-    for (int i = tid; i < S2M2_EVAL_HIST_BINS; i += kEvalThreads) hist[i] = 0;
-    for (int i = tid; i < S2M2_EVAL_CONF_BINS * kEvalLevels; i += kEvalThreads) levels[i] = 0;
+    for (int i = tid; i < S2M2_EVAL_HIST_BINS; i += kRasterThreads) hist[i] = 0;
+    for (int i = tid; i < S2M2_EVAL_CONF_BINS * kEvalLevels; i += kRasterThreads) levels[i] = 0;
     if (tid < S2M2_EVAL_CONF_BINS) conf_sum[tid] = 0;
     if (tid < 2 * S2M2_EVAL_BLOCK_WORDS) words[tid] = 0;
     __syncthreads();
 
     const int b = blockIdx.y, tile = blockIdx.x;
-    const int shift = p.ox & 3;
-    const int v0 = tile * p.rows_per_tile;
-    // block-uniform steps of kEvalChunk pixels (every lane takes every step: the flushes are whole waves): row by row, left to right
-    const int steps_per_row = (p.W + shift + kEvalChunk - 1) / kEvalChunk;
-    const int steps = (min(p.H, v0 + p.rows_per_tile) - v0) * steps_per_row;
+    // block-uniform steps of kRasterChunk pixels (every lane takes every step: the flushes are whole waves): row by row, left to right
     EvalCounters all, kept;
     EvalPixels cur, next = {};
-    eval_load<VEC, CONF>(p, b, v0, -shift + tid * 4, cur);
-    for (int step = 0, sr = 0, v = v0; step < steps; ++step) {
-        const int u0 = -shift + sr * kEvalChunk + tid * 4;
-        if (++sr == steps_per_row) { sr = 0; ++v; }
-        if (step + 1 < steps) eval_load<VEC, CONF>(p, b, v, -shift + sr * kEvalChunk + tid * 4, next);     // in flight while this step is counted
+    RasterWalk w(p, tile, p.H);                             // (a tile has at least one row)
+    eval_load<VEC, CONF>(p, b, w.v, w.u0(), cur);
+    for (int step = 0; w.more(); ++step) {
+        const int u0 = w.u0();
+        w.next();
+        if (w.more()) eval_load<VEC, CONF>(p, b, w.v, w.u0(), next);         // in flight while this step is counted
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool in_region = u0 + j >= 0 && u0 + j < p.W && cur.r[j] != 0;
@@ -232,7 +183,7 @@ __global__ __launch_bounds__(kEvalThreads) void eval_tile_kernel(const EvalParam
                 atomicAdd(&hist[h >= 1024.f ? 1024 : (int)h], 1u);
             }
             if constexpr (CONF) {
-                const bool keep = cur.c[j] > p.conf_min && cur.o[j] > p.occ_min;
+                const bool keep = cloud_valid(cur.c[j], cur.o[j], p.conf_min, p.occ_min);
                 kept.add(in_region && keep, evaluated && keep, finite, d1, level, q, s);
                 const float cs = cur.c[j] * 64.f;
                 const int cbin = !(cs >= 0.f) ? 0 : (cs >= 63.f ? 63 : (int)cs);          // NaN -> 0
@@ -252,7 +203,7 @@ __global__ __launch_bounds__(kEvalThreads) void eval_tile_kernel(const EvalParam
 
     // the partial block of this tile: low halves in the order of the stat block, then the high halves of the wide words
     unsigned* part = p.part + ((size_t)b * p.tiles + tile) * kEvalPart;
-    for (int w = tid; w < kEvalPart; w += kEvalThreads) {
+    for (int w = tid; w < kEvalPart; w += kRasterThreads) {
         u64 x = 0;
         if (w < S2M2_EVAL_HIST) x = words[w];
         else if (w < S2M2_EVAL_CONF) x = hist[w - S2M2_EVAL_HIST];
@@ -297,15 +248,10 @@ __global__ __launch_bounds__(kEvalSumThreads) void eval_sum_kernel(const unsigne
 
 static int eval_impl(const s2m2_eval_desc* d, void* stream) {
     S2M2_REQUIRE(d != nullptr, "disp_eval: null descriptor");
-    S2M2_REQUIRE(!plan_recording(), "disp_eval: s2m2_disp_eval is not recorded in launch plans -- call it after s2m2_plan_end, behind "
-                                    "s2m2_plan_run / s2m2_engine_run on the same stream");
+    if (int rc = refuse_while_recording("disp_eval")) return rc;
     S2M2_REQUIRE(d->disp && d->gt && d->stats && d->workspace, "disp_eval: null pointer (disp / gt / stats / workspace)");
     S2M2_REQUIRE((d->occ == nullptr) == (d->conf == nullptr), "disp_eval: occ and conf come together (exactly one of them is a null pointer)");
-    S2M2_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Hp > 0 && d->Wp > 0, "disp_eval: non-positive extents B=%d H=%d W=%d Hp=%d Wp=%d", d->B,
-                 d->H, d->W, d->Hp, d->Wp);
-    S2M2_REQUIRE(d->H <= d->Hp && d->W <= d->Wp, "disp_eval: the ground truth (H=%d, W=%d) is larger than the maps (Hp=%d, Wp=%d)", d->H, d->W,
-                 d->Hp, d->Wp);
-    S2M2_REQUIRE(eval_extents_ok(d->B, d->H, d->W) && (long long)d->Hp * d->Wp < (1LL << 31), "disp_eval: extents too large (B <= 65535, H*W < 2^31)");
+    if (int rc = check_padded_maps("disp_eval", "ground truth", d->B, d->H, d->W, d->Hp, d->Wp)) return rc;
     S2M2_REQUIRE(d->nthr >= 0 && d->nthr <= S2M2_EVAL_MAX_THR, "disp_eval: nthr=%d is outside 0..%d", d->nthr, S2M2_EVAL_MAX_THR);
     for (int t = 0; t < d->nthr; ++t)
         S2M2_REQUIRE(isfinite(d->thr[t]) && d->thr[t] > (t ? d->thr[t - 1] : 0.f),
@@ -325,7 +271,7 @@ static int eval_impl(const s2m2_eval_desc* d, void* stream) {
     p.H = d->H; p.W = d->W; p.Hp = d->Hp; p.Wp = d->Wp;
     p.oy = (d->Hp - d->H) / 2; p.ox = (d->Wp - d->W) / 2;
     p.rows_per_tile = eval_tile_rows(d->H, d->W);
-    p.tiles = (d->H + p.rows_per_tile - 1) / p.rows_per_tile;
+    p.tiles = tiles(d->H, p.rows_per_tile);
     p.nthr = d->nthr;
     p.gt_vec = ((uintptr_t)d->gt & 15) == 0;
     p.region_vec = ((uintptr_t)d->region & 3) == 0;
@@ -333,7 +279,7 @@ static int eval_impl(const s2m2_eval_desc* d, void* stream) {
     p.d1_abs = d->d1_abs; p.d1_rel = d->d1_rel; p.gt_min = d->gt_min; p.conf_min = d->conf_min; p.occ_min = d->occ_min;
     const bool vec = d->Wp % 4 == 0 && (((uintptr_t)d->disp | (uintptr_t)d->occ | (uintptr_t)d->conf) & 15) == 0;
     const bool conf = d->conf != nullptr;
-    const dim3 grid(p.tiles, d->B), block(kEvalThreads);
+    const dim3 grid(p.tiles, d->B), block(kRasterThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
     if (vec) rc = conf ? launch<eval_tile_kernel<true, true>>("disp_eval (tiles)", grid, block, 0, s, p)
@@ -347,15 +293,12 @@ static int eval_impl(const s2m2_eval_desc* d, void* stream) {
 
 }  // namespace s2m2
 
-extern "C" int s2m2_eval_tile_rows(int H, int W) {
-    return s2m2::eval_extents_ok(1, H, W) ? s2m2::eval_tile_rows(H, W) : 0;
-}
+extern "C" int s2m2_eval_tile_rows(int H, int W) { return s2m2::raster_extents_ok(1, H, W) ? s2m2::eval_tile_rows(H, W) : 0; }
 
 extern "C" size_t s2m2_eval_workspace_bytes(int B, int H, int W) {
-    if (!s2m2::eval_extents_ok(B, H, W)) return 0;
-    const int rows = s2m2::eval_tile_rows(H, W);
-    const size_t tiles = (size_t)B * ((H + rows - 1) / rows);
-    return (tiles * s2m2::kEvalPart * sizeof(unsigned) + 255) / 256 * 256;
+    using namespace s2m2;
+    if (!raster_extents_ok(B, H, W)) return 0;
+    return round256((size_t)B * tiles(H, eval_tile_rows(H, W)) * kEvalPart * sizeof(unsigned));
 }
 
 extern "C" int s2m2_disp_eval(const s2m2_eval_desc* desc, void* stream) { return s2m2::eval_impl(desc, stream); }

@@ -2,12 +2,12 @@
 // pixels of similar disparity, both compacted in raster order.  Three launches without a host step, atomics or waiting between blocks:
 //   mesh_count_kernel   a block owns a tile of whole image rows and reads one halo row below it: dense depth / mask, the number of kept pixels
 //                       and the number of faces of the tile's quads into the workspace
-//   mesh_vertex_kernel  K15's scatter (prefix over the tile counts, ballot ranks, records through cloud_record) which also stores the rank of
-//                       every pixel (-1: not kept) into the dense rank map: `index`, or the workspace without it
-//   mesh_face_kernel    prefix over the tile face counts, the face rule again from disp and the rank map (rank >= 0 <=> keep), ballot ranks of
-//                       the two candidate slots of every quad, 12-byte stores (ranks run by lane, then by quad and slot: a thread's up to
-//                       eight faces lie back to back and the faces of a wave's step fill one contiguous range)
-// A quad belongs to the thread that owns its top-left pixel (cloud_device.h: four consecutive pixels per thread).  Its right-hand column is the
+//   (vertices)          K15's scatter kernel itself (cloud.hip: cloud_scatter_kernel with the rank-map option) on K20's tiles: the records, and
+//                       the rank of every pixel (-1: not kept) into the dense rank map: `index`, or the workspace without it
+//   mesh_face_kernel    prefix over the tile face counts, the face rule again from disp and the rank map (rank >= 0 <=> keep), ranks of the
+//                       two candidate slots of every quad (raster_rank_step), 12-byte stores (ranks run by lane, then by quad and slot: a
+//                       thread's up to eight faces lie back to back and the faces of a wave's step fill one contiguous range)
+// A quad belongs to the thread that owns its top-left pixel (raster_tiles.h: four consecutive pixels per thread).  Its right-hand column is the
 // first pixel of the next lane (a shuffle); the last lane of a wave reads that pixel itself.  The row below is read by the same thread with the
 // same loads (it is the tile's own next row, or the halo row: served by the cache, not by HBM).
 #include "cloud_device.h"
@@ -16,27 +16,10 @@
 
 namespace s2m2 {
 
-typedef int int4_t __attribute__((ext_vector_type(4)));
-
-constexpr int kMeshThreads = kCloudThreads;              // four waves
-constexpr int kMeshChunk = kMeshThreads * 4;             // pixels of one block step
 // A tile: as many whole rows as fit (at least one).  Half of K15's: the steps of a block run one after the other (every step waits for its
 // loads, then for the barrier of the ranks), and at 1216x1024 the three launches take 51 us with one row per tile, 78 us with three, 122 us
 // with six (profiles/mesh/tile_size.txt); below one row per tile nothing is left to gain, and 2432x2048 does not depend on it
 constexpr int kMeshTilePixels = 2048;
-
-static inline int mesh_tile_rows(int W) { return W >= kMeshTilePixels ? 1 : kMeshTilePixels / W; }
-
-struct MeshParams {
-    CloudParams c;
-    int* faces;                 // (B, face_capacity, 3)
-    int* face_count;
-    int* rank;                  // (B, H, W): the dense rank map
-    int* tile_faces;            // faces per tile, behind the vertex counts in the workspace
-    long long face_capacity;
-    float max_jump;
-    int rank_vec;               // the rank map is 16-byte aligned: aligned groups of four take one load / store
-};
 
 // keep, disparity and (face kernel) rank of the 2 x 5 pixels behind a thread's four quads: [row][column], column 4 = the next lane's first pixel
 struct Corners {
@@ -82,7 +65,7 @@ __device__ __forceinline__ void mesh_corners_from_maps(const CloudParams& p, int
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             if (r == 0 || below) {
-                const size_t m = ((size_t)b * p.Hp + (v + r + p.oy)) * (size_t)p.Wp + (size_t)(p.ox + ur);
+                const size_t m = raster_map_index(p, b, v + r, ur);
                 dr[r] = p.disp[m];
                 zr[r] = cloud_z(p, dr[r], p.occ[m], p.conf[m]);
             }
@@ -98,52 +81,26 @@ __device__ __forceinline__ void mesh_corners_from_maps(const CloudParams& p, int
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(const MeshParams mp) {
-    __shared__ int red_v[kMeshThreads / 64], red_f[kMeshThreads / 64];
+__global__ __launch_bounds__(kRasterThreads) void mesh_count_kernel(const MeshParams mp) {
+    __shared__ int red_v[kRasterWaves], red_f[kRasterWaves];
     const CloudParams& p = mp.c;
     const int b = blockIdx.y, tile = blockIdx.x;
-    const int shift = p.ox & 3;
-    const int v_end = min(p.H, (tile + 1) * p.rows_per_tile);
     int n = 0, nf = 0;
-    for (int v = tile * p.rows_per_tile; v < v_end; ++v) {
-        const size_t row = ((size_t)b * p.H + v) * (size_t)p.W;
-        for (int c0 = -shift; c0 < p.W; c0 += kMeshChunk) {               // block-uniform: every lane takes every step (shuffles inside)
-            const int u0 = c0 + (int)threadIdx.x * 4;
-            float z[4] = {0.f, 0.f, 0.f, 0.f}, d[4] = {0.f, 0.f, 0.f, 0.f};
-            if (u0 < p.W) cloud_eval4d<VEC>(p, b, v, u0, z, d);
+    for (RasterWalk w(p, tile, p.H); w.more(); w.next()) {                // (shuffles inside)
+        const int v = w.v, u0 = w.u0();
+        float z[4] = {0.f, 0.f, 0.f, 0.f}, d[4] = {0.f, 0.f, 0.f, 0.f};
+        if (u0 < p.W) cloud_eval4d<VEC>(p, b, v, u0, z, d);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) n += z[j] > 0.f;
-            Corners q;
-            mesh_corners_from_maps<VEC>(p, b, v, u0, z, d, q);
+        for (int j = 0; j < 4; ++j) n += z[j] > 0.f;
+        Corners q;
+        mesh_corners_from_maps<VEC>(p, b, v, u0, z, d, q);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                bool diag_ae, f0, f1;
-                mesh_quad(q, j, mp.max_jump, diag_ae, f0, f1);
-                nf += (int)f0 + (int)f1;
-            }
-            if (u0 >= p.W) continue;
-            const bool whole = VEC && u0 >= 0 && u0 + 3 < p.W && ((row + u0) & 3) == 0;
-            if (p.depth) {
-                if (whole) {
-                    float4_t zz = {z[0], z[1], z[2], z[3]};
-                    *reinterpret_cast<float4_t*>(p.depth + row + u0) = zz;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (u0 + j >= 0 && u0 + j < p.W) p.depth[row + u0 + j] = z[j];
-                }
-            }
-            if (p.mask) {
-                if (whole) {
-                    uchar4_t kk = {(unsigned char)(z[0] > 0.f), (unsigned char)(z[1] > 0.f), (unsigned char)(z[2] > 0.f), (unsigned char)(z[3] > 0.f)};
-                    *reinterpret_cast<uchar4_t*>(p.mask + row + u0) = kk;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (u0 + j >= 0 && u0 + j < p.W) p.mask[row + u0 + j] = (unsigned char)(z[j] > 0.f);
-                }
-            }
+        for (int j = 0; j < 4; ++j) {
+            bool diag_ae, f0, f1;
+            mesh_quad(q, j, mp.max_jump, diag_ae, f0, f1);
+            nf += (int)f0 + (int)f1;
         }
+        if (u0 < p.W) cloud_store_dense<VEC>(p, b, v, u0, z);
     }
     n = block_sum_int(n, red_v);
     nf = block_sum_int(nf, red_f);
@@ -153,175 +110,63 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(const MeshPara
     }
 }
 
-template <bool VEC, typename IT>
-__global__ __launch_bounds__(kMeshThreads) void mesh_vertex_kernel(const MeshParams mp) {
-    __shared__ int red[kMeshThreads / 64];
-    __shared__ int wave_n[2][kMeshThreads / 64];
-    const CloudParams& p = mp.c;
-    const int b = blockIdx.y, tile = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int* counts = p.tile_counts + (size_t)b * p.tiles;
-    int before = 0;
-    for (int t = threadIdx.x; t < tile; t += kMeshThreads) before += counts[t];
-    long long base = block_sum_int(before, red);
-
-    const IT* img = static_cast<const IT*>(p.image) + (size_t)b * 3 * p.H * p.W;
-    const size_t plane = (size_t)p.H * p.W;
-    uint4_t* rec = p.records + (size_t)b * (size_t)p.capacity;
-    const int shift = p.ox & 3;
-    const int v_end = min(p.H, (tile + 1) * p.rows_per_tile);
-    int step = 0;
-    for (int v = tile * p.rows_per_tile; v < v_end; ++v) {
-        const size_t row = ((size_t)b * p.H + v) * (size_t)p.W;         // in the rank map (all pairs)
-        for (int c0 = -shift; c0 < p.W; c0 += kMeshChunk, ++step) {       // block-uniform: every wave takes every step (barrier inside)
-            const int u0 = c0 + (int)threadIdx.x * 4;
-            float z[4] = {0.f, 0.f, 0.f, 0.f};
-            if (u0 < p.W) cloud_eval4<VEC>(p, b, v, u0, z);
-            int below = 0, wave_total = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned long long bal = __ballot(z[j] > 0.f);
-                below += __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-                wave_total += __popcll(bal);
-            }
-            if (lane == 0) wave_n[step & 1][wave] = wave_total;
-            __syncthreads();                             // (two buffers: the step after next rewrites this one behind the next barrier)
-            long long r = base;
-            int block_total = 0;
-#pragma unroll
-            for (int w = 0; w < kMeshThreads / 64; ++w) {
-                const int nw = wave_n[step & 1][w];
-                if (w < wave) r += nw;
-                block_total += nw;
-            }
-            base += block_total;
-            r += below;
-            int rk[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                rk[j] = -1;
-                if (z[j] > 0.f) {
-                    if (r < p.capacity) rec[r] = cloud_record<IT>(p, img, plane, v, u0 + j, z[j]);
-                    rk[j] = (int)r;
-                    ++r;
-                }
-            }
-            if (u0 >= p.W) continue;
-            if (mp.rank_vec && u0 >= 0 && u0 + 3 < p.W && ((row + u0) & 3) == 0) {
-                int4_t rr = {rk[0], rk[1], rk[2], rk[3]};
-                *reinterpret_cast<int4_t*>(mp.rank + row + u0) = rr;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (u0 + j >= 0 && u0 + j < p.W) mp.rank[row + u0 + j] = rk[j];
-            }
-        }
-    }
-    if (tile == p.tiles - 1 && threadIdx.x == 0) p.count[b] = (int)base;
-}
-
-// face kernel: disparity and rank of the thread's four pixels of image row v (pixels outside the row: rank -1, d = 0)
+// face kernel: disparity and rank of the thread's four pixels of image row v (pixels outside the row keep d = 0, rank -1)
 template <bool VEC>
 __device__ __forceinline__ void mesh_load4(const MeshParams& mp, int b, int v, int u0, float d[4], int rk[4]) {
-    const CloudParams& p = mp.c;
-    const size_t m = ((size_t)b * p.Hp + (v + p.oy)) * (size_t)p.Wp + (size_t)(p.ox + u0);
-    const size_t px = ((size_t)b * p.H + v) * (size_t)p.W + u0;            // (wraps for u0 < 0: only used where the pixel exists)
-    if constexpr (VEC) {
-        const raw16_t dv = global_load16(p.disp + m);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = dv[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[j] = (u0 + j >= 0 && u0 + j < p.W) ? p.disp[m + j] : 0.f;
-    }
-    if (mp.rank_vec && u0 >= 0 && u0 + 3 < p.W && (px & 3) == 0) {
-        const int4_t rr = *reinterpret_cast<const int4_t*>(mp.rank + px);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rk[j] = rr[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rk[j] = (u0 + j >= 0 && u0 + j < p.W) ? mp.rank[px + j] : -1;
-    }
+    map_load4<VEC>(mp.c.disp, raster_map_index(mp.c, b, v, u0), u0, mp.c.W, d);
+    dense_load4(mp.rank, raster_dense_row(mp.c, b, v), u0, mp.c.W, mp.rank_vec != 0, rk);
 }
 
 struct __attribute__((packed, aligned(4))) MeshFace { int a, b, c; };
 
 template <bool VEC>
-__global__ __launch_bounds__(kMeshThreads) void mesh_face_kernel(const MeshParams mp) {
-    __shared__ int red[kMeshThreads / 64];
-    __shared__ int wave_n[2][kMeshThreads / 64];
+__global__ __launch_bounds__(kRasterThreads) void mesh_face_kernel(const MeshParams mp) {
+    __shared__ int red[kRasterWaves];
+    __shared__ int wave_n[2][kRasterWaves];
     const CloudParams& p = mp.c;
     const int b = blockIdx.y, tile = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int* counts = mp.tile_faces + (size_t)b * p.tiles;
-    int before = 0;
-    for (int t = threadIdx.x; t < tile; t += kMeshThreads) before += counts[t];
-    long long base = block_sum_int(before, red);
-
+    const int lane = threadIdx.x & 63;
+    long long base = tile_prefix(mp.tile_faces + (size_t)b * p.tiles, tile, red);
     MeshFace* faces = reinterpret_cast<MeshFace*>(mp.faces) + (size_t)b * (size_t)mp.face_capacity;
-    const int shift = p.ox & 3;
-    const int v_end = min(p.H - 1, (tile + 1) * p.rows_per_tile);          // the last image row has no quads
     int step = 0;
-    for (int v = tile * p.rows_per_tile; v < v_end; ++v) {
-        for (int c0 = -shift; c0 < p.W; c0 += kMeshChunk, ++step) {       // block-uniform: every wave takes every step (barrier, shuffles)
-            const int u0 = c0 + (int)threadIdx.x * 4;
-            float d[2][5];
-            int rk[2][5];
+    for (RasterWalk w(p, tile, p.H - 1); w.more(); w.next()) {            // the last image row has no quads; (shuffles inside)
+        const int v = w.v, u0 = w.u0();
+        float d[2][5];
+        int rk[2][5];
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
+        for (int r = 0; r < 2; ++r) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { d[r][j] = 0.f; rk[r][j] = -1; }
-                if (u0 < p.W) mesh_load4<VEC>(mp, b, v + r, u0, d[r], rk[r]);
-                float dr = 0.f;
-                int rr = -1;
-                const int ur = u0 + 4;
-                if (lane == 63 && ur < p.W) {
-                    dr = p.disp[((size_t)b * p.Hp + (v + r + p.oy)) * (size_t)p.Wp + (size_t)(p.ox + ur)];
-                    rr = mp.rank[((size_t)b * p.H + (v + r)) * (size_t)p.W + ur];
-                }
-                d[r][4] = mesh_from_right(d[r][0], dr);
-                rk[r][4] = __builtin_bit_cast(int, mesh_from_right(__builtin_bit_cast(float, rk[r][0]), __builtin_bit_cast(float, rr)));
+            for (int j = 0; j < 4; ++j) { d[r][j] = 0.f; rk[r][j] = -1; }
+            if (u0 < p.W) mesh_load4<VEC>(mp, b, v + r, u0, d[r], rk[r]);
+            float dr = 0.f;
+            int rr = -1;
+            const int ur = u0 + 4;
+            if (lane == 63 && ur < p.W) {
+                dr = p.disp[raster_map_index(p, b, v + r, ur)];
+                rr = mp.rank[raster_dense_row(p, b, v + r) + ur];
             }
-            Corners q;
+            d[r][4] = mesh_from_right(d[r][0], dr);
+            rk[r][4] = __builtin_bit_cast(int, mesh_from_right(__builtin_bit_cast(float, rk[r][0]), __builtin_bit_cast(float, rr)));
+        }
+        Corners q;
 #pragma unroll
-            for (int r = 0; r < 2; ++r)
+        for (int r = 0; r < 2; ++r)
 #pragma unroll
-                for (int j = 0; j < 5; ++j) { q.k[r][j] = rk[r][j] >= 0; q.d[r][j] = d[r][j]; }
-            bool diag[4], f[4][2];
-            int below = 0, wave_total = 0;
+            for (int j = 0; j < 5; ++j) { q.k[r][j] = rk[r][j] >= 0; q.d[r][j] = d[r][j]; }
+        bool diag[4], f[8];                                                // f: by quad, then by slot
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                mesh_quad(q, j, mp.max_jump, diag[j], f[j][0], f[j][1]);
+        for (int j = 0; j < 4; ++j) mesh_quad(q, j, mp.max_jump, diag[j], f[2 * j], f[2 * j + 1]);
+        long long r = raster_rank_step(f, wave_n, step++, base);
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const unsigned long long bal = __ballot(f[j][s]);
-                    below += __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-                    wave_total += __popcll(bal);
-                }
+        for (int j = 0; j < 4; ++j) {
+            const int ra = rk[0][j], rb = rk[0][j + 1], rc = rk[1][j], re = rk[1][j + 1];
+            if (f[2 * j]) {
+                if (r < mp.face_capacity) { MeshFace t = {ra, rc, diag[j] ? re : rb}; faces[r] = t; }
+                ++r;
             }
-            if (lane == 0) wave_n[step & 1][wave] = wave_total;
-            __syncthreads();                             // (two buffers, as in the vertex kernel)
-            long long r = base;
-            int block_total = 0;
-#pragma unroll
-            for (int w = 0; w < kMeshThreads / 64; ++w) {
-                const int nw = wave_n[step & 1][w];
-                if (w < wave) r += nw;
-                block_total += nw;
-            }
-            base += block_total;
-            r += below;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ra = rk[0][j], rb = rk[0][j + 1], rc = rk[1][j], re = rk[1][j + 1];
-                if (f[j][0]) {
-                    if (r < mp.face_capacity) { MeshFace t = {ra, rc, diag[j] ? re : rb}; faces[r] = t; }
-                    ++r;
-                }
-                if (f[j][1]) {
-                    if (r < mp.face_capacity) { MeshFace t = {diag[j] ? ra : rb, diag[j] ? re : rc, diag[j] ? rb : re}; faces[r] = t; }
-                    ++r;
-                }
+            if (f[2 * j + 1]) {
+                if (r < mp.face_capacity) { MeshFace t = {diag[j] ? ra : rb, diag[j] ? re : rc, diag[j] ? rb : re}; faces[r] = t; }
+                ++r;
             }
         }
     }
@@ -329,26 +174,21 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_face_kernel(const MeshParam
 }
 
 // faces of a pair fit an int32 count: 2 (H-1) (W-1) < 2^31
-static bool mesh_extents_ok(int B, int H, int W) { return cloud_extents_ok(B, H, W) && (long long)H * W < (1LL << 30); }
+static bool mesh_extents_ok(int B, int H, int W) { return raster_extents_ok(B, H, W, 1LL << 30); }
 
-static size_t mesh_counts_bytes(int B, int H, int W) {
-    const int rows = mesh_tile_rows(W);
-    const size_t tiles = (size_t)B * ((H + rows - 1) / rows);
-    return (2 * tiles * sizeof(int) + 255) / 256 * 256;
-}
+static int mesh_tile_rows(int W) { return tile_rows(W, kMeshTilePixels); }
+
+static size_t mesh_counts_bytes(int B, int H, int W) { return round256(2 * (size_t)B * tiles(H, mesh_tile_rows(W)) * sizeof(int)); }
 
 static int mesh_impl(const s2m2_mesh_desc* d, void* stream) {
     S2M2_REQUIRE(d != nullptr, "mesh: null descriptor");
-    S2M2_REQUIRE(!plan_recording(), "mesh: s2m2_mesh is not recorded in launch plans -- call it after s2m2_plan_end, behind s2m2_plan_run / "
-                                    "s2m2_engine_run on the same stream");
+    if (int rc = refuse_while_recording("mesh")) return rc;
     const s2m2_cloud_desc* cd = &d->cloud;
     if (d->face_count == nullptr) return s2m2_cloud(cd, stream);           // no mesh requested: K15 on the same fields
     S2M2_REQUIRE(cd->count != nullptr, "mesh: face_count comes with count (the faces index the vertex records)");
     MeshParams mp;
     bool vec = false;
-    if (int rc = cloud_validate(cd, "mesh", mp.c, vec)) return rc;
-    mp.c.rows_per_tile = mesh_tile_rows(cd->W);            // K20's own tile geometry
-    mp.c.tiles = (cd->H + mp.c.rows_per_tile - 1) / mp.c.rows_per_tile;
+    if (int rc = cloud_validate(cd, "mesh", kMeshTilePixels, mp.c, vec)) return rc;       // K20's own tile geometry
     S2M2_REQUIRE(mesh_extents_ok(cd->B, cd->H, cd->W), "mesh: extents too large (H*W < 2^30)");
     S2M2_REQUIRE(d->face_capacity >= 0, "mesh: negative face_capacity %lld", d->face_capacity);
     S2M2_REQUIRE(d->faces != nullptr || d->face_capacity == 0, "mesh: null pointer (faces) with face_capacity %lld", d->face_capacity);
@@ -365,16 +205,11 @@ static int mesh_impl(const s2m2_mesh_desc* d, void* stream) {
     mp.face_capacity = d->face_capacity;
     mp.max_jump = (float)d->max_jump;
 
-    const dim3 grid(mp.c.tiles, cd->B), block(kMeshThreads);
+    const dim3 grid(mp.c.tiles, cd->B), block(kRasterThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = vec ? launch<mesh_count_kernel<true>>("mesh (count)", grid, block, 0, s, mp) : launch<mesh_count_kernel<false>>("mesh (count)", grid, block, 0, s, mp))
         return rc;
-    if (int rc = by_image_dtype(cd->image_dtype, "mesh", [&](auto ti) {      // (validated above)
-            using IT = decltype(ti);
-            if (vec) return launch<mesh_vertex_kernel<true, IT>>("mesh (vertices)", grid, block, 0, s, mp);
-            return launch<mesh_vertex_kernel<false, IT>>("mesh (vertices)", grid, block, 0, s, mp);
-        }))
-        return rc;
+    if (int rc = mesh_vertices(mp, vec, cd->image_dtype, grid, s)) return rc;
     return vec ? launch<mesh_face_kernel<true>>("mesh (faces)", grid, block, 0, s, mp) : launch<mesh_face_kernel<false>>("mesh (faces)", grid, block, 0, s, mp);
 }
 
@@ -382,7 +217,7 @@ static int mesh_impl(const s2m2_mesh_desc* d, void* stream) {
 
 extern "C" size_t s2m2_mesh_workspace_bytes(int B, int H, int W) {
     if (!s2m2::mesh_extents_ok(B, H, W)) return 0;
-    return s2m2::mesh_counts_bytes(B, H, W) + ((size_t)B * H * W * sizeof(int) + 255) / 256 * 256;
+    return s2m2::mesh_counts_bytes(B, H, W) + s2m2::round256((size_t)B * H * W * sizeof(int));
 }
 
 extern "C" int s2m2_mesh_tile_rows(int H, int W) { return s2m2::mesh_extents_ok(1, H, W) ? s2m2::mesh_tile_rows(W) : 0; }

@@ -15,6 +15,13 @@
 namespace s2m2 {
 
 bool plan_recording();
+// The refusal of the output stages that run BEHIND a plan and are not recorded into one (s2m2_<entry>: cloud, mesh, disp_eval).  K16 keeps its
+// own text: s2m2_rectify runs before a plan, not after.
+inline int refuse_while_recording(const char* entry) {
+    S2M2_REQUIRE(!plan_recording(), "%s: s2m2_%s is not recorded in launch plans -- call it after s2m2_plan_end, behind s2m2_plan_run / "
+                                    "s2m2_engine_run on the same stream", entry, entry);
+    return 0;
+}
 constexpr int kPlanMaskWords = 4;                                // 256 eight-byte words: blobs of up to 2 KB
 struct PlanPtrMask {
     unsigned long long bits[kPlanMaskWords] = {0, 0, 0, 0};

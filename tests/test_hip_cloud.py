@@ -112,7 +112,11 @@ def _records(pc, b, stored):
     return pc.records[b, :stored].cpu().numpy().view(cloud.RECORD_DTYPE).reshape(-1)
 
 
-SIZES = [(1024, 1216, 1024, 1216), (1024, 1216, 1000, 1190), (32, 32, 1, 1), (2048, 2432, 2000, 2400)]
+# The last three are shapes of tests/test_hip_mesh.py, whose vertex launch is K15's scatter kernel: map width no multiple of 4 (the per-pixel
+# kernels) with crop offset 1; the aligned kernels with ox % 4 == 1 over three tiles of 67 rows; five block steps per row (both buffers of the
+# rank step are reused), one row per tile
+SIZES = [(1024, 1216, 1024, 1216), (1024, 1216, 1000, 1190), (32, 32, 1, 1), (2048, 2432, 2000, 2400),
+         (40, 63, 37, 61), (160, 64, 140, 61), (32, 4128, 3, 4100)]
 CASES = [(s, B, f, t, dt) for s in SIZES for B in (1, 3) for f in (True, False) for t in (3.0, None) for dt in ("uint8", "float16", "float32")]
 
 

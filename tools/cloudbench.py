@@ -29,23 +29,12 @@ def main() -> None:
     a = ap.parse_args()
     import torch
     from s2m2_amd import hip
+    from tools.kbench import captured, timed
     lines = []
 
     def say(s: str) -> None:
         print(s, flush=True)
         lines.append(s)
-
-    def timed(fn, steps: int) -> float:
-        """microseconds per call"""
-        fn()
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(steps):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return 1000.0 * t0.elapsed_time(t1) / steps
 
     forward_us = None
     if a.forward:
@@ -84,15 +73,7 @@ def main() -> None:
             def k15():
                 hip.cloud(disp, occ, conf, img, **kw)
 
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                k15()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                k15()
+            graph = captured(k15)
 
             bf, doffs = float(CAL["baseline"] * CAL["fx"]), CAL["doffs"]
             uu = torch.arange(W, device="cuda", dtype=torch.float32).expand(H, W)

@@ -30,6 +30,7 @@ def main() -> None:
     a = ap.parse_args()
     import torch
     from s2m2_amd import hip
+    from tools.kbench import captured, timed
     if not torch.cuda.is_available():
         raise SystemExit("evalbench: needs the GPU (nothing is measured without one)")
     lines = []
@@ -37,18 +38,6 @@ def main() -> None:
     def say(s: str) -> None:
         print(s, flush=True)
         lines.append(s)
-
-    def timed(fn, steps: int) -> float:
-        """microseconds per call"""
-        fn()
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(steps):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return 1000.0 * t0.elapsed_time(t1) / steps
 
     forward_us = None
     if a.forward:
@@ -84,15 +73,7 @@ def main() -> None:
             def k18():
                 hip.disp_eval(disp, gt, stats, ws, **kw)
 
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                k18()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                k18()
+            graph = captured(k18)
 
             def block(sel, a_, q, s, finite, bad, d1):
                 """the 14 words of one set of pixels (sel: evaluated pixels of the set)"""

@@ -7,6 +7,7 @@ Prints one line per kernel/config: time (us), algorithmic GB/s or TFLOP/s.
 import argparse
 import json
 import os
+import statistics
 import sys
 
 import torch
@@ -50,6 +51,39 @@ def timeit_graph_cold(fn, iters=20, reps=5, mb=64):
     t_f = timeit_graph(lambda: buf.zero_(), iters, reps)
     t = timeit_graph(lambda: (buf.zero_(), fn()), iters, reps)
     return t - t_f
+
+
+# The timing method of the output-stage benches (cloudbench, meshbench, evalbench, rectifybench): one definition, so that their figures compare.
+def timed(fn, steps: int) -> float:
+    """microseconds per call: events around `steps` calls, after one warm call and a synchronise"""
+    fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(steps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return 1000.0 * t0.elapsed_time(t1) / steps
+
+
+def spread(ts) -> str:
+    """the median of the windows with their minimum and maximum behind it"""
+    return f"{statistics.median(ts):8.1f} us [{min(ts):.1f} .. {max(ts):.1f}]"
+
+
+def captured(fn):
+    """a hipGraph that holds one call of fn (warmed on a side stream first)"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fn()
+    return graph
 
 
 def timeit(fn, iters, warmup=5):

@@ -34,38 +34,12 @@ def main() -> None:
     a = ap.parse_args()
     import torch
     from s2m2_amd import hip
+    from tools.kbench import captured, spread, timed
     lines = []
 
     def say(s: str) -> None:
         print(s, flush=True)
         lines.append(s)
-
-    def timed(fn, steps: int) -> float:
-        """microseconds per call"""
-        fn()
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(steps):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        return 1000.0 * t0.elapsed_time(t1) / steps
-
-    def spread(ts) -> str:
-        return f"{statistics.median(ts):8.1f} us [{min(ts):.1f} .. {max(ts):.1f}]"
-
-    def captured(fn):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            fn()
-        return graph
 
     forward_us = None
     if a.forward:
