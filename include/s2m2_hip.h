@@ -44,7 +44,8 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * engine files of 800 are invalidated.  A library built before K16 reports 800 as well and lacks the symbol: s2m2_amd/hip.py load() names the
  * missing symbol and asks for a rebuild.  Still 800 with s2m2_disp_eval, s2m2_eval_workspace_bytes, s2m2_eval_tile_rows and s2m2_eval_desc (K18, the
  * evaluation stage behind the forward), added the same way, and with s2m2_mesh, s2m2_mesh_workspace_bytes, s2m2_mesh_tile_rows and s2m2_mesh_desc
- * (K20, the surface mesh behind the 3D stage). */
+ * (K20, the surface mesh behind the 3D stage), and with s2m2_register, s2m2_register_workspace_bytes and s2m2_register_desc (K21, the depth
+ * map registered to a second camera). */
 #define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
@@ -962,6 +963,62 @@ typedef struct s2m2_mesh_desc {
 size_t s2m2_mesh_workspace_bytes(int B, int H, int W);      /* 0: bad extents */
 int s2m2_mesh_tile_rows(int H, int W);                      /* image rows of one tile of all three launches; 0: bad extents */
 int s2m2_mesh(const s2m2_mesh_desc* desc, void* stream);
+
+/*
+ * K21 -- registration of the depth map to a second camera: a z-buffered forward warp of the kept pixels of the rectified left view into a
+ *   target camera (the colour camera of a rig, the right view, a virtual view), on the device.  Like K18 and K20 it has no counterpart in the
+ *   reference: the semantics are defined here and pinned by the numpy oracle of tests/register_oracle.py.  Still S2M2_ABI_VERSION 800: the
+ *   entry points are added, nothing changes in place.
+ *   `cloud` holds the INPUT fields of s2m2_cloud, with their meaning: the padded maps, the unpadded image (only needed with image_t), the fused
+ *   crop, camera and filter parameters.  Its output fields (depth, mask, records, count, capacity, workspace) are IGNORED.
+ *   per kept source pixel (v,u), all in fp32, every operation ONE IEEE rounding, nothing fused into a multiply-add:
+ *     keep, z as in K15 (the same device function);   x = ((float)u - cx) * z / fx;   y = ((float)v - cy) * z / fy
+ *     X = ((r00*x + r01*y) + r02*z) + tx;   Y = ((r10*x + r11*y) + r12*z) + ty;   Z = ((r20*x + r21*y) + r22*z) + tz
+ *                                            (R row-major, source camera -> target camera; t in the unit of z; R, t and the target
+ *                                            intrinsics are converted to fp32 once on the host)
+ *     accepted iff Z > 0 and Z is finite
+ *     up = (fx_t * X) / Z + cx_t;            vp = (fy_t * Y) / Z + cy_t
+ *     c = (splat - 2) / 2  (-0.5, 0, 0.5 or 1: exact);   fu = floorf(up - c);   fv = floorf(vp - c)
+ *     discarded unless fu >= -splat && fu < Wt && fv >= -splat && fv < Ht  (float comparisons, before any conversion to int: a NaN discards)
+ *     footprint: the target pixels (fv + dy, fu + dx), 0 <= dx, dy < splat, those inside the target image.  splat 1 is the nearest target
+ *     pixel, splat 2 the four target pixels nearest to the projected point
+ *     key = ((uint64)bits(Z) << 32) | (uint32)(v * W + u)
+ *   A target pixel keeps the MINIMUM key of all footprints that cover it: the nearest Z, and on exactly equal Z bits the lowest source index.
+ *   outputs, each optional (NULL), at least one:
+ *     depth_t  (B,1,Ht,Wt) fp32: Z (in the TARGET camera) of the winner, 0 at a hole (a target pixel that no footprint covers)
+ *     index_t  (B,1,Ht,Wt) int32: the winner's source pixel v * W + u, -1 at a hole
+ *     image_t  (B,3,Ht,Wt) planar uint8: the winner's colour (K15's byte rule), 0 at a hole; requires cloud.image
+ *     visible  (B,1,H,W) uint8: 1 iff the source pixel won at least one target pixel -- the geometric counterpart of the occ map
+ *     count    (B) int32: the covered target pixels of every pair
+ *   workspace: >= s2m2_register_workspace_bytes(B, Ht, Wt) bytes, 8-byte aligned, always required: the z-buffer, one key per target pixel.
+ *   Three launches, no host step.  (A) clear: the z-buffer to all ones, count and visible to 0.  (B) splat: thread -> pixel map and 16-byte
+ *   map loads of K15's launch A; one 64-bit unsigned atomic minimum without return per covered target pixel.  (C) resolve: per target pixel
+ *   the key is decoded, depth_t / index_t / image_t are stored densely, visible[b, index] takes a 1 (same-value plain stores) and the block's
+ *   covered pixels are added to count[b] with one integer atomic add.  A minimum and an integer sum do not depend on the order of arrival and
+ *   the keys are unique: the result is bit-reproducible although this stage uses atomics.
+ *   Launch plans: s2m2_register is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing;
+ *   the stage runs after s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ *   Errors (before any device call): null descriptor; everything s2m2_cloud checks on its inputs (maps, extents, fx, fy, depth_scale, image
+ *   dtype, alignment); non-positive Ht, Wt, fx_t, fy_t; splat outside 1..4; a non-finite R, t or target intrinsic (also as fp32); H * W or
+ *   Ht * Wt >= 2^31; no output requested; image_t without cloud.image; a missing or misaligned workspace; depth_t, index_t or count not 4-byte
+ *   aligned.
+ */
+typedef struct s2m2_register_desc {
+    s2m2_cloud_desc cloud;
+    int Ht, Wt;                 /* target image */
+    int splat;                  /* 1..4: side of the square footprint in target pixels */
+    double fx_t, fy_t, cx_t, cy_t;
+    double R[9];                /* row-major, source camera -> target camera */
+    double t[3];                /* in the unit of z (i.e. after depth_scale) */
+    float*         depth_t;
+    int32_t*       index_t;
+    unsigned char* image_t;
+    unsigned char* visible;
+    int32_t*       count;
+    void*          workspace;
+} s2m2_register_desc;
+size_t s2m2_register_workspace_bytes(int B, int Ht, int Wt);   /* 0: bad extents */
+int s2m2_register(const s2m2_register_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,16 @@
 //   --calib, honours every option above, names its files like --ply for B > 1, and may be given next to --ply or instead of it.  With
 //   --repeat: {"mesh_vertices", "mesh_faces", "repeat", "mesh_us_per_pair"} on a line of its own.
 //
+// --register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]: the depth map registered to a second
+//   camera (s2m2_register), behind --calib; honours --image, --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered, and may be
+//   given next to --ply / --mesh or without them.  CAM is the word "right" (cam1 of --calib at the engine's image size, no rotation, t =
+//   (-baseline / depth_scale, 0, 0)) or a text file in the calib file's syntax: width=, height=, cam=[fx 0 cx; 0 fy cy; 0 0 1], R=[r00 r01 r02;
+//   r10 r11 r12; r20 r21 r22] (source camera -> target camera; default: the identity), t=[tx ty tz] (in the unit of z; default: 0).
+//   --splat: the footprint, 1..4 (default 2).  --register-depth: raw float32 (Ht,Wt) z in the target camera, 0 = hole; --register-index: raw
+//   int32 (Ht,Wt) winning source pixel v * W + u, -1 = hole; --register-image: a binary PPM (P6) of the winners' colours.  B > 1: one file per
+//   pair each, named as --ply names its files (OUT.<b>.f32, OUT.<b>.i32, OUT.<b>.ppm).  With --repeat: {"register_covered", "repeat", "register_us_per_pair"} on a line
+//   of its own.
+//
 // Evaluation against ground truth (s2m2_disp_eval on the device buffers of the run; without --gt nothing below happens):
 //   --gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] [--thresholds a,b,c] [--conf-min X] [--occ-min X] --metrics OUT.json
 // --gt: a greyscale PFM (Pf) of W x (B * H) pixels, H <= out_h and W <= out_w of the engine: the ground truths of the B pairs stacked top to
@@ -42,7 +52,8 @@
 
 static const char* USAGE =
     "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
-    "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
+    "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]";
 
 static int fail(const char* what) {
@@ -74,7 +85,8 @@ static bool write_raw(const std::string& path, const std::vector<float>& v) {
 // cam0=[fx 0 cx; 0 fy cy; 0 0 1], doffs=, baseline= of a Middlebury calib.txt; every other key is ignored
 struct Calib {
     double fx = 0, fy = 0, cx = 0, cy = 0, doffs = 0, baseline = 0;
-    bool have_cam0 = false, have_baseline = false;
+    double cam1[4] = {0, 0, 0, 0};      // fx, fy, cx, cy of cam1 (--register right)
+    bool have_cam0 = false, have_baseline = false, have_cam1 = false;
 };
 
 static bool read_calib(const char* path, Calib& c) {
@@ -86,11 +98,50 @@ static bool read_calib(const char* path, Calib& c) {
         if (sscanf(line, " cam0 = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
             c.fx = m[0]; c.cx = m[2]; c.fy = m[4]; c.cy = m[5];
             c.have_cam0 = true;
+        } else if (sscanf(line, " cam1 = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            c.cam1[0] = m[0]; c.cam1[1] = m[4]; c.cam1[2] = m[2]; c.cam1[3] = m[5];
+            c.have_cam1 = true;
         } else if (sscanf(line, " doffs = %lf", m) == 1) c.doffs = m[0];
         else if (sscanf(line, " baseline = %lf", m) == 1) { c.baseline = m[0]; c.have_baseline = true; }
     }
     fclose(f);
     return c.have_cam0 && c.have_baseline;
+}
+
+// the target camera of --register: a text file in the calib file's syntax (see the head of this file)
+struct TargetCamera {
+    int width = 0, height = 0;
+    double fx = 0, fy = 0, cx = 0, cy = 0;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double t[3] = {0, 0, 0};
+};
+
+static bool read_camera(const char* path, TargetCamera& c) {
+    FILE* f = fopen(path, "r");
+    if (!f) return false;
+    char line[512];
+    bool have_cam = false;
+    while (fgets(line, sizeof line, f)) {
+        double m[9];
+        if (sscanf(line, " cam = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            c.fx = m[0]; c.cx = m[2]; c.fy = m[4]; c.cy = m[5];
+            have_cam = true;
+        } else if (sscanf(line, " R = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            memcpy(c.R, m, sizeof c.R);
+        } else if (sscanf(line, " t = [ %lf %lf %lf", m, m + 1, m + 2) == 3) {
+            memcpy(c.t, m, sizeof c.t);
+        } else if (sscanf(line, " width = %lf", m) == 1) c.width = (int)m[0];
+        else if (sscanf(line, " height = %lf", m) == 1) c.height = (int)m[0];
+    }
+    fclose(f);
+    return have_cam && c.width > 0 && c.height > 0;
+}
+
+static bool write_bytes(const std::string& path, const char* head, const void* data, size_t n) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(head, 1, strlen(head), f) == strlen(head) && fwrite(data, 1, n, f) == n;
+    return fclose(f) == 0 && ok;
 }
 
 static bool write_ply(const std::string& path, const void* records, long long n) {
@@ -118,12 +169,13 @@ static bool write_ply_mesh(const std::string& path, const void* records, long lo
     return fclose(f) == 0 && ok;
 }
 
-// OUT.ply, or OUT.<b>.ply for engines of more than one pair (a trailing ".ply" of OUT is dropped first)
-static std::string pair_path(const char* out, int B, int b) {
+// OUT.ply, or OUT.<b>.ply for engines of more than one pair (a trailing ".ply" of OUT is dropped first); --register-image: ".ppm"
+static std::string pair_path(const char* out, int B, int b, const char* ext = ".ply") {
     std::string stem = out;
     if (B <= 1) return stem;
-    if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".ply") == 0) stem.resize(stem.size() - 4);
-    return stem + "." + std::to_string(b) + ".ply";
+    const size_t ne = strlen(ext);
+    if (stem.size() > ne && stem.compare(stem.size() - ne, ne, ext) == 0) stem.resize(stem.size() - ne);
+    return stem + "." + std::to_string(b) + ext;
 }
 
 // greyscale PFM: "Pf", "width height", "scale" (negative: little-endian), then the rows bottom to top -> rows top to bottom
@@ -195,6 +247,8 @@ int main(int argc, char** argv) {
     const char* out_dir = nullptr;
     const char *calib_path = nullptr, *image_path = nullptr, *ply_path = nullptr, *depth_path = nullptr, *mesh_path = nullptr;
     const char* max_jump_arg = nullptr;
+    const char *register_cam = nullptr, *reg_depth_path = nullptr, *reg_image_path = nullptr, *reg_index_path = nullptr, *splat_arg = nullptr;
+    int splat = 2;
     double max_jump = 1.0;
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5;
     int unfiltered = 0;
@@ -209,6 +263,11 @@ int main(int argc, char** argv) {
         else if (strcmp(argv[i], "--mesh") == 0 && i + 1 < argc) mesh_path = argv[++i];
         else if (strcmp(argv[i], "--max-jump") == 0 && i + 1 < argc) max_jump_arg = argv[++i];
         else if (strcmp(argv[i], "--depth") == 0 && i + 1 < argc) depth_path = argv[++i];
+        else if (strcmp(argv[i], "--register") == 0 && i + 1 < argc) register_cam = argv[++i];
+        else if (strcmp(argv[i], "--splat") == 0 && i + 1 < argc) splat_arg = argv[++i];
+        else if (strcmp(argv[i], "--register-depth") == 0 && i + 1 < argc) reg_depth_path = argv[++i];
+        else if (strcmp(argv[i], "--register-image") == 0 && i + 1 < argc) reg_image_path = argv[++i];
+        else if (strcmp(argv[i], "--register-index") == 0 && i + 1 < argc) reg_index_path = argv[++i];
         else if (strcmp(argv[i], "--depth-trunc") == 0 && i + 1 < argc) depth_trunc = atof(argv[++i]);
         else if (strcmp(argv[i], "--depth-scale") == 0 && i + 1 < argc) depth_scale = atof(argv[++i]);
         else if (strcmp(argv[i], "--conf-min") == 0 && i + 1 < argc) conf_min = atof(argv[++i]);
@@ -225,7 +284,14 @@ int main(int argc, char** argv) {
     }
     if (npos != 3 || repeat < 0) return fail(USAGE);
     if (mesh_path && !calib_path) return fail("--calib and --mesh come together");
-    if (!mesh_path && (calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
+    if (register_cam && (!calib_path || !reg_depth_path)) return fail("--register needs --calib and --register-depth");
+    if (!register_cam && (reg_depth_path || reg_image_path || reg_index_path || splat_arg)) return fail("--splat and --register-* need --register");
+    if (splat_arg) {
+        splat = atoi(splat_arg);
+        if (splat < 1 || splat > 4) return fail("--splat: 1, 2, 3 or 4");
+    }
+    if (!mesh_path && !register_cam && (calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
+    if (register_cam && !mesh_path && !ply_path && depth_path) return fail("--depth needs --ply or --mesh");
     if (max_jump_arg && !mesh_path) return fail("--max-jump needs --mesh");
     if (max_jump_arg) {
         char* end = nullptr;
@@ -325,7 +391,7 @@ int main(int argc, char** argv) {
         (void)hipEventDestroy(t0);
         (void)hipEventDestroy(t1);
     }
-    if (calib_path) {
+    if (calib_path && (ply_path || mesh_path)) {
         Calib cal;
         if (!read_calib(calib_path, cal)) return fail("--calib: cannot read cam0 and baseline from the file");
         if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
@@ -432,6 +498,107 @@ int main(int argc, char** argv) {
         (void)hipFree(ddepth);
         (void)hipFree(dfaces);
         (void)hipFree(dfcount);
+    }
+    if (register_cam) {
+        Calib cal;
+        if (!read_calib(calib_path, cal)) return fail("--calib: cannot read cam0 and baseline from the file");
+        if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
+        TargetCamera cam;
+        if (strcmp(register_cam, "right") == 0) {
+            if (!cal.have_cam1) return fail("--register right: the calib file has no cam1");
+            cam.width = m.W; cam.height = m.H;
+            cam.fx = cal.cam1[0]; cam.fy = cal.cam1[1]; cam.cx = cal.cam1[2]; cam.cy = cal.cam1[3];
+            cam.t[0] = -cal.baseline / depth_scale;
+        } else if (!read_camera(register_cam, cam)) return fail("--register: the word right, or a file with width=, height= and cam=[fx 0 cx; 0 fy cy; 0 0 1]");
+        const size_t ws_bytes = s2m2_register_workspace_bytes(m.B, cam.height, cam.width);
+        if (ws_bytes == 0) return fail("--register: target extents too large");
+        const size_t tpix = (size_t)cam.height * cam.width;
+        void *dimg = nullptr, *dws = nullptr;
+        float* dd = nullptr;
+        int32_t *di = nullptr, *dcount = nullptr;
+        unsigned char* dc = nullptr;
+        if (image_path) {
+            std::vector<unsigned char> hi(img);
+            FILE* f = fopen(image_path, "rb");
+            const bool ok = f && fread(hi.data(), 1, img, f) == img && fgetc(f) == EOF;
+            if (f) fclose(f);
+            if (!ok) {
+                fprintf(stderr, "s2m2_run_engine: --image must be a raw uint8 (%d,3,%d,%d) file\n", m.B, m.H, m.W);
+                return 1;
+            }
+            HIP_OK(hipMalloc(&dimg, img), "hipMalloc");
+            HIP_OK(hipMemcpy(dimg, hi.data(), img, hipMemcpyHostToDevice), "upload");
+        }
+        HIP_OK(hipMalloc(&dws, ws_bytes), "hipMalloc");
+        HIP_OK(hipMalloc((void**)&dd, (size_t)m.B * tpix * sizeof(float)), "hipMalloc");
+        HIP_OK(hipMalloc((void**)&dcount, m.B * sizeof(int32_t)), "hipMalloc");
+        if (reg_index_path) HIP_OK(hipMalloc((void**)&di, (size_t)m.B * tpix * sizeof(int32_t)), "hipMalloc");
+        if (reg_image_path) HIP_OK(hipMalloc((void**)&dc, (size_t)m.B * 3 * tpix), "hipMalloc");
+        s2m2_register_desc rd;
+        memset(&rd, 0, sizeof rd);
+        s2m2_cloud_desc& cd = rd.cloud;
+        cd.disp = dout[0]; cd.occ = dout[1]; cd.conf = dout[2];
+        cd.image = image_path ? dimg : dl;
+        cd.image_dtype = image_path ? 2 : S2M2_F32;
+        cd.B = m.B; cd.H = m.H; cd.W = m.W; cd.Hp = m.out_h; cd.Wp = m.out_w;
+        cd.unfiltered = unfiltered;
+        cd.fx = cal.fx; cd.fy = cal.fy; cd.cx = cal.cx; cd.cy = cal.cy; cd.baseline = cal.baseline; cd.doffs = cal.doffs;
+        cd.depth_scale = depth_scale; cd.depth_trunc = depth_trunc; cd.conf_min = conf_min; cd.occ_min = occ_min;
+        rd.Ht = cam.height; rd.Wt = cam.width; rd.splat = splat;
+        rd.fx_t = cam.fx; rd.fy_t = cam.fy; rd.cx_t = cam.cx; rd.cy_t = cam.cy;
+        memcpy(rd.R, cam.R, sizeof rd.R);
+        memcpy(rd.t, cam.t, sizeof rd.t);
+        rd.depth_t = dd; rd.index_t = di; rd.image_t = dc; rd.count = dcount; rd.workspace = dws;
+        if (s2m2_register(&rd, s) != 0) return fail_lib("s2m2_register failed");
+        HIP_OK(hipStreamSynchronize(s), "s2m2_register");
+        std::vector<int32_t> hcount(m.B);
+        HIP_OK(hipMemcpy(hcount.data(), dcount, m.B * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+        {
+            std::vector<float> hd((size_t)m.B * tpix);
+            HIP_OK(hipMemcpy(hd.data(), dd, hd.size() * sizeof(float), hipMemcpyDeviceToHost), "download");
+            for (int b = 0; b < m.B; ++b)
+                if (!write_bytes(pair_path(reg_depth_path, m.B, b, ".f32"), "", hd.data() + (size_t)b * tpix, tpix * sizeof(float)))
+                    return fail("cannot write the registered depth map");
+        }
+        if (reg_index_path) {
+            std::vector<int32_t> hidx((size_t)m.B * tpix);
+            HIP_OK(hipMemcpy(hidx.data(), di, hidx.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+            for (int b = 0; b < m.B; ++b)
+                if (!write_bytes(pair_path(reg_index_path, m.B, b, ".i32"), "", hidx.data() + (size_t)b * tpix, tpix * sizeof(int32_t)))
+                    return fail("cannot write the registered index map");
+        }
+        if (reg_image_path) {
+            std::vector<unsigned char> planar((size_t)m.B * 3 * tpix), rgb(3 * tpix);
+            HIP_OK(hipMemcpy(planar.data(), dc, planar.size(), hipMemcpyDeviceToHost), "download");
+            char head[64];
+            snprintf(head, sizeof head, "P6\n%d %d\n255\n", cam.width, cam.height);
+            for (int b = 0; b < m.B; ++b) {
+                for (size_t i = 0; i < tpix; ++i)
+                    for (int ch = 0; ch < 3; ++ch) rgb[3 * i + ch] = planar[((size_t)b * 3 + ch) * tpix + i];
+                if (!write_bytes(pair_path(reg_image_path, m.B, b, ".ppm"), head, rgb.data(), rgb.size())) return fail("cannot write the registered image");
+            }
+        }
+        if (repeat > 0) {
+            hipEvent_t t0, t1;
+            HIP_OK(hipEventCreate(&t0), "hipEventCreate");
+            HIP_OK(hipEventCreate(&t1), "hipEventCreate");
+            HIP_OK(hipEventRecord(t0, s), "hipEventRecord");
+            for (int i = 0; i < repeat; ++i)
+                if (s2m2_register(&rd, s) != 0) return fail_lib("s2m2_register failed");
+            HIP_OK(hipEventRecord(t1, s), "hipEventRecord");
+            HIP_OK(hipEventSynchronize(t1), "timed register runs");
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, t0, t1), "hipEventElapsedTime");
+            printf("{\"register_covered\": %d, \"repeat\": %d, \"register_us_per_pair\": %.2f}\n", hcount[0], repeat, 1000.f * ms / repeat / m.B);
+            (void)hipEventDestroy(t0);
+            (void)hipEventDestroy(t1);
+        }
+        (void)hipFree(dimg);
+        (void)hipFree(dws);
+        (void)hipFree(dd);
+        (void)hipFree(di);
+        (void)hipFree(dc);
+        (void)hipFree(dcount);
     }
     if (gt_path) {
         const int gt_h = gt_rows / m.B;

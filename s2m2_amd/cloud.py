@@ -9,7 +9,11 @@ its inputs and its outputs this module only allocates; the host reads ``count`` 
 differ by at most ``max_jump``, as int32 vertex ranks in raster order of their quads (the rule: include/s2m2_hip.h, K20).  Three launches, no
 synchronisation, capturable; the host reads the counts in the accessors of ``Mesh`` alone.
 
-A record is 16 bytes -- ``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
+``register`` (K21, ``s2m2_register``) moves the depth map into another camera -- the colour camera of a rig, the right view (``right_camera``),
+a virtual view: a z-buffered forward warp that keeps the nearest surface per target pixel, with the winners' colours, their source indices and
+the visibility of every left pixel from that camera (the rule: include/s2m2_hip.h, K21).  Three launches, no synchronisation, capturable.
+
+A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
 from __future__ import annotations
@@ -224,3 +228,65 @@ def mesh(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch
              max_jump=max_jump, records=records, count=count, faces=faces, face_count=face_count, workspace=workspace, index=index, depth=depth,
              mask=mask)
     return Mesh(records, count, faces, face_count, index, depth, mask)
+
+
+class Camera:
+    """A pinhole target camera for ``register``: the image size, the intrinsics and the pose relative to the rectified left camera -- a point p
+    of the left camera's frame is ``R @ p + t`` in this camera's (``R`` (3,3), ``t`` (3,) in the unit of z, i.e. after ``depth_scale``)."""
+
+    def __init__(self, width: int, height: int, fx: float, fy: float, cx: float, cy: float, R=None, t=None):
+        self.width, self.height = int(width), int(height)
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self.R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64).reshape(3, 3)
+        self.t = np.zeros(3) if t is None else np.asarray(t, dtype=np.float64).reshape(3)
+
+    def __repr__(self) -> str:
+        return (f"Camera({self.width}x{self.height}, fx={self.fx}, fy={self.fy}, cx={self.cx}, cy={self.cy}, R={self.R.tolist()}, "
+                f"t={self.t.tolist()})")
+
+
+def right_camera(calib: Dict[str, object], width: int, height: int, depth_scale: float = 1000.0) -> Camera:
+    """The rectified right view of a Middlebury calib (``read_calib_file``): cam1's intrinsics, no rotation, and the left camera's origin
+    one baseline to the left of the right camera's: t = (-baseline / depth_scale, 0, 0)."""
+    k = np.asarray(calib["cam1"], dtype=np.float64)
+    return Camera(width, height, k[0, 0], k[1, 1], k[0, 2], k[1, 2], np.eye(3), (-float(calib["baseline"]) / float(depth_scale), 0.0, 0.0))
+
+
+class Registered:
+    """What ``register`` returns, all on the device and in the TARGET camera unless noted: ``depth`` (B,1,Ht,Wt) fp32 z of the nearest surface
+    (0: hole), ``index`` (B,1,Ht,Wt) int32 source pixel v*W+u that won (-1: hole), ``image`` (B,3,Ht,Wt) uint8 or None, ``visible`` (B,1,H,W)
+    uint8 in the SOURCE camera (1: the pixel won a target pixel) or None, ``count`` (B) int32 covered target pixels or None."""
+
+    def __init__(self, depth: torch.Tensor, index: torch.Tensor, image: Optional[torch.Tensor], visible: Optional[torch.Tensor],
+                 count: Optional[torch.Tensor]):
+        self.depth, self.index, self.image, self.visible, self.count = depth, index, image, visible, count
+
+    def holes(self, b: int = 0) -> int:
+        """target pixels of pair b that nothing covers -- reads ``count`` on the host (synchronises)"""
+        if self.count is None:
+            raise ValueError("Registered.holes: register was called with want_count=False")
+        return self.depth.shape[-2] * self.depth.shape[-1] - int(self.count[b].item())
+
+
+def register(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, cx: float, cy: float, baseline: float,
+             doffs: float = 0.0, to: Camera, splat: int = 2, fy: Optional[float] = None, depth_scale: float = 1000.0,
+             depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True, want_image: bool = True,
+             want_visible: bool = False, want_count: bool = True) -> Registered:
+    """``reproject``'s operands and conventions -> the depth map in the camera ``to`` (K21, ``s2m2_register``): every kept pixel is
+    back-projected as in ``reproject``, moved by ``to.R``, ``to.t``, projected and splatted over ``splat`` x ``splat`` target pixels into a
+    z-buffer that keeps the nearest surface (the rule: include/s2m2_hip.h, K21).  Three launches, no synchronisation, capturable."""
+    B = disp.shape[0]
+    H, W = image.shape[-2:]
+    Ht, Wt = to.height, to.width
+    dev = disp.device
+    depth = torch.empty((B, 1, Ht, Wt), device=dev, dtype=torch.float32)
+    index = torch.empty((B, 1, Ht, Wt), device=dev, dtype=torch.int32)
+    image_t = torch.empty((B, 3, Ht, Wt), device=dev, dtype=torch.uint8) if want_image else None
+    visible = torch.empty((B, 1, H, W), device=dev, dtype=torch.uint8) if want_visible else None
+    count = torch.empty((B,), device=dev, dtype=torch.int32) if want_count else None
+    workspace = torch.empty((hip.register_workspace_bytes(B, Ht, Wt),), device=dev, dtype=torch.uint8)
+    hip.register(disp, occ, conf, image, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs, depth_scale=depth_scale,
+                 depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min, unfiltered=not filtered,
+                 Ht=Ht, Wt=Wt, splat=splat, fx_t=to.fx, fy_t=to.fy, cx_t=to.cx, cy_t=to.cy, R=to.R.ravel().tolist(), t=to.t.tolist(),
+                 workspace=workspace, depth_t=depth, index_t=index, image_t=image_t, visible=visible, count=count)
+    return Registered(depth, index, image_t, visible, count)

@@ -74,10 +74,11 @@ __global__ __launch_bounds__(kRasterThreads) void cloud_scatter_kernel(const Sca
 }
 
 // every check of a s2m2_cloud_desc that include/s2m2_hip.h lists, then the kernel parameters: shared with s2m2_mesh (mesh.hip), which takes the
-// same descriptor fields (`what` prefixes the messages) with its own tile size
-int cloud_validate(const s2m2_cloud_desc* d, const char* what, int tile_pixels, CloudParams& p, bool& vec) {
+// same descriptor fields (`what` prefixes the messages) with its own tile size.  K21 (register.hip) reads the inputs alone and has outputs of its
+// own: it passes a copy without the output fields and outputs = false
+int cloud_validate(const s2m2_cloud_desc* d, const char* what, int tile_pixels, CloudParams& p, bool& vec, bool outputs) {
     S2M2_REQUIRE(d->disp && d->occ && d->conf, "%s: null pointer (disp / occ / conf)", what);
-    S2M2_REQUIRE(d->depth || d->mask || d->count, "%s: no output requested (depth, mask and count are all null pointers)", what);
+    S2M2_REQUIRE(!outputs || d->depth || d->mask || d->count, "%s: no output requested (depth, mask and count are all null pointers)", what);
     if (int rc = check_padded_maps(what, "image", d->B, d->H, d->W, d->Hp, d->Wp)) return rc;
     S2M2_REQUIRE(d->fx > 0.0 && d->fy > 0.0, "%s: fx and fy must be positive (fx=%g fy=%g)", what, d->fx, d->fy);
     S2M2_REQUIRE(d->depth_scale > 0.0, "%s: depth_scale must be positive (%g)", what, d->depth_scale);

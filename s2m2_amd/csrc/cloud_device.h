@@ -101,8 +101,8 @@ struct MeshParams {
 };
 
 // cloud.hip.  The header's checks of a s2m2_cloud_desc, shared by s2m2_cloud and s2m2_mesh (`what` prefixes the messages); fills p, with the
-// tile geometry of tile_pixels
-int cloud_validate(const s2m2_cloud_desc* d, const char* what, int tile_pixels, CloudParams& p, bool& vec);
+// tile geometry of tile_pixels.  outputs = false (K21): the descriptor need not request an output
+int cloud_validate(const s2m2_cloud_desc* d, const char* what, int tile_pixels, CloudParams& p, bool& vec, bool outputs = true);
 // K20's vertex launch: cloud_scatter_kernel with the rank-map option on mp's tile geometry
 int mesh_vertices(const MeshParams& mp, bool vec, int image_dtype, dim3 grid, hipStream_t stream);
 

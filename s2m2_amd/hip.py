@@ -129,6 +129,13 @@ class MeshDesc(ctypes.Structure):
     _fields_ = [("cloud", CloudDesc), ("faces", _vp), ("face_count", _vp), ("index", _vp), ("face_capacity", _ll), ("max_jump", ctypes.c_double)]
 
 
+class RegisterDesc(ctypes.Structure):
+    """mirror of s2m2_register_desc (include/s2m2_hip.h): K21, the depth map registered to a second camera"""
+    _fields_ = [("cloud", CloudDesc), ("Ht", _i), ("Wt", _i), ("splat", _i), ("fx_t", ctypes.c_double), ("fy_t", ctypes.c_double),
+                ("cx_t", ctypes.c_double), ("cy_t", ctypes.c_double), ("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("depth_t", _vp),
+                ("index_t", _vp), ("image_t", _vp), ("visible", _vp), ("count", _vp), ("workspace", _vp)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -234,6 +241,8 @@ SIGNATURES = {
     "s2m2_mesh_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_mesh_tile_rows": (_i, [_i, _i]),
     "s2m2_mesh": (_i, [ctypes.POINTER(MeshDesc), _vp]),
+    "s2m2_register_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_register": (_i, [ctypes.POINTER(RegisterDesc), _vp]),
 }
 
 
@@ -1276,3 +1285,6 @@ from .hip_tail import conv_block_tail, conv_block_tail_supported  # noqa: E402,F
 
 # K20 (s2m2_mesh): likewise, from hip_mesh.py
 from .hip_mesh import mesh, mesh_tile_rows, mesh_workspace_bytes  # noqa: E402,F401
+
+# K21 (s2m2_register): likewise, from hip_register.py
+from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
