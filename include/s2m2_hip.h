@@ -45,7 +45,8 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * missing symbol and asks for a rebuild.  Still 800 with s2m2_disp_eval, s2m2_eval_workspace_bytes, s2m2_eval_tile_rows and s2m2_eval_desc (K18, the
  * evaluation stage behind the forward), added the same way, and with s2m2_mesh, s2m2_mesh_workspace_bytes, s2m2_mesh_tile_rows and s2m2_mesh_desc
  * (K20, the surface mesh behind the 3D stage), and with s2m2_register, s2m2_register_workspace_bytes and s2m2_register_desc (K21, the depth
- * map registered to a second camera). */
+ * map registered to a second camera), and with s2m2_segment, s2m2_segment_workspace_bytes, s2m2_segment_tile_rows, s2m2_segment_tile_cols and
+ * s2m2_segment_desc (K22, connected components and the speckle filter). */
 #define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
@@ -1019,6 +1020,65 @@ typedef struct s2m2_register_desc {
 } s2m2_register_desc;
 size_t s2m2_register_workspace_bytes(int B, int Ht, int Wt);   /* 0: bad extents */
 int s2m2_register(const s2m2_register_desc* desc, void* stream);
+
+/*
+ * K22 -- connected components and speckle filter: the transitive closure of K20's "joined" relation, the size of every component, and the
+ *   disparity map with the small components removed (what OpenCV's filterSpeckles does for classical stereo; the reference leaves it to open3d
+ *   on the host).  Like K18, K20 and K21 it has no counterpart in the reference: the semantics are defined here and pinned by the numpy oracle
+ *   of tests/segment_oracle.py.  Still S2M2_ABI_VERSION 800: the entry points are added, nothing changes in place.
+ *   `cloud` holds the INPUT fields of s2m2_cloud, with their meaning, as s2m2_register takes them: the padded maps, H, W, Hp, Wp (fused crop),
+ *   camera and filter parameters, unfiltered.  image is not read.  Its output fields (depth, mask, records, count, capacity, workspace) are
+ *   IGNORED.
+ *   keep of a pixel is K15's, formula for formula (the same device function).  d is the value of the disp map at the pixel (the map's own
+ *   value, not the filter's -1).  A NaN or infinite disparity is never kept (K15's z is 0 for it), so d is finite wherever the rule is applied.
+ *   Two pixels p, q that are neighbours in a row (left / right) or in a column (up / down) are JOINED iff
+ *       keep(p) && keep(q) && fabsf(d_p - d_q) <= (float)max_jump
+ *     K20's rule on the 4-neighbourhood: one fp32 subtraction, exact.  Diagonal neighbours are not joined by themselves.
+ *   A COMPONENT is a class of the transitive closure of "joined" over the kept pixels of ONE pair; components never cross pairs.  A kept
+ *   pixel with no joined neighbour is a component of size 1.
+ *   outputs, each optional (NULL), at least one:
+ *     label    (B,1,H,W) int32: for a kept pixel the raster index v * W + u of the FIRST pixel (smallest raster index) of its component; -1
+ *              for a pixel that is not kept
+ *     size     (B,1,H,W) int32: the number of pixels of the pixel's component; 0 where not kept
+ *     mask     (B,1,H,W) uint8: survive = keep && size >= min_size
+ *     disp_out (B,1,Hp,Wp) fp32, PADDED geometry: the disp map's own value where survive, -1.0f everywhere else, the border outside the crop
+ *              included.  Fed to s2m2_cloud / s2m2_mesh / s2m2_register with unfiltered = 1 it yields exactly the surviving pixels with their
+ *              z WHENEVER K15 itself drops d <= 0, that is whenever 1e9f / depth_scale >= depth_trunc; with depth_trunc <= 0 (1e9) K15 keeps
+ *              d <= 0 at z = 1e9f / depth_scale as the reference's formula does, the removed pixels included.  Must not alias cloud.disp
+ *     stats    (B,4) int32: kept pixels, components, surviving pixels, surviving components of every pair
+ *   workspace: >= s2m2_segment_workspace_bytes(B, H, W) bytes, 4-byte aligned, always required: two int32 planes (parent links, sizes at the
+ *   roots).  Nothing depends on what it or the outputs held before.
+ *   Four launches (three where a pair is a single tile: a function of the extents, not of the data), no host step, no waiting between blocks.
+ *   (A) local: a block takes a tile of s2m2_segment_tile_rows x s2m2_segment_tile_cols pixels -- tile column tx spans the image columns
+ *   [tx * tile_cols - s, (tx + 1) * tile_cols - s) with s = ((Wp - W) / 2) & 3, tile row ty the rows [ty * tile_rows, (ty + 1) * tile_rows) --,
+ *   evaluates keep, resolves the tile's components by union-find in LDS, counts their pixels there, and stores every pixel's root as a global
+ *   raster index and every root's count.  (B) border: one thread per pixel of a tile's right column or bottom row unites it with its joined
+ *   neighbour across the border (int32 atomic minima on the link array).  (C) flatten: every link is replaced by its root, and the count of a
+ *   tile's root moves to the component's root (one int32 atomic add per tile and component).  (D) outputs: a walk over the padded geometry.  A link only ever moves to a smaller index of its component, so every
+ *   loop is bounded by an index, and the root of a component is its smallest raster index whatever the order of arrival; sizes and counts are
+ *   integer sums: the result is bit-reproducible although this stage uses atomics.
+ *   Launch plans: s2m2_segment is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing;
+ *   the stage runs after s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ *   Errors (before any device call): null descriptor; everything s2m2_cloud checks on its inputs (maps, extents, fx, fy, depth_scale, image
+ *   dtype, alignment); H * W >= 2^30; no output requested; a missing or misaligned workspace; label, size, disp_out or stats not 4-byte aligned
+ *   (mask: any alignment); disp_out == cloud.disp; max_jump negative or NaN (+inf is allowed: every kept pair of neighbours is joined);
+ *   min_size < 1 or > 2^30.
+ */
+typedef struct s2m2_segment_desc {
+    s2m2_cloud_desc cloud;
+    int32_t*       label;
+    int32_t*       size;
+    unsigned char* mask;
+    float*         disp_out;
+    int32_t*       stats;
+    void*          workspace;
+    double         max_jump;   /* px, >= 0 */
+    long long      min_size;   /* >= 1; 1 removes nothing (labels and sizes only) */
+} s2m2_segment_desc;
+size_t s2m2_segment_workspace_bytes(int B, int H, int W);   /* 0: bad extents */
+int s2m2_segment_tile_rows(int H, int W);                   /* the tile of launch A (at most H), so that tests can aim at its borders; 0: bad extents */
+int s2m2_segment_tile_cols(int H, int W);                   /* ... (at most W) */
+int s2m2_segment(const s2m2_segment_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,14 @@
 //   pair each, named as --ply names its files (OUT.<b>.f32, OUT.<b>.i32, OUT.<b>.ppm).  With --repeat: {"register_covered", "repeat", "register_us_per_pair"} on a line
 //   of its own.
 //
+// --min-size N [--max-jump X] [--labels OUT.i32] [--segment-mask OUT.u8]: the speckle filter (s2m2_segment) behind the forward and in front of
+//   every 3D output above: the 4-connected components of the kept pixels whose neighbouring disparities differ by at most X px (the --max-jump
+//   of --mesh, default 1), and the disparity map without the components of fewer than N pixels (N >= 1; 1 removes nothing).  Needs --calib;
+//   honours --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered.  --ply, --mesh, --depth and --register* then read the
+//   filtered map with the filter already applied (unfiltered = 1).  --labels: raw int32 (B,1,H,W), the first raster index of every kept pixel's
+//   component, -1 = not kept; --segment-mask: raw uint8 (B,1,H,W), 1 = survives.  With --repeat: {"segment_kept", "segment_components",
+//   "segment_surviving", "repeat", "segment_us_per_pair"} on a line of its own.  Without --min-size nothing here happens.
+//
 // Evaluation against ground truth (s2m2_disp_eval on the device buffers of the run; without --gt nothing below happens):
 //   --gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] [--thresholds a,b,c] [--conf-min X] [--occ-min X] --metrics OUT.json
 // --gt: a greyscale PFM (Pf) of W x (B * H) pixels, H <= out_h and W <= out_w of the engine: the ground truths of the B pairs stacked top to
@@ -53,7 +61,8 @@
 static const char* USAGE =
     "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
     "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
-    "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]] "
+    "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]";
 
 static int fail(const char* what) {
@@ -248,6 +257,8 @@ int main(int argc, char** argv) {
     const char *calib_path = nullptr, *image_path = nullptr, *ply_path = nullptr, *depth_path = nullptr, *mesh_path = nullptr;
     const char* max_jump_arg = nullptr;
     const char *register_cam = nullptr, *reg_depth_path = nullptr, *reg_image_path = nullptr, *reg_index_path = nullptr, *splat_arg = nullptr;
+    const char *min_size_arg = nullptr, *labels_path = nullptr, *segmask_path = nullptr;
+    long long min_size = 1;
     int splat = 2;
     double max_jump = 1.0;
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5;
@@ -268,6 +279,9 @@ int main(int argc, char** argv) {
         else if (strcmp(argv[i], "--register-depth") == 0 && i + 1 < argc) reg_depth_path = argv[++i];
         else if (strcmp(argv[i], "--register-image") == 0 && i + 1 < argc) reg_image_path = argv[++i];
         else if (strcmp(argv[i], "--register-index") == 0 && i + 1 < argc) reg_index_path = argv[++i];
+        else if (strcmp(argv[i], "--min-size") == 0 && i + 1 < argc) min_size_arg = argv[++i];
+        else if (strcmp(argv[i], "--labels") == 0 && i + 1 < argc) labels_path = argv[++i];
+        else if (strcmp(argv[i], "--segment-mask") == 0 && i + 1 < argc) segmask_path = argv[++i];
         else if (strcmp(argv[i], "--depth-trunc") == 0 && i + 1 < argc) depth_trunc = atof(argv[++i]);
         else if (strcmp(argv[i], "--depth-scale") == 0 && i + 1 < argc) depth_scale = atof(argv[++i]);
         else if (strcmp(argv[i], "--conf-min") == 0 && i + 1 < argc) conf_min = atof(argv[++i]);
@@ -290,9 +304,16 @@ int main(int argc, char** argv) {
         splat = atoi(splat_arg);
         if (splat < 1 || splat > 4) return fail("--splat: 1, 2, 3 or 4");
     }
-    if (!mesh_path && !register_cam && (calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
-    if (register_cam && !mesh_path && !ply_path && depth_path) return fail("--depth needs --ply or --mesh");
-    if (max_jump_arg && !mesh_path) return fail("--max-jump needs --mesh");
+    if (min_size_arg && !calib_path) return fail("--min-size needs --calib");
+    if (!min_size_arg && (labels_path || segmask_path)) return fail("--labels and --segment-mask need --min-size");
+    if (min_size_arg) {
+        char* end = nullptr;
+        min_size = strtoll(min_size_arg, &end, 10);
+        if (end == min_size_arg || *end || min_size < 1 || min_size > (1LL << 30)) return fail("--min-size: an integer >= 1 (at most 2^30)");
+    }
+    if (!mesh_path && !register_cam && !min_size_arg && (calib_path == nullptr) != (ply_path == nullptr)) return fail("--calib and --ply come together");
+    if ((register_cam || min_size_arg) && !mesh_path && !ply_path && depth_path) return fail("--depth needs --ply or --mesh");
+    if (max_jump_arg && !mesh_path && !min_size_arg) return fail("--max-jump needs --mesh or --min-size");
     if (max_jump_arg) {
         char* end = nullptr;
         max_jump = strtod(max_jump_arg, &end);
@@ -391,6 +412,73 @@ int main(int argc, char** argv) {
         (void)hipEventDestroy(t0);
         (void)hipEventDestroy(t1);
     }
+    // --min-size: the 3D outputs below read the map K22 leaves, with the filter already applied
+    const float* disp3d = dout[0];
+    int unfiltered3d = unfiltered;
+    float* dseg = nullptr;
+    if (min_size_arg) {
+        Calib cal;
+        if (!read_calib(calib_path, cal)) return fail("--calib: cannot read cam0 and baseline from the file");
+        if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
+        const size_t npix = (size_t)m.H * m.W;
+        const size_t ws_bytes = s2m2_segment_workspace_bytes(m.B, m.H, m.W);
+        if (ws_bytes == 0) return fail("--min-size: extents too large");
+        void* dws = nullptr;
+        int32_t *dlabel = nullptr, *dstats = nullptr;
+        unsigned char* dmask = nullptr;
+        HIP_OK(hipMalloc(&dws, ws_bytes), "hipMalloc");
+        HIP_OK(hipMalloc((void**)&dseg, map * sizeof(float)), "hipMalloc");
+        HIP_OK(hipMalloc((void**)&dstats, m.B * 4 * sizeof(int32_t)), "hipMalloc");
+        if (labels_path) HIP_OK(hipMalloc((void**)&dlabel, (size_t)m.B * npix * sizeof(int32_t)), "hipMalloc");
+        if (segmask_path) HIP_OK(hipMalloc((void**)&dmask, (size_t)m.B * npix), "hipMalloc");
+        s2m2_segment_desc sd;
+        memset(&sd, 0, sizeof sd);
+        s2m2_cloud_desc& cd = sd.cloud;
+        cd.disp = dout[0]; cd.occ = dout[1]; cd.conf = dout[2];
+        cd.image_dtype = S2M2_F32;
+        cd.B = m.B; cd.H = m.H; cd.W = m.W; cd.Hp = m.out_h; cd.Wp = m.out_w;
+        cd.unfiltered = unfiltered;
+        cd.fx = cal.fx; cd.fy = cal.fy; cd.cx = cal.cx; cd.cy = cal.cy; cd.baseline = cal.baseline; cd.doffs = cal.doffs;
+        cd.depth_scale = depth_scale; cd.depth_trunc = depth_trunc; cd.conf_min = conf_min; cd.occ_min = occ_min;
+        sd.label = dlabel; sd.mask = dmask; sd.disp_out = dseg; sd.stats = dstats; sd.workspace = dws;
+        sd.max_jump = max_jump; sd.min_size = min_size;
+        if (s2m2_segment(&sd, s) != 0) return fail_lib("s2m2_segment failed");
+        HIP_OK(hipStreamSynchronize(s), "s2m2_segment");
+        std::vector<int32_t> hstats((size_t)m.B * 4);
+        HIP_OK(hipMemcpy(hstats.data(), dstats, hstats.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+        if (labels_path) {
+            std::vector<int32_t> hl32((size_t)m.B * npix);
+            HIP_OK(hipMemcpy(hl32.data(), dlabel, hl32.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+            if (!write_bytes(labels_path, "", hl32.data(), hl32.size() * sizeof(int32_t))) return fail("cannot write the labels");
+        }
+        if (segmask_path) {
+            std::vector<unsigned char> hm((size_t)m.B * npix);
+            HIP_OK(hipMemcpy(hm.data(), dmask, hm.size(), hipMemcpyDeviceToHost), "download");
+            if (!write_bytes(segmask_path, "", hm.data(), hm.size())) return fail("cannot write the segment mask");
+        }
+        if (repeat > 0) {
+            hipEvent_t t0, t1;
+            HIP_OK(hipEventCreate(&t0), "hipEventCreate");
+            HIP_OK(hipEventCreate(&t1), "hipEventCreate");
+            HIP_OK(hipEventRecord(t0, s), "hipEventRecord");
+            for (int i = 0; i < repeat; ++i)
+                if (s2m2_segment(&sd, s) != 0) return fail_lib("s2m2_segment failed");
+            HIP_OK(hipEventRecord(t1, s), "hipEventRecord");
+            HIP_OK(hipEventSynchronize(t1), "timed segment runs");
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, t0, t1), "hipEventElapsedTime");
+            printf("{\"segment_kept\": %d, \"segment_components\": %d, \"segment_surviving\": %d, \"repeat\": %d, \"segment_us_per_pair\": %.2f}\n",
+                   hstats[0], hstats[1], hstats[2], repeat, 1000.f * ms / repeat / m.B);
+            (void)hipEventDestroy(t0);
+            (void)hipEventDestroy(t1);
+        }
+        (void)hipFree(dws);
+        (void)hipFree(dlabel);
+        (void)hipFree(dmask);
+        (void)hipFree(dstats);
+        disp3d = dseg;
+        unfiltered3d = 1;
+    }
     if (calib_path && (ply_path || mesh_path)) {
         Calib cal;
         if (!read_calib(calib_path, cal)) return fail("--calib: cannot read cam0 and baseline from the file");
@@ -425,12 +513,12 @@ int main(int argc, char** argv) {
         s2m2_mesh_desc md;                                   // --mesh: one s2m2_mesh call writes the vertices (the --ply records) and the faces
         memset(&md, 0, sizeof md);
         s2m2_cloud_desc& cd = md.cloud;
-        cd.disp = dout[0]; cd.occ = dout[1]; cd.conf = dout[2];
+        cd.disp = disp3d; cd.occ = dout[1]; cd.conf = dout[2];
         cd.image = image_path ? dimg : dl;
         cd.image_dtype = image_path ? 2 : S2M2_F32;
         cd.depth = ddepth; cd.records = drec; cd.count = dcount; cd.workspace = dws;
         cd.B = m.B; cd.H = m.H; cd.W = m.W; cd.Hp = m.out_h; cd.Wp = m.out_w;
-        cd.unfiltered = unfiltered;
+        cd.unfiltered = unfiltered3d;
         cd.capacity = (long long)npix;
         cd.fx = cal.fx; cd.fy = cal.fy; cd.cx = cal.cx; cd.cy = cal.cy; cd.baseline = cal.baseline; cd.doffs = cal.doffs;
         cd.depth_scale = depth_scale; cd.depth_trunc = depth_trunc; cd.conf_min = conf_min; cd.occ_min = occ_min;
@@ -537,11 +625,11 @@ int main(int argc, char** argv) {
         s2m2_register_desc rd;
         memset(&rd, 0, sizeof rd);
         s2m2_cloud_desc& cd = rd.cloud;
-        cd.disp = dout[0]; cd.occ = dout[1]; cd.conf = dout[2];
+        cd.disp = disp3d; cd.occ = dout[1]; cd.conf = dout[2];
         cd.image = image_path ? dimg : dl;
         cd.image_dtype = image_path ? 2 : S2M2_F32;
         cd.B = m.B; cd.H = m.H; cd.W = m.W; cd.Hp = m.out_h; cd.Wp = m.out_w;
-        cd.unfiltered = unfiltered;
+        cd.unfiltered = unfiltered3d;
         cd.fx = cal.fx; cd.fy = cal.fy; cd.cx = cal.cx; cd.cy = cal.cy; cd.baseline = cal.baseline; cd.doffs = cal.doffs;
         cd.depth_scale = depth_scale; cd.depth_trunc = depth_trunc; cd.conf_min = conf_min; cd.occ_min = occ_min;
         rd.Ht = cam.height; rd.Wt = cam.width; rd.splat = splat;
@@ -677,6 +765,7 @@ int main(int argc, char** argv) {
     }
     s2m2_engine_destroy(eng);
     for (auto& p : dout) (void)hipFree(p);
+    (void)hipFree(dseg);
     (void)hipFree(dl);
     (void)hipFree(dr);
     (void)hipStreamDestroy(s);

@@ -13,6 +13,10 @@ synchronisation, capturable; the host reads the counts in the accessors of ``Mes
 a virtual view: a z-buffered forward warp that keeps the nearest surface per target pixel, with the winners' colours, their source indices and
 the visibility of every left pixel from that camera (the rule: include/s2m2_hip.h, K21).  Three launches, no synchronisation, capturable.
 
+``segment`` (K22, ``s2m2_segment``) is the speckle filter in front of all three: the connected components of the kept pixels under ``mesh``'s
+"joined" rule on the 4-neighbourhood, their sizes, and the disparity map with the components below ``min_size`` removed (the rule:
+include/s2m2_hip.h, K22).  Four launches, no synchronisation, capturable.
+
 A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
@@ -290,3 +294,54 @@ def register(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: t
                  Ht=Ht, Wt=Wt, splat=splat, fx_t=to.fx, fy_t=to.fy, cx_t=to.cx, cy_t=to.cy, R=to.R.ravel().tolist(), t=to.t.tolist(),
                  workspace=workspace, depth_t=depth, index_t=index, image_t=image_t, visible=visible, count=count)
     return Registered(depth, index, image_t, visible, count)
+
+
+class Segments:
+    """What ``segment`` returns, all on the device: ``disp`` (B,1,Hp,Wp) fp32, the PADDED disparity with -1 wherever the pixel does not survive
+    (border included); ``mask`` (B,1,H,W) uint8 (1: kept and in a component of at least ``min_size`` pixels); ``label`` (B,1,H,W) int32 or None
+    (raster index of the first pixel of the component, -1: not kept); ``size`` (B,1,H,W) int32 or None (pixels of the component, 0: not kept);
+    ``stats`` (B,4) int32: kept pixels, components, surviving pixels, surviving components."""
+
+    def __init__(self, disp: torch.Tensor, mask: torch.Tensor, label: Optional[torch.Tensor], size: Optional[torch.Tensor], stats: torch.Tensor):
+        self.disp, self.mask, self.label, self.size, self.stats = disp, mask, label, size, stats
+
+    def kept(self, b: int = 0) -> int:
+        """kept pixels of pair b -- this and the three readers below read ``stats`` on the host (synchronise)"""
+        return int(self.stats[b, 0].item())
+
+    def components(self, b: int = 0) -> int:
+        return int(self.stats[b, 1].item())
+
+    def surviving(self, b: int = 0) -> int:
+        return int(self.stats[b, 2].item())
+
+    def surviving_components(self, b: int = 0) -> int:
+        return int(self.stats[b, 3].item())
+
+
+def segment(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: int, W: int, fx: float, cx: float, cy: float, baseline: float,
+            doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0, depth_trunc: Optional[float] = None,
+            conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True, max_jump: float = 1.0, min_size: int = 1,
+            want_label: bool = True, want_size: bool = True) -> Segments:
+    """``reproject``'s maps and conventions (no image: ``H`` and ``W`` name the fused crop) -> Segments (K22, ``s2m2_segment``).  Kept
+    neighbours in a row or a column are joined where their disparities differ by at most ``max_jump`` (``mesh``'s rule; inf joins every kept
+    neighbour); a component is a class of the transitive closure; a pixel survives if it is kept and its component has at least ``min_size``
+    pixels (1: nothing is removed).  Only allocates: four launches, no synchronisation, capturable.
+
+    Composition: ``s = segment(...)`` then ``reproject(s.disp, occ, conf, image, ..., filtered=False)`` (or ``mesh`` / ``register``) gives
+    exactly the surviving pixels with their original z -- whenever K15 itself drops d <= 0, that is whenever ``1e9 / depth_scale >=
+    depth_trunc``.  With ``depth_trunc=None`` K15 keeps d <= 0 at z = 1e6 (depth_scale 1000) as the reference's formula does, the removed pixels
+    included: pass a real truncation distance to the stage behind."""
+    B, _, Hp, Wp = disp.shape
+    dev = disp.device
+    out = torch.empty((B, 1, Hp, Wp), device=dev, dtype=torch.float32)
+    mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.uint8)
+    label = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_label else None
+    size = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_size else None
+    stats = torch.empty((B, 4), device=dev, dtype=torch.int32)
+    workspace = torch.empty((hip.segment_workspace_bytes(B, H, W),), device=dev, dtype=torch.uint8)
+    hip.segment(disp, occ, conf, H=H, W=W, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs,
+                depth_scale=depth_scale, depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min,
+                unfiltered=not filtered, max_jump=max_jump, min_size=min_size, workspace=workspace, label=label, size=size, mask=mask,
+                disp_out=out, stats=stats)
+    return Segments(out, mask, label, size, stats)

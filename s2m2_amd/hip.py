@@ -136,6 +136,12 @@ class RegisterDesc(ctypes.Structure):
                 ("index_t", _vp), ("image_t", _vp), ("visible", _vp), ("count", _vp), ("workspace", _vp)]
 
 
+class SegmentDesc(ctypes.Structure):
+    """mirror of s2m2_segment_desc (include/s2m2_hip.h): K22, connected components and the speckle filter"""
+    _fields_ = [("cloud", CloudDesc), ("label", _vp), ("size", _vp), ("mask", _vp), ("disp_out", _vp), ("stats", _vp), ("workspace", _vp),
+                ("max_jump", ctypes.c_double), ("min_size", _ll)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -243,6 +249,10 @@ SIGNATURES = {
     "s2m2_mesh": (_i, [ctypes.POINTER(MeshDesc), _vp]),
     "s2m2_register_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_register": (_i, [ctypes.POINTER(RegisterDesc), _vp]),
+    "s2m2_segment_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_segment_tile_rows": (_i, [_i, _i]),
+    "s2m2_segment_tile_cols": (_i, [_i, _i]),
+    "s2m2_segment": (_i, [ctypes.POINTER(SegmentDesc), _vp]),
 }
 
 
@@ -1288,3 +1298,5 @@ from .hip_mesh import mesh, mesh_tile_rows, mesh_workspace_bytes  # noqa: E402,F
 
 # K21 (s2m2_register): likewise, from hip_register.py
 from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
+# K22 (s2m2_segment): likewise, from hip_segment.py
+from .hip_segment import segment, segment_tile, segment_workspace_bytes  # noqa: E402,F401

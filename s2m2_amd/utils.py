@@ -9,6 +9,8 @@ image_utils.py) -- SURVEY.md section 8f rows 1-2: same names, arguments and retu
 * ``get_pointcloud``       model_utils.py:111-136 (depth from disparity + open3d's RGBD -> point cloud conversion; HIP kernels ``s2m2_cloud``)
 * ``get_mesh``             no counterpart in the reference: ``get_pointcloud``'s arguments -> the surface mesh that connects neighbouring
   pixels of similar disparity (HIP kernels ``s2m2_mesh``; ``s2m2_amd.cloud.mesh``)
+* ``filter_speckles``      no counterpart in the reference (its demos leave outlier removal to open3d on the host): ``get_pointcloud``'s
+  conventions -> the disparity with the small connected components removed (HIP kernels ``s2m2_segment``; ``s2m2_amd.cloud.segment``)
 * ``compute_confidence_scores``  the calibration objective (calibration/base.py:15-36 called 20 x 5 times one pair at a time by
   calibration/cem.py:66-72) for a whole population of rectified pairs at once: one batched forward, or sharded over the ranks of a
   ``torch.distributed`` group
@@ -182,3 +184,21 @@ def get_mesh(rgb, disp, calib, depth_trunc=None, max_jump=1.0):
         return cloud.mesh(disp_t, disp_t, disp_t, image, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
                           baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
                           max_jump=max_jump)
+
+
+def filter_speckles(disp, calib, depth_trunc=None, max_jump=1.0, min_size=100):
+    """``get_pointcloud``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter: ``disp`` (H,W) arrives filtered, -1
+    where invalid) -> the (H,W) fp32 disparity on the device with -1 also wherever the pixel's 4-connected component of similar disparity
+    (neighbours differ by at most ``max_jump`` px) has fewer than ``min_size`` pixels: the speckle filter in front of ``get_pointcloud`` /
+    ``get_mesh``."""
+    from . import cloud
+    disp_t = torch.as_tensor(disp)
+    device = disp_t.device if disp_t.is_cuda else torch.device("cuda")
+    disp_t = disp_t.to(device=device, dtype=torch.float32).contiguous()[None, None]
+    H, W = disp_t.shape[-2:]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(device):
+        s = cloud.segment(disp_t, disp_t, disp_t, H=H, W=W, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
+                          baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
+                          max_jump=max_jump, min_size=min_size, want_label=False, want_size=False)
+    return s.disp[0, 0]
