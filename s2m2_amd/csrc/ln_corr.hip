@@ -20,6 +20,7 @@
 // Algorithmic traffic per pair: 2*h*w*C*sizeof(T) read + h*w*w*sizeof(TO) written.
 #include "common.h"
 #include "launch.h"
+#include "ln_corr_select.h"
 #include "plan.h"
 #include <hip/hip_ext.h>
 #include <stdlib.h>
@@ -464,21 +465,14 @@ static int launch_ln_corr(const void* feat, const float* g, const float* bta, vo
     // carries two events on the dispatch)
     static size_t lds_granted[kMaxDevices] = {};                     // per instantiation
     if (reserve_lds(reinterpret_cast<const void*>(kern), CFG::lds_bytes(CFG::NWMAX), lds_granted, "ln_corr")) return 1;
-    const int tiles = (w + 31) / 32;                     // 32-pixel row tiles = waves needed per image row
-    int nstrip = (tiles + CFG::NWMAX - 1) / CFG::NWMAX;
-    // small problems: split rows into strips until the grid covers the chip (each strip re-reads / re-normalises the right row).  More, smaller
-    // blocks do not help the 120-row case (c2): 240 three-wave blocks 12.1 us, 480-600 one- / two-wave blocks 14.6-15.6 us (profiles/r05/k1_minblocks.txt)
-    while (B * h * nstrip < 200 && nstrip < tiles && (tiles + nstrip) / (nstrip + 1) >= 2) ++nstrip;
-    int nw = (tiles + nstrip - 1) / nstrip;
-    nw = (nw + CFG::NWGRAN - 1) / CFG::NWGRAN * CFG::NWGRAN;      // chunks of nw * TPW right tokens are whole 32-column tiles
-    const int nblocks = B * h * nstrip;
+    // strips, waves per block and the cache policy of the stores: ln_corr_select.h, whose block shapes are this configuration's
+    constexpr LnCorrShape shape = ln_corr_shape((int)sizeof(T), (int)sizeof(TO), CFG::C);
+    static_assert(shape.nwmax == CFG::NWMAX && shape.nwgran == CFG::NWGRAN && shape.tpw == CFG::TPW, "ln_corr_select.h restates LnCorrCfg");
     const int pitch = o.pitch > 0 ? o.pitch : w;
-    // cache policy of the volume stores (store_cv): sc1 write-through by default -- measured (profiles/r04/k1_store_modes.txt, ab_k1_store_sc1lib_overlap.txt)
-    // 19.2 -> 16.8 us back to back and 19.7-20.7 -> 17.7 us inside the forward against the write-back default of rounds 1-3; S2M2_K1_NT=0..4 A/B
-    // (only for volume rows on 128-byte lines: a write-through store of a PARTIAL line is a read-modify-write at the memory side -- dense 608-byte
-    // rows measured 25.0 us with sc1 against 21.8 with plain stores, profiles/r04/kbench.txt; the engine always allocates aligned rows)
     static const int k1_env = (int)env_int("S2M2_K1_NT", -1);
-    const int k1_flags = k1_env >= 0 ? k1_env : ((pitch * (int)sizeof(TO)) % 128 == 0 ? 2 : 0);
+    const LnCorrPlan plan = ln_corr_plan(B, h, w, pitch, (int)sizeof(T), (int)sizeof(TO), CFG::C, k1_env);
+    const int nstrip = plan.nstrip, nw = plan.nw, k1_flags = plan.store_mode;
+    const int nblocks = B * h * nstrip;
     if (o.ev_start || o.ev_stop)
         hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(nw * 64), CFG::lds_bytes(nw), st, o.ev_start, o.ev_stop, 0,
                               static_cast<const T*>(feat), g, bta, static_cast<TO*>(cv), B, h, w, nstrip, o.band, pitch, k1_flags);
@@ -501,6 +495,18 @@ template <> struct LnCorrPick<float, 128>  { template <typename TO> using cfg = 
 template <> struct LnCorrPick<float, 192>  { template <typename TO> using cfg = LnCorrCfg<float, TO, 192, 8, 2, false>; };
 template <> struct LnCorrPick<float, 256>  { template <typename TO> using cfg = LnCorrCfg<float, TO, 256, 4, 2, false>; };
 template <> struct LnCorrPick<float, 384>  { template <typename TO> using cfg = LnCorrCfg<float, TO, 384, 4, 1, false>; };
+
+// ln_corr_select.h plans every launch from its own table of block shapes: the table is these 15 configurations'
+template <typename T, typename TO, int C> constexpr bool select_restates_cfg() {
+    using CFG = typename LnCorrPick<T, C>::template cfg<TO>;
+    constexpr LnCorrShape s = ln_corr_shape((int)sizeof(T), (int)sizeof(TO), C);
+    return s.nwmax == CFG::NWMAX && s.nwgran == CFG::NWGRAN && s.tpw == CFG::TPW;
+}
+#define S2M2_SAME(T, TO)                                                                                                     \
+    static_assert(select_restates_cfg<T, TO, 64>() && select_restates_cfg<T, TO, 128>() && select_restates_cfg<T, TO, 192>() && \
+                  select_restates_cfg<T, TO, 256>() && select_restates_cfg<T, TO, 384>(), "ln_corr_select.h: NWMAX / NWGRAN / TPW of " #T " -> " #TO);
+S2M2_SAME(half_t, half_t) S2M2_SAME(half_t, float) S2M2_SAME(float, float)
+#undef S2M2_SAME
 
 template <typename T, typename TO, bool PRENORM = false>
 static int dispatch_c(const void* feat, const float* g, const float* bta, void* cv, int B, int h, int w, int C, const K1Opt& o, hipStream_t st) {
