@@ -660,7 +660,7 @@ int s2m2_convex_upsample(const float* const* x, float* const* out, const float* 
  * [A2,A3] multi-head attention softmax(Q K^T * scale) V, flash style (no score matrix in memory).  Replaces
  *   F.scaled_dot_product_attention and the explicit attention + positional-encoding einsums (attentions.py:42-50, :83-91).
  *   q, k, v, out: token rows; element (batch b, token n, head hd, e) at base + (b*N + n)*stride + hd*D + e  (so the fused
- *   QKV projection is read in place and the output is (tokens, heads*D)).  D multiple of 8, <= 256 (<= 128 with PE).
+ *   QKV projection is read in place and the output is (tokens, heads*D)).  D multiple of 8, <= 384 (<= 128 with PE).
  *   swap_halves = 1: keys/values of batch b come from batch (b + nb/2) % nb (symmetric cross attention, CrossAttn).
  *   pe_x != NULL selects SelfAttn(use_pe=True): tokens form a grid_h x grid_w grid (row major), pe_x (2*grid_w-1, 16) and
  *   pe_y (2*grid_h-1, 16) fp32 are the separable sinc tables of get_pe (utils.py:32-60) indexed by xq-xk+grid_w-1 /
@@ -677,6 +677,18 @@ int s2m2_attention(const void* q, const void* k, const void* v, void* out, long 
  *   forward (token grids above 96 x 96 cells = images above 3072 px per side have no PE instantiation).
  */
 int s2m2_attention_supported(int nb, int heads, int N, int D, int grid_w, int grid_h, int dtype);
+/*
+ * The launch s2m2_attention would make for this call, as its own planning code decides it (the walk of s2m2_attention_supported with Nq, Nk
+ *   and swap_halves given): the kernel instantiation -- padded head dim, fewest waves a block is built for, key-split mode, PE bin tiles
+ *   (0, 0 without PE), 32-key sub-tiles per stage, two-sweep softmax, queries in LDS, two stages in flight -- and the launch: waves per block,
+ *   query blocks per (batch, head), dynamic LDS bytes.  Host code only.  0 = planned, otherwise s2m2_last_error says why not (`*plan` zeroed).
+ *   tests/test_k4_cases_cpu.py holds every case of the K4 plan tests to what this entry reports.
+ */
+typedef struct s2m2_attn_plan {
+    int dp, minw, ksplit, nxt, nyt, nw, nblk, kt, twopass, qlds, deep;
+    long long lds_bytes;
+} s2m2_attn_plan;
+int s2m2_attention_plan(int nb, int heads, int Nq, int Nk, int D, int swap_halves, int grid_w, int grid_h, int dtype, s2m2_attn_plan* plan);
 
 /*
  * [A2,A3] 2x resampling of an NHWC activation: mode 0 = nn.AvgPool2d(2) (unet.py:25-30, stacked_MRT.py:22-27), mode 1 =

@@ -36,6 +36,9 @@
 
 namespace s2m2 {
 
+// s2m2_attention_plan: where launch_attn_t reports the launch it planned (host side, the calling thread's; null on every other path)
+static thread_local s2m2_attn_plan* t_plan_out = nullptr;
+
 constexpr size_t kLdsBytes = 160 * 1024;
 
 struct AttnArgs {
@@ -102,6 +105,9 @@ struct AttnCfg {
     //   d = 256 (512,1,304):  223 -> 256 us (312 registers either way, one block per CU: the extra QK^T sweep is not paid back) -> stays online
     static constexpr bool TWOPASS = S2M2_ATTN_TWOPASS && !PE_ && !KSPLIT_ && (DP_ == 192 || DP_ >= 384);
     static constexpr bool QLDS = S2M2_ATTN_QLDS && !PE_ && !KSPLIT_ && sizeof(T) == 2 && DP_ >= 384;
+    // key-split blocks (few, long rows; fp16, no PE) are chains of short stages -- two sub-tiles of arithmetic per wave between the barriers --
+    // whose K / V fetch (requested one stage ahead) is not covered by that arithmetic: they keep TWO stages in flight in registers
+    static constexpr bool DEEP = KSPLIT_ && !PE_ && sizeof(T) == 2 && !(S2M2_ATTN_DBG & 16);
     static constexpr size_t Q_OFF = (K_BYTES + V_BYTES + 15) / 16 * 16;
     static constexpr size_t Q_WAVE_BYTES = (size_t)32 * KRS * sizeof(T);
     // (measured and dropped, profiles/r04/ab_minwaves.txt: a second launch bound of three waves per SIMD takes the key-split kernel from 208 to 121
@@ -226,9 +232,7 @@ __global__ __launch_bounds__(CFG::MAXW * 64) void attention_kernel(AttnArgs a) {
     constexpr int K_TASKS = KVT * KP, V_TASKS = (KVT / 4) * KP;
     constexpr int MINT = 64 * CFG::MINW;                        // blocks have >= MINW waves (launch_attn)
     constexpr int K_IT_MAX = (K_TASKS + MINT - 1) / MINT, V_IT_MAX = (V_TASKS + MINT - 1) / MINT;
-    // key-split blocks (few, long rows; fp16, no PE) are chains of short stages -- two sub-tiles of arithmetic per wave between the barriers --
-    // whose K / V fetch (requested one stage ahead) is not covered by that arithmetic: they keep TWO stages in flight in registers
-    constexpr bool DEEP = CFG::KSPLIT && !CFG::PE && sizeof(T) == 2 && !(S2M2_ATTN_DBG & 16);
+    constexpr bool DEEP = CFG::DEEP;                           // two stages in flight in registers (AttnCfg)
     Vec16<T> rkA[K_IT_MAX], rkB[DEEP ? K_IT_MAX : 1];
     Vec16<T> rvA[V_IT_MAX][4], rvB[DEEP ? V_IT_MAX : 1][4];
     auto zero16 = []() { Vec16<T> z;
@@ -634,9 +638,13 @@ static int launch_attn_t(const AttnArgs& a, int nw, hipStream_t st) {
         lds = need(nw);
     }
     if (lds > kLdsBytes) return set_error("attention: %zu bytes of LDS needed (head dim %d, %d x %d token grid)", lds, a.D, a.gw, a.gh);
-    if (a.dry) return 0;
     const int ntq = (a.Nq + 31) / 32;
     const int nblk = KSPLIT ? ntq : (ntq + nw - 1) / nw;
+    if (t_plan_out) {
+        *t_plan_out = s2m2_attn_plan{DP, MINW, KSPLIT ? 1 : 0, PE ? NXT : 0, PE ? NYT : 0, nw, nblk, CFG::KT, CFG::TWOPASS ? 1 : 0, CFG::QLDS ? 1 : 0,
+                                     CFG::DEEP ? 1 : 0, (long long)lds};
+    }
+    if (a.dry) return 0;
     if ((long long)nblk * a.nb * a.heads >= (1LL << 31)) return set_error("attention: %lld blocks do not fit a grid dimension", (long long)nblk * a.nb * a.heads);
     AttnArgs b = a;
     b.nblk = nblk;
@@ -694,7 +702,9 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
         // few (batch, head) pairs (the 2-D global blocks at 1/32): smaller blocks until the grid covers the chip; every block
         // re-stages K/V from L2, which is cheap next to an idle GPU
         while (nw > 2 && (long long)((ntq + nw - 1) / nw) * bh < 512) nw = (nw + 1) / 2;
-        if (nw < 4) return launch_attn_w<T, DP, PE, 2>(a, nw, st);
+        // (a single query tile gives nw = 1: the staging loops of the MINW = 2 instantiation are sized for 128 threads, so the block gets its
+        // second wave -- without a query tile, but loading K / V and sitting in every barrier -- as the four-wave blocks below do)
+        if (nw < 4) return launch_attn_w<T, DP, PE, 2>(a, nw < 2 ? 2 : nw, st);
     }
     return launch_attn_w<T, DP, PE, 4>(a, nw < 4 ? 4 : nw, st);
 }
@@ -772,6 +782,22 @@ extern "C" int s2m2_attention_supported(int nb, int heads, int N, int D, int gri
     const int c = heads * ((D + 7) / 8 * 8);
     return attention_entry(nullptr, nullptr, nullptr, nullptr, 3 * c, 3 * c, 3 * c, c, nb, heads, N, N, D, 1.0f, 0, pe ? &dummy : nullptr,
                            pe ? &dummy : nullptr, pe ? const_cast<float*>(&dummy) : nullptr, heads * 32, grid_w, grid_h, dtype, nullptr, 1) == 0;
+}
+
+extern "C" int s2m2_attention_plan(int nb, int heads, int Nq, int Nk, int D, int swap_halves, int grid_w, int grid_h, int dtype,
+                                   s2m2_attn_plan* plan) {
+    // the dry walk of s2m2_attention_supported with Nq, Nk and swap_halves of the caller's; launch_attn_t writes what it would launch
+    static const float dummy = 0.f;
+    S2M2_REQUIRE(plan, "attention_plan: null plan");
+    const bool pe = grid_w > 0 || grid_h > 0;
+    const int c = heads * ((D + 7) / 8 * 8);
+    *plan = s2m2_attn_plan{};
+    s2m2::t_plan_out = plan;
+    const int rc = attention_entry(nullptr, nullptr, nullptr, nullptr, 3 * c, 3 * c, 3 * c, c, nb, heads, Nq, Nk, D, 1.0f, swap_halves,
+                                   pe ? &dummy : nullptr, pe ? &dummy : nullptr, pe ? const_cast<float*>(&dummy) : nullptr, heads * 32, grid_w,
+                                   grid_h, dtype, nullptr, 1);
+    s2m2::t_plan_out = nullptr;
+    return rc;
 }
 
 // recordable entry points of this file (plan.h: the table engine files are loaded through)

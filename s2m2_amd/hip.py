@@ -164,6 +164,11 @@ class EvalDesc(ctypes.Structure):
                 ("occ_min", ctypes.c_float)]
 
 
+class AttnPlan(ctypes.Structure):
+    """mirror of s2m2_attn_plan (include/s2m2_hip.h): the launch K4's planner decides on"""
+    _fields_ = [(n, _i) for n in ("dp", "minw", "ksplit", "nxt", "nyt", "nw", "nblk", "kt", "twopass", "qlds", "deep")] + [("lds_bytes", _ll)]
+
+
 # the stat block of s2m2_disp_eval in 64-bit words (include/s2m2_hip.h: S2M2_EVAL_*): word offsets inside the ALL / KEPT blocks and inside a
 # row of the confidence table, then the offsets of the four blocks
 EVAL_N_REGION, EVAL_N_EVAL, EVAL_N_NONFINITE, EVAL_SUM_ABS_Q, EVAL_SUM_SQ_Q, EVAL_D1_BAD, EVAL_BAD, EVAL_BLOCK_WORDS = 0, 1, 2, 3, 4, 5, 6, 14
@@ -224,6 +229,7 @@ SIGNATURES = {
     "s2m2_attention": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _vp, _vp, _ll,
                             _i, _i, _i, _vp]),
     "s2m2_attention_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "s2m2_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(AttnPlan)]),
     "s2m2_resample2x": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _ll, _i, _i, _vp]),
     "s2m2_image_prep": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "s2m2_refine_prep": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp]),
@@ -1050,6 +1056,16 @@ def attention_supported(nb: int, heads: int, N: int, D: int, dtype: torch.dtype,
     lib = load()
     ok = bool(lib.s2m2_attention_supported(nb, heads, N, D, gw, gh, _DT[dtype]))
     return ok, ("" if ok else lib.s2m2_last_error().decode())
+
+
+def attention_plan(nb: int, heads: int, Nq: int, Nk: int, D: int, dtype: torch.dtype, swap_halves: bool = False,
+                   grid: Optional[Tuple[int, int]] = None) -> dict:
+    """The launch s2m2_attention would make, from its own planner (s2m2_attention_plan; host code, no device needed) -> the fields of
+    s2m2_attn_plan by name.  Raises with the planner's message where it refuses the call."""
+    gw, gh = grid if grid is not None else (0, 0)
+    p = AttnPlan()
+    _check(load().s2m2_attention_plan(nb, heads, Nq, Nk, D, int(swap_halves), gw, gh, _DT[dtype], ctypes.byref(p)), "s2m2_attention_plan")
+    return {n: int(getattr(p, n)) for n, _ in AttnPlan._fields_}
 
 
 def resample2x(x: torch.Tensor, mode: int) -> torch.Tensor:

@@ -209,11 +209,11 @@ WRAPPERS = sorted(_wrapper_calls())
 
 
 def test_the_table_covers_every_launching_wrapper():
-    """every public function of the binding that takes a tensor is in the table above (the *_supported queries, cv_alloc and the
-    workspace-size queries take none)"""
+    """every public function of the binding that takes a tensor is in the table above (the *_supported queries, attention_plan, cv_alloc and
+    the workspace-size queries take none)"""
     import inspect
     public = {n for n, f in vars(hip).items() if inspect.isfunction(f) and f.__module__ == hip.__name__ and not n.startswith("_")}
-    no_tensor = {n for n in public if n.endswith("_supported")} | {"load", "cv_alloc", "cloud_workspace_bytes", "poison_lds"}
+    no_tensor = {n for n in public if n.endswith("_supported")} | {"load", "cv_alloc", "cloud_workspace_bytes", "poison_lds", "attention_plan"}
     assert public - no_tensor == set(WRAPPERS)
 
 
