@@ -1,0 +1,381 @@
+// The host side of s2m2_run_engine (run_engine.cpp): everything that needs no device -- the options, the readers of the files the program is
+// given (calib, camera, PFM, raw), the names and writers of the files it leaves, the evaluation's derived numbers.  Plain C++ over the C header;
+// nothing of HIP, so tools/runner_host_checks.cpp exercises all of it on a machine without a GPU.
+#ifndef S2M2_RUNNER_HOST_H
+#define S2M2_RUNNER_HOST_H
+
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+#include "s2m2_hip.h"
+
+inline const char* const USAGE =
+    "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
+    "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
+    "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]] "
+    "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--thresholds a,b,c] --metrics OUT.json]";
+
+// ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
+struct Options {
+    const char* pos[3] = {nullptr, nullptr, nullptr};    // ENGINE LEFT RIGHT
+    int npos = 0;
+    const char *out_dir = nullptr, *repeat_arg = nullptr;
+    const char *calib_path = nullptr, *image_path = nullptr, *ply_path = nullptr, *depth_path = nullptr, *mesh_path = nullptr;
+    const char *depth_trunc_arg = nullptr, *depth_scale_arg = nullptr, *conf_min_arg = nullptr, *occ_min_arg = nullptr, *unfiltered_arg = nullptr;
+    const char* max_jump_arg = nullptr;
+    const char *register_cam = nullptr, *reg_depth_path = nullptr, *reg_image_path = nullptr, *reg_index_path = nullptr, *splat_arg = nullptr;
+    const char *min_size_arg = nullptr, *labels_path = nullptr, *segmask_path = nullptr;
+    const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr, *gt_min_arg = nullptr;
+
+    int repeat = 0, splat = 2, unfiltered = 0;
+    long long min_size = 1;
+    double max_jump = 1.0;
+    double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5, gt_min = 0.0;
+};
+
+// one row per option; a new option is one row here, one member above and, where it has rules, one line in check_options
+struct OptionRow {
+    const char* name;
+    bool takes_value;                 // false: a flag, stored as its own name
+    const char* Options::*dst;
+};
+
+inline const OptionRow OPTION_TABLE[] = {
+    {"--out", true, &Options::out_dir},
+    {"--repeat", true, &Options::repeat_arg},
+    {"--calib", true, &Options::calib_path},
+    {"--image", true, &Options::image_path},
+    {"--ply", true, &Options::ply_path},
+    {"--mesh", true, &Options::mesh_path},
+    {"--max-jump", true, &Options::max_jump_arg},
+    {"--depth", true, &Options::depth_path},
+    {"--register", true, &Options::register_cam},
+    {"--splat", true, &Options::splat_arg},
+    {"--register-depth", true, &Options::reg_depth_path},
+    {"--register-image", true, &Options::reg_image_path},
+    {"--register-index", true, &Options::reg_index_path},
+    {"--min-size", true, &Options::min_size_arg},
+    {"--labels", true, &Options::labels_path},
+    {"--segment-mask", true, &Options::segmask_path},
+    {"--depth-trunc", true, &Options::depth_trunc_arg},
+    {"--depth-scale", true, &Options::depth_scale_arg},
+    {"--conf-min", true, &Options::conf_min_arg},
+    {"--occ-min", true, &Options::occ_min_arg},
+    {"--unfiltered", false, &Options::unfiltered_arg},
+    {"--gt", true, &Options::gt_path},
+    {"--gt-region", true, &Options::region_path},
+    {"--gt-min", true, &Options::gt_min_arg},
+    {"--thresholds", true, &Options::thr_arg},
+    {"--metrics", true, &Options::metrics_path},
+};
+
+// false: an unknown option, an option without its value or a fourth positional (the caller prints USAGE); a repeated option: the last one
+inline bool parse_options(int argc, char** argv, Options& o) {
+    for (int i = 1; i < argc; ++i) {
+        const OptionRow* row = nullptr;
+        for (const OptionRow& r : OPTION_TABLE)
+            if (strcmp(argv[i], r.name) == 0) row = &r;
+        if (row && !row->takes_value) o.*row->dst = argv[i];
+        else if (row && i + 1 < argc) o.*row->dst = argv[++i];
+        else if (o.npos < 3 && argv[i][0] != '-') o.pos[o.npos++] = argv[i];
+        else return false;
+    }
+    return true;
+}
+
+// the numbers of the options and the rules between options, in the order the messages have always come in; null: the options are complete
+inline const char* check_options(Options& o) {
+    if (o.repeat_arg) o.repeat = atoi(o.repeat_arg);
+    if (o.depth_trunc_arg) o.depth_trunc = atof(o.depth_trunc_arg);
+    if (o.depth_scale_arg) o.depth_scale = atof(o.depth_scale_arg);
+    if (o.conf_min_arg) o.conf_min = atof(o.conf_min_arg);
+    if (o.occ_min_arg) o.occ_min = atof(o.occ_min_arg);
+    if (o.gt_min_arg) o.gt_min = atof(o.gt_min_arg);
+    o.unfiltered = o.unfiltered_arg != nullptr;
+    if (o.npos != 3 || o.repeat < 0) return USAGE;
+    if (o.mesh_path && !o.calib_path) return "--calib and --mesh come together";
+    if (o.register_cam && (!o.calib_path || !o.reg_depth_path)) return "--register needs --calib and --register-depth";
+    if (!o.register_cam && (o.reg_depth_path || o.reg_image_path || o.reg_index_path || o.splat_arg)) return "--splat and --register-* need --register";
+    if (o.splat_arg) {
+        o.splat = atoi(o.splat_arg);
+        if (o.splat < 1 || o.splat > 4) return "--splat: 1, 2, 3 or 4";
+    }
+    if (o.min_size_arg && !o.calib_path) return "--min-size needs --calib";
+    if (!o.min_size_arg && (o.labels_path || o.segmask_path)) return "--labels and --segment-mask need --min-size";
+    if (o.min_size_arg) {
+        char* end = nullptr;
+        o.min_size = strtoll(o.min_size_arg, &end, 10);
+        if (end == o.min_size_arg || *end || o.min_size < 1 || o.min_size > (1LL << 30)) return "--min-size: an integer >= 1 (at most 2^30)";
+    }
+    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && (o.calib_path == nullptr) != (o.ply_path == nullptr)) return "--calib and --ply come together";
+    if ((o.register_cam || o.min_size_arg) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
+    if (o.max_jump_arg && !o.mesh_path && !o.min_size_arg) return "--max-jump needs --mesh or --min-size";
+    if (o.max_jump_arg) {
+        char* end = nullptr;
+        o.max_jump = strtod(o.max_jump_arg, &end);
+        if (end == o.max_jump_arg || *end || !(o.max_jump >= 0.0)) return "--max-jump: a number >= 0 (inf is allowed)";
+    }
+    if (!o.calib_path && (o.image_path || o.depth_path)) return "--image and --depth need --calib and --ply";
+    if ((o.gt_path == nullptr) != (o.metrics_path == nullptr)) return "--gt and --metrics come together";
+    if (!o.gt_path && (o.region_path || o.thr_arg)) return "--gt-region and --thresholds need --gt and --metrics";
+    return nullptr;
+}
+
+// ---- readers
+// a file of exactly `bytes` bytes
+inline bool read_exact(const char* path, void* data, size_t bytes) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    const size_t n = fread(data, 1, bytes, f);
+    const bool at_end = fgetc(f) == EOF;
+    fclose(f);
+    return n == bytes && at_end;
+}
+
+// a raw little-endian float32 file of exactly v.size() values
+inline bool read_raw(const char* path, std::vector<float>& v) { return read_exact(path, v.data(), v.size() * sizeof(float)); }
+
+// a raw uint8 file of exactly v.size() bytes (--image, --gt-region)
+inline bool read_raw_u8(const char* path, std::vector<unsigned char>& v) { return read_exact(path, v.data(), v.size()); }
+
+// cam0=[fx 0 cx; 0 fy cy; 0 0 1], doffs=, baseline= of a Middlebury calib.txt; every other key is ignored
+struct Calib {
+    double fx = 0, fy = 0, cx = 0, cy = 0, doffs = 0, baseline = 0;
+    double cam1[4] = {0, 0, 0, 0};      // fx, fy, cx, cy of cam1 (--register right)
+    bool have_cam0 = false, have_baseline = false, have_cam1 = false;
+};
+
+inline bool read_calib(const char* path, Calib& c) {
+    FILE* f = fopen(path, "r");
+    if (!f) return false;
+    char line[512];
+    while (fgets(line, sizeof line, f)) {
+        double m[9];
+        if (sscanf(line, " cam0 = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            c.fx = m[0]; c.cx = m[2]; c.fy = m[4]; c.cy = m[5];
+            c.have_cam0 = true;
+        } else if (sscanf(line, " cam1 = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            c.cam1[0] = m[0]; c.cam1[1] = m[4]; c.cam1[2] = m[2]; c.cam1[3] = m[5];
+            c.have_cam1 = true;
+        } else if (sscanf(line, " doffs = %lf", m) == 1) c.doffs = m[0];
+        else if (sscanf(line, " baseline = %lf", m) == 1) { c.baseline = m[0]; c.have_baseline = true; }
+    }
+    fclose(f);
+    return c.have_cam0 && c.have_baseline;
+}
+
+// the target camera of --register: a text file in the calib file's syntax (see the head of run_engine.cpp)
+struct TargetCamera {
+    int width = 0, height = 0;
+    double fx = 0, fy = 0, cx = 0, cy = 0;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double t[3] = {0, 0, 0};
+};
+
+inline bool read_camera(const char* path, TargetCamera& c) {
+    FILE* f = fopen(path, "r");
+    if (!f) return false;
+    char line[512];
+    bool have_cam = false;
+    while (fgets(line, sizeof line, f)) {
+        double m[9];
+        if (sscanf(line, " cam = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            c.fx = m[0]; c.cx = m[2]; c.fy = m[4]; c.cy = m[5];
+            have_cam = true;
+        } else if (sscanf(line, " R = [ %lf %lf %lf ; %lf %lf %lf ; %lf %lf %lf", m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8) == 9) {
+            memcpy(c.R, m, sizeof c.R);
+        } else if (sscanf(line, " t = [ %lf %lf %lf", m, m + 1, m + 2) == 3) {
+            memcpy(c.t, m, sizeof c.t);
+        } else if (sscanf(line, " width = %lf", m) == 1) c.width = (int)m[0];
+        else if (sscanf(line, " height = %lf", m) == 1) c.height = (int)m[0];
+    }
+    fclose(f);
+    return have_cam && c.width > 0 && c.height > 0;
+}
+
+// greyscale PFM: "Pf", "width height", "scale" (negative: little-endian), then the rows bottom to top -> rows top to bottom
+inline bool read_pfm(const char* path, std::vector<float>& v, int& width, int& height, const char*& why) {
+    FILE* f = fopen(path, "rb");
+    why = "cannot open the file";
+    if (!f) return false;
+    char magic[3] = {0, 0, 0};
+    double scale = 0.0;
+    bool ok = false;
+    why = "not a greyscale PFM (header Pf, width height, scale)";
+    if (fscanf(f, "%2s %d %d %lf", magic, &width, &height, &scale) == 4 && strcmp(magic, "Pf") == 0 && fgetc(f) == '\n' && width > 0 &&
+        height > 0 && (long long)width * height < (1LL << 31) && scale != 0.0 && scale == scale) {
+        why = "the data is not width * height float32 values";
+        v.resize((size_t)width * height);
+        ok = true;
+        for (int y = height - 1; y >= 0 && ok; --y) ok = fread(v.data() + (size_t)y * width, sizeof(float), width, f) == (size_t)width;
+        ok = ok && fgetc(f) == EOF;
+        if (ok && scale > 0.0) {                                     // big-endian
+            unsigned char* p = reinterpret_cast<unsigned char*>(v.data());
+            for (size_t i = 0; i < v.size(); ++i, p += 4) {
+                const unsigned char a = p[0], b = p[1];
+                p[0] = p[3]; p[1] = p[2]; p[2] = b; p[3] = a;
+            }
+        }
+    }
+    fclose(f);
+    return ok;
+}
+
+// --thresholds a,b,c: up to S2M2_EVAL_MAX_THR finite numbers > 0, strictly increasing (a trailing comma passes; "": no threshold)
+inline bool parse_thresholds(const char* arg, float* thr, int& nthr) {
+    nthr = 0;
+    for (const char* c = arg; *c;) {
+        char* end = nullptr;
+        const float t = strtof(c, &end);
+        if (end == c || nthr == S2M2_EVAL_MAX_THR || !(t > (nthr ? thr[nthr - 1] : 0.f)) || !isfinite(t) || (*end && *end != ',')) return false;
+        thr[nthr++] = t;
+        c = *end ? end + 1 : end;
+    }
+    return true;
+}
+
+// what --gt, --gt-region, --thresholds and --gt-min give the evaluation stage
+struct GroundTruth {
+    std::vector<float> gt;                   // w x rows: the B ground truths stacked
+    std::vector<unsigned char> region;
+    int w = 0, rows = 0, nthr = 4;
+    float thr[S2M2_EVAL_MAX_THR] = {0.5f, 1.f, 2.f, 4.f, 0.f, 0.f, 0.f, 0.f};
+};
+
+// parsed and validated before the engine is loaded and anything touches the device; "": fine (also without --gt), else the message
+inline std::string read_ground_truth(const Options& o, GroundTruth& g) {
+    if (!o.gt_path) return "";
+    const char* why = "";
+    if (!read_pfm(o.gt_path, g.gt, g.w, g.rows, why)) return std::string("--gt ") + o.gt_path + ": " + why;
+    if (o.region_path) {
+        g.region.resize(g.gt.size());
+        if (!read_raw_u8(o.region_path, g.region))
+            return "--gt-region must be a raw uint8 file of the ground truth's " + std::to_string(g.w) + " x " + std::to_string(g.rows) + " pixels";
+    }
+    if (o.thr_arg && !parse_thresholds(o.thr_arg, g.thr, g.nthr)) return "--thresholds: up to 8 numbers > 0, strictly increasing, separated by commas";
+    if (o.gt_min != o.gt_min) return "--gt-min: not a number";
+    return "";
+}
+
+// ---- the input half of s2m2_cloud_desc, shared by K15 / K20, K21 and K22: maps, image, extents, camera and filter numbers.  `unfiltered` is
+// the option's, or 1 behind K22 (the filter is in the map then)
+inline void fill_cloud_inputs(s2m2_cloud_desc& cd, const s2m2_engine_info& m, const float* disp, const float* occ, const float* conf,
+                              const void* image, int image_dtype, int unfiltered, const Calib& cal, const Options& o) {
+    cd.disp = disp; cd.occ = occ; cd.conf = conf;
+    cd.image = image;
+    cd.image_dtype = image_dtype;
+    cd.B = m.B; cd.H = m.H; cd.W = m.W; cd.Hp = m.out_h; cd.Wp = m.out_w;
+    cd.unfiltered = unfiltered;
+    cd.fx = cal.fx; cd.fy = cal.fy; cd.cx = cal.cx; cd.cy = cal.cy; cd.baseline = cal.baseline; cd.doffs = cal.doffs;
+    cd.depth_scale = o.depth_scale; cd.depth_trunc = o.depth_trunc; cd.conf_min = o.conf_min; cd.occ_min = o.occ_min;
+}
+
+// ---- writers
+// OUT.ply, or OUT.<b>.ply for engines of more than one pair (a trailing ".ply" of OUT is dropped first); --register-image: ".ppm"
+inline std::string pair_path(const char* out, int B, int b, const char* ext = ".ply") {
+    std::string stem = out;
+    if (B <= 1) return stem;
+    const size_t ne = strlen(ext);
+    if (stem.size() > ne && stem.compare(stem.size() - ne, ne, ext) == 0) stem.resize(stem.size() - ne);
+    return stem + "." + std::to_string(b) + ext;
+}
+
+inline bool write_bytes(const std::string& path, const char* head, const void* data, size_t n) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(head, 1, strlen(head), f) == strlen(head) && fwrite(data, 1, n, f) == n;
+    return fclose(f) == 0 && ok;
+}
+
+inline bool write_ply(const std::string& path, const void* records, long long n) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nend_header\n", n);
+    const bool ok = fwrite(records, 16, (size_t)n, f) == (size_t)n;
+    return fclose(f) == 0 && ok;
+}
+
+// the same vertices, then every face as a count byte (3) and three little-endian int32 vertex indices: 13 bytes
+inline bool write_ply_mesh(const std::string& path, const void* records, long long n, const int32_t* faces, long long nf) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face %lld\n"
+               "property list uchar int vertex_indices\nend_header\n", n, nf);
+    std::vector<unsigned char> disk((size_t)nf * 13);
+    for (long long i = 0; i < nf; ++i) {
+        disk[(size_t)i * 13] = 3;
+        memcpy(&disk[(size_t)i * 13 + 1], faces + i * 3, 12);
+    }
+    const bool ok = fwrite(records, 16, (size_t)n, f) == (size_t)n && fwrite(disk.data(), 13, (size_t)nf, f) == (size_t)nf;
+    return fclose(f) == 0 && ok;
+}
+
+inline void json_number(FILE* f, const char* key, double x, const char* tail) {
+    if (isfinite(x)) fprintf(f, "\"%s\": %.17g%s", key, x, tail);
+    else fprintf(f, "\"%s\": null%s", key, tail);
+}
+
+// the derived numbers of one ALL / KEPT block (s2m2_amd/evaluate.py: EvalStats, the same arithmetic in double)
+inline void json_block(FILE* f, const unsigned long long* blk, const float* thr, int nthr) {
+    const double n = (double)blk[S2M2_EVAL_N_EVAL], fin = (double)(blk[S2M2_EVAL_N_EVAL] - blk[S2M2_EVAL_N_NONFINITE]);
+    fprintf(f, "\"n_region\": %llu, \"n_eval\": %llu, \"nonfinite\": %llu, ", blk[S2M2_EVAL_N_REGION], blk[S2M2_EVAL_N_EVAL], blk[S2M2_EVAL_N_NONFINITE]);
+    json_number(f, "epe", (double)blk[S2M2_EVAL_SUM_ABS_Q] / 65536.0 / fin, ", ");
+    json_number(f, "rmse", sqrt((double)blk[S2M2_EVAL_SUM_SQ_Q] / 4096.0 / fin), ", ");
+    for (int t = 0; t < nthr; ++t) {
+        char key[32];
+        snprintf(key, sizeof key, "bad_%g", (double)thr[t]);
+        json_number(f, key, (double)blk[S2M2_EVAL_BAD + t] / n, ", ");
+    }
+    json_number(f, "d1", (double)blk[S2M2_EVAL_D1_BAD] / n, "");
+}
+
+// upper edge in px of the histogram bin where the cumulative count first reaches p * n; inf for the overflow bin, NaN without pixels
+inline double eval_quantile(const unsigned long long* hist, double p) {
+    unsigned long long n = 0, cum = 0;
+    for (int i = 0; i < S2M2_EVAL_HIST_BINS; ++i) n += hist[i];
+    if (n == 0) return NAN;
+    for (int i = 0; i < S2M2_EVAL_HIST_BINS; ++i) {
+        cum += hist[i];
+        if ((double)cum >= p * (double)n) return i == S2M2_EVAL_HIST_BINS - 1 ? INFINITY : (double)(i + 1) / 64.0;
+    }
+    return INFINITY;
+}
+
+// --metrics: `words` = the B stat blocks of s2m2_disp_eval for ground truths of gt_h x g.w pixels
+inline bool write_metrics(const char* path, int B, int gt_h, const GroundTruth& g, const Options& o, const unsigned long long* words) {
+    FILE* f = fopen(path, "w");
+    if (!f) return false;
+    fprintf(f, "{\"B\": %d, \"H\": %d, \"W\": %d, \"gt_min\": ", B, gt_h, g.w);
+    if (isfinite(o.gt_min)) fprintf(f, "%.9g", o.gt_min);
+    else fprintf(f, "null");
+    fprintf(f, ", \"conf_min\": %.9g, \"occ_min\": %.9g, \"thresholds\": [", o.conf_min, o.occ_min);
+    for (int t = 0; t < g.nthr; ++t) fprintf(f, "%s%.9g", t ? ", " : "", (double)g.thr[t]);
+    fprintf(f, "],\n \"pairs\": [");
+    for (int b = 0; b < B; ++b) {
+        const unsigned long long* w = words + (size_t)b * S2M2_EVAL_WORDS;
+        fprintf(f, "%s\n  {", b ? "," : "");
+        json_block(f, w + S2M2_EVAL_ALL, g.thr, g.nthr);
+        fprintf(f, ", ");
+        json_number(f, "a50", eval_quantile(w + S2M2_EVAL_HIST, 0.5), ", ");
+        json_number(f, "a90", eval_quantile(w + S2M2_EVAL_HIST, 0.9), ", ");
+        json_number(f, "a95", eval_quantile(w + S2M2_EVAL_HIST, 0.95), ", ");
+        json_number(f, "a99", eval_quantile(w + S2M2_EVAL_HIST, 0.99), ", ");
+        json_number(f, "density", (double)w[S2M2_EVAL_KEPT + S2M2_EVAL_N_EVAL] / (double)w[S2M2_EVAL_ALL + S2M2_EVAL_N_EVAL], ",\n   ");
+        fprintf(f, "\"kept\": {");
+        json_block(f, w + S2M2_EVAL_KEPT, g.thr, g.nthr);
+        fprintf(f, "},\n   \"words\": [");
+        for (int i = 0; i < S2M2_EVAL_WORDS; ++i) fprintf(f, "%s%llu", i ? ", " : "", w[i]);
+        fprintf(f, "]}");
+    }
+    fprintf(f, "\n ]}\n");
+    return fclose(f) == 0;
+}
+
+#endif  // S2M2_RUNNER_HOST_H

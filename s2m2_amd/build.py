@@ -121,13 +121,14 @@ def build(force: bool = False, verbose: bool = True, extra_defines=()) -> str:
 
 
 RUNNER_SRC = os.path.join(HERE, "app", "run_engine.cpp")
+RUNNER_HOST = os.path.join(HERE, "app", "runner_host.h")            # the runner's host-only half, included by RUNNER_SRC
 RUNNER = os.path.join(LIBDIR, "s2m2_run_engine")
 
 
 def build_runner(force: bool = False, verbose: bool = True) -> str:
     """lib/s2m2_run_engine: host code only, linked against lib/libs2m2_hip.so (rpath $ORIGIN) and the HIP runtime (rpath: ROCm's lib)"""
     include = os.path.join(os.path.dirname(HERE), "include")
-    newest = max(os.path.getmtime(RUNNER_SRC), os.path.getmtime(LIB), os.path.getmtime(os.path.join(include, "s2m2_hip.h")))
+    newest = max(os.path.getmtime(p) for p in (RUNNER_SRC, RUNNER_HOST, LIB, os.path.join(include, "s2m2_hip.h")))
     if force or not os.path.exists(RUNNER) or os.path.getmtime(RUNNER) < newest:
         rocm_lib = os.path.join(os.path.dirname(os.path.dirname(HIPCC)), "lib")
         cmd = [HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wall", "-I", include, RUNNER_SRC, "-o", RUNNER, "-L", LIBDIR,

@@ -149,6 +149,13 @@ class PointCloud:
         return write_ply_records(path, self.records[b, :self.size(b)].cpu().numpy())
 
 
+def _binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered) -> Dict[str, object]:
+    """``reproject``'s conventions -> the camera and filter keywords of the binding (hip.cloud, hip.mesh, hip.register, hip.segment): fy
+    defaults to fx and depth_trunc None is 1e9, both as in the reference; filtered becomes unfiltered; the rest passes through."""
+    return dict(fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs, depth_scale=depth_scale,
+                depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min, unfiltered=not filtered)
+
+
 def reproject(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, cx: float, cy: float,
               baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
               depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True,
@@ -168,9 +175,8 @@ def reproject(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: 
     workspace = torch.empty((hip.cloud_workspace_bytes(B, H, W),), device=dev, dtype=torch.uint8)
     depth = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if want_depth else None
     mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.uint8) if want_mask else None
-    hip.cloud(disp, occ, conf, image, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs,
-              depth_scale=depth_scale, depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min,
-              unfiltered=not filtered, records=records, count=count, workspace=workspace, depth=depth, mask=mask)
+    hip.cloud(disp, occ, conf, image, **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
+              records=records, count=count, workspace=workspace, depth=depth, mask=mask)
     return PointCloud(records, count, depth, mask)
 
 
@@ -227,8 +233,7 @@ def mesh(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch
     index = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_index else None
     depth = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32) if want_depth else None
     mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.uint8) if want_mask else None
-    hip.mesh(disp, occ, conf, image, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs, depth_scale=depth_scale,
-             depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min, unfiltered=not filtered,
+    hip.mesh(disp, occ, conf, image, **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
              max_jump=max_jump, records=records, count=count, faces=faces, face_count=face_count, workspace=workspace, index=index, depth=depth,
              mask=mask)
     return Mesh(records, count, faces, face_count, index, depth, mask)
@@ -289,8 +294,7 @@ def register(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: t
     visible = torch.empty((B, 1, H, W), device=dev, dtype=torch.uint8) if want_visible else None
     count = torch.empty((B,), device=dev, dtype=torch.int32) if want_count else None
     workspace = torch.empty((hip.register_workspace_bytes(B, Ht, Wt),), device=dev, dtype=torch.uint8)
-    hip.register(disp, occ, conf, image, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs, depth_scale=depth_scale,
-                 depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min, unfiltered=not filtered,
+    hip.register(disp, occ, conf, image, **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
                  Ht=Ht, Wt=Wt, splat=splat, fx_t=to.fx, fy_t=to.fy, cx_t=to.cx, cy_t=to.cy, R=to.R.ravel().tolist(), t=to.t.tolist(),
                  workspace=workspace, depth_t=depth, index_t=index, image_t=image_t, visible=visible, count=count)
     return Registered(depth, index, image_t, visible, count)
@@ -340,8 +344,7 @@ def segment(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: int
     size = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_size else None
     stats = torch.empty((B, 4), device=dev, dtype=torch.int32)
     workspace = torch.empty((hip.segment_workspace_bytes(B, H, W),), device=dev, dtype=torch.uint8)
-    hip.segment(disp, occ, conf, H=H, W=W, fx=fx, fy=fx if fy is None else fy, cx=cx, cy=cy, baseline=baseline, doffs=doffs,
-                depth_scale=depth_scale, depth_trunc=1e9 if depth_trunc is None else depth_trunc, conf_min=conf_min, occ_min=occ_min,
-                unfiltered=not filtered, max_jump=max_jump, min_size=min_size, workspace=workspace, label=label, size=size, mask=mask,
+    hip.segment(disp, occ, conf, H=H, W=W, **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
+                max_jump=max_jump, min_size=min_size, workspace=workspace, label=label, size=size, mask=mask,
                 disp_out=out, stats=stats)
     return Segments(out, mask, label, size, stats)

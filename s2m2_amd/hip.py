@@ -1198,26 +1198,54 @@ def image_pad(img: torch.Tensor, factor: int = 32) -> torch.Tensor:
     return out
 
 
-def _cloud_desc(what: str, d: CloudDesc, need, disp, occ, conf, image, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min,
-                occ_min, unfiltered, records, count, workspace, depth, mask) -> None:
-    """fills ``d`` for s2m2_cloud / s2m2_mesh from validated operands; ``need(B, H, W)``: the workspace bytes that ``count`` requires (asked
-    behind the shape checks, as ever)"""
+def _opt(t: Optional[torch.Tensor], shape, dtype: torch.dtype, what: str):
+    """an optional output: None -> NULL; a contiguous tensor of exactly this shape and dtype (_mat) -> its pointer"""
+    if t is None:
+        return None
+    _mat(t, shape, dtype, what)
+    return t.data_ptr()
+
+
+def _extent_query(symbol: str, stage: str, **extents: int) -> int:
+    """the extent queries of the output stages (workspace bytes, tile rows / columns): the library answers 0 for extents it refuses"""
+    n = int(getattr(load(), symbol)(*extents.values()))
+    if n == 0:
+        raise ValueError(f"{stage}: bad extents " + " ".join(f"{k}={v}" for k, v in extents.items()))
+    return n
+
+
+def _cloud_inputs(what: str, d: CloudDesc, disp, occ, conf, image, H, W, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min,
+                  occ_min, unfiltered) -> Tuple[int, int, int]:
+    """the input half of ``d``, which s2m2_cloud, s2m2_mesh, s2m2_register and s2m2_segment all take: the three maps, the image (or, with
+    ``image`` None, the extents ``H`` x ``W`` of the fused crop), the camera and filter numbers -> (B, H, W)"""
     if disp.dtype != torch.float32 or occ.dtype != torch.float32 or conf.dtype != torch.float32 or disp.dim() != 4 or disp.shape[1] != 1:
         raise ValueError(f"{what}: disp / occ / conf must be (B,1,Hp,Wp) fp32 tensors")
     if occ.shape != disp.shape or conf.shape != disp.shape:
         raise ValueError(f"{what}: disp, occ and conf must have one shape")
-    if image.dtype not in _IMG_DT or image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != disp.shape[0]:
-        raise ValueError(f"{what}: image must be a (B,3,H,W) uint8 / fp16 / fp32 tensor")
     B, _, Hp, Wp = disp.shape
-    H, W = image.shape[-2:]
-    d.disp, d.occ, d.conf, d.image = disp.data_ptr(), occ.data_ptr(), conf.data_ptr(), image.data_ptr()
-    d.B, d.H, d.W, d.Hp, d.Wp, d.image_dtype, d.unfiltered = B, H, W, Hp, Wp, _IMG_DT[image.dtype], int(unfiltered)
-    if depth is not None:
-        _mat(depth, (B, 1, H, W), torch.float32, f"{what}: depth")
-        d.depth = depth.data_ptr()
-    if mask is not None:
-        _mat(mask, (B, 1, H, W), torch.uint8, f"{what}: mask")
-        d.mask = mask.data_ptr()
+    if image is not None:
+        if image.dtype not in _IMG_DT or image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != B:
+            raise ValueError(f"{what}: image must be a (B,3,H,W) uint8 / fp16 / fp32 tensor")
+        if (H is not None and H != image.shape[2]) or (W is not None and W != image.shape[3]):
+            raise ValueError(f"{what}: H and W differ from the image")
+        H, W = image.shape[-2:]
+        d.image, d.image_dtype = image.data_ptr(), _IMG_DT[image.dtype]
+    elif H is None or W is None:
+        raise ValueError(f"{what}: without an image, H and W are required")
+    else:
+        d.image_dtype = _IMG_DT[torch.uint8]
+    d.disp, d.occ, d.conf = disp.data_ptr(), occ.data_ptr(), conf.data_ptr()
+    d.B, d.H, d.W, d.Hp, d.Wp, d.unfiltered = B, H, W, Hp, Wp, int(unfiltered)
+    d.fx, d.fy, d.cx, d.cy, d.baseline, d.doffs = fx, fy, cx, cy, baseline, doffs
+    d.depth_scale, d.depth_trunc, d.conf_min, d.occ_min = depth_scale, depth_trunc, conf_min, occ_min
+    return B, H, W
+
+
+def _cloud_outputs(what: str, d: CloudDesc, need, records, count, workspace, depth, mask) -> None:
+    """K15's outputs in ``d`` (s2m2_cloud, s2m2_mesh), behind _cloud_inputs; ``need(B, H, W)``: the workspace bytes that ``count`` requires"""
+    B, H, W = d.B, d.H, d.W
+    d.depth = _opt(depth, (B, 1, H, W), torch.float32, f"{what}: depth")
+    d.mask = _opt(mask, (B, 1, H, W), torch.uint8, f"{what}: mask")
     if count is not None:
         _vec(count, B, f"{what}: count", dtype=torch.int32)
         need = need(B, H, W)
@@ -1231,8 +1259,6 @@ def _cloud_desc(what: str, d: CloudDesc, need, disp, occ, conf, image, fx, fy, c
             d.records = records.data_ptr() if records.shape[1] > 0 else None
     elif records is not None:
         raise ValueError(f"{what}: records come with count")
-    d.fx, d.fy, d.cx, d.cy, d.baseline, d.doffs = fx, fy, cx, cy, baseline, doffs
-    d.depth_scale, d.depth_trunc, d.conf_min, d.occ_min = depth_scale, depth_trunc, conf_min, occ_min
 
 
 def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, fy: float, cx: float, cy: float,
@@ -1245,17 +1271,14 @@ def cloud(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torc
     _resident("cloud", disp, occ, conf, image, records, count, workspace, depth, mask)
     _contig("cloud", disp, occ, conf, image, records, count, workspace, depth, mask)
     d = CloudDesc()
-    _cloud_desc("cloud", d, cloud_workspace_bytes, disp, occ, conf, image, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min,
-                unfiltered, records, count, workspace, depth, mask)
+    _cloud_inputs("cloud", d, disp, occ, conf, image, None, None, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, unfiltered)
+    _cloud_outputs("cloud", d, cloud_workspace_bytes, records, count, workspace, depth, mask)
     with torch.cuda.device(disp.device):
         _check(load().s2m2_cloud(ctypes.byref(d), _stream()), "s2m2_cloud")
 
 
 def cloud_workspace_bytes(B: int, H: int, W: int) -> int:
-    n = int(load().s2m2_cloud_workspace_bytes(B, H, W))
-    if n == 0:
-        raise ValueError(f"cloud: bad extents B={B} H={H} W={W}")
-    return n
+    return _extent_query("s2m2_cloud_workspace_bytes", "cloud", B=B, H=H, W=W)
 
 
 def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, maps: Optional[torch.Tensor] = None, *, hd: Optional[int] = None,
@@ -1292,9 +1315,7 @@ def rectify(srcs, records: torch.Tensor, out: Optional[torch.Tensor] = None, map
         _mat(out, (n, 3, Hd, Wd), out.dtype, "rectify: out")
         d.out, d.out_dtype = out.data_ptr(), _IMG_DT[out.dtype]
         d.src[0], d.src[1] = srcs[0].data_ptr(), srcs[-1].data_ptr()
-    if maps is not None:
-        _mat(maps, (n, 2, Hd, Wd), torch.float32, "rectify: maps")
-        d.maps = maps.data_ptr()
+    d.maps = _opt(maps, (n, 2, Hd, Wd), torch.float32, "rectify: maps")
     d.records, d.n_src, d.n_img, d.Hs, d.Ws, d.Hd, d.Wd = records.data_ptr(), len(srcs), n, Hs, Ws, Hd, Wd
     d.src_format, d.round, d.order = fmt, int(bool(round)), order
     with torch.cuda.device(records.device):

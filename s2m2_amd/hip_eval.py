@@ -10,18 +10,12 @@ from . import hip as _h
 
 
 def eval_workspace_bytes(B: int, H: int, W: int) -> int:
-    n = int(_h.load().s2m2_eval_workspace_bytes(B, H, W))
-    if n == 0:
-        raise ValueError(f"disp_eval: bad extents B={B} H={H} W={W}")
-    return n
+    return _h._extent_query("s2m2_eval_workspace_bytes", "disp_eval", B=B, H=H, W=W)
 
 
 def eval_tile_rows(H: int, W: int) -> int:
     """image rows of one tile of K18's first launch (a pair of H rows is ceil(H / rows) partial blocks in the workspace)"""
-    n = int(_h.load().s2m2_eval_tile_rows(H, W))
-    if n == 0:
-        raise ValueError(f"disp_eval: bad extents H={H} W={W}")
-    return n
+    return _h._extent_query("s2m2_eval_tile_rows", "disp_eval", H=H, W=W)
 
 
 def disp_eval(disp: torch.Tensor, gt: torch.Tensor, stats: torch.Tensor, workspace: torch.Tensor, *, region: Optional[torch.Tensor] = None,
@@ -40,20 +34,17 @@ def disp_eval(disp: torch.Tensor, gt: torch.Tensor, stats: torch.Tensor, workspa
     H, W = gt.shape[-2:]
     _h._mat(gt, (B, 1, H, W), torch.float32, "disp_eval: gt")
     _h._mat(stats, (B, _h.EVAL_WORDS), torch.int64, "disp_eval: stats")
-    for name, t in (("occ", occ), ("conf", conf)):
-        if t is not None:
-            _h._mat(t, (B, 1, Hp, Wp), torch.float32, f"disp_eval: {name}")
-    if region is not None:
-        _h._mat(region, (B, 1, H, W), torch.uint8, "disp_eval: region")
+    d = _h.EvalDesc()
+    d.occ = _h._opt(occ, (B, 1, Hp, Wp), torch.float32, "disp_eval: occ")
+    d.conf = _h._opt(conf, (B, 1, Hp, Wp), torch.float32, "disp_eval: conf")
+    d.region = _h._opt(region, (B, 1, H, W), torch.uint8, "disp_eval: region")
     thresholds = tuple(float(t) for t in thresholds)
     if len(thresholds) > _h.EVAL_MAX_THR:
         raise ValueError(f"disp_eval: at most {_h.EVAL_MAX_THR} thresholds, got {len(thresholds)}")
     need = eval_workspace_bytes(B, H, W)
     if workspace.nbytes < need:
         raise ValueError(f"disp_eval: a workspace of {need} bytes is required, got {workspace.nbytes}")
-    d = _h.EvalDesc()
-    d.disp, d.occ, d.conf, d.gt, d.region = disp.data_ptr(), _h._ptr(occ), _h._ptr(conf), gt.data_ptr(), _h._ptr(region)
-    d.workspace, d.stats = workspace.data_ptr(), stats.data_ptr()
+    d.disp, d.gt, d.workspace, d.stats = disp.data_ptr(), gt.data_ptr(), workspace.data_ptr(), stats.data_ptr()
     d.B, d.H, d.W, d.Hp, d.Wp, d.nthr = B, H, W, Hp, Wp, len(thresholds)
     for i, t in enumerate(thresholds):
         d.thr[i] = t

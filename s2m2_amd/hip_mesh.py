@@ -21,32 +21,24 @@ def mesh(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch
     if records is None or count is None or faces is None or face_count is None:
         raise ValueError("mesh: records, count, faces and face_count are required")
     d = _h.MeshDesc()
-    _h._cloud_desc("mesh", d.cloud, mesh_workspace_bytes, disp, occ, conf, image, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min,
-                unfiltered, records, count, workspace, depth, mask)
-    B, H, W = d.cloud.B, d.cloud.H, d.cloud.W
+    B, H, W = _h._cloud_inputs("mesh", d.cloud, disp, occ, conf, image, None, None, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min,
+                               occ_min, unfiltered)
+    _h._cloud_outputs("mesh", d.cloud, mesh_workspace_bytes, records, count, workspace, depth, mask)
     _h._vec(face_count, B, "mesh: face_count", dtype=torch.int32)
     if faces.dtype != torch.int32 or faces.dim() != 3 or faces.shape[0] != B or faces.shape[2] != 3:
         raise ValueError("mesh: faces must be a (B, face_capacity, 3) int32 tensor")
     d.face_count, d.face_capacity = face_count.data_ptr(), faces.shape[1]
     d.faces = faces.data_ptr() if faces.shape[1] > 0 else None
-    if index is not None:
-        _h._mat(index, (B, 1, H, W), torch.int32, "mesh: index")
-        d.index = index.data_ptr()
+    d.index = _h._opt(index, (B, 1, H, W), torch.int32, "mesh: index")
     d.max_jump = max_jump
     with torch.cuda.device(disp.device):
         _h._check(_h.load().s2m2_mesh(ctypes.byref(d), _h._stream()), "s2m2_mesh")
 
 
 def mesh_workspace_bytes(B: int, H: int, W: int) -> int:
-    n = int(_h.load().s2m2_mesh_workspace_bytes(B, H, W))
-    if n == 0:
-        raise ValueError(f"mesh: bad extents B={B} H={H} W={W}")
-    return n
+    return _h._extent_query("s2m2_mesh_workspace_bytes", "mesh", B=B, H=H, W=W)
 
 
 def mesh_tile_rows(H: int, W: int) -> int:
     """image rows of one tile of s2m2_mesh's launches (tests sit on the tile boundaries)"""
-    n = int(_h.load().s2m2_mesh_tile_rows(H, W))
-    if n == 0:
-        raise ValueError(f"mesh: bad extents H={H} W={W}")
-    return n
+    return _h._extent_query("s2m2_mesh_tile_rows", "mesh", H=H, W=W)

@@ -24,33 +24,15 @@ def segment(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: int
         raise ValueError(f"segment: min_size must be an integer in 1..2^30, got {min_size}")
     _h._resident("segment", disp, occ, conf, workspace, label, size, mask, disp_out, stats)
     _h._contig("segment", disp, occ, conf, workspace, label, size, mask, disp_out, stats)
-    if disp.dtype != torch.float32 or occ.dtype != torch.float32 or conf.dtype != torch.float32 or disp.dim() != 4 or disp.shape[1] != 1:
-        raise ValueError("segment: disp / occ / conf must be (B,1,Hp,Wp) fp32 tensors")
-    if occ.shape != disp.shape or conf.shape != disp.shape:
-        raise ValueError("segment: disp, occ and conf must have one shape")
-    B, _, Hp, Wp = disp.shape
     d = _h.SegmentDesc()
-    c = d.cloud
-    c.disp, c.occ, c.conf = disp.data_ptr(), occ.data_ptr(), conf.data_ptr()
-    c.B, c.H, c.W, c.Hp, c.Wp, c.unfiltered, c.image_dtype = B, H, W, Hp, Wp, int(unfiltered), _h._IMG_DT[torch.uint8]
-    c.fx, c.fy, c.cx, c.cy, c.baseline, c.doffs = fx, fy, cx, cy, baseline, doffs
-    c.depth_scale, c.depth_trunc, c.conf_min, c.occ_min = depth_scale, depth_trunc, conf_min, occ_min
+    B, H, W = _h._cloud_inputs("segment", d.cloud, disp, occ, conf, None, H, W, fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min,
+                               occ_min, unfiltered)
     d.max_jump, d.min_size = float(max_jump), int(min_size)
-    if label is not None:
-        _h._mat(label, (B, 1, H, W), torch.int32, "segment: label")
-        d.label = label.data_ptr()
-    if size is not None:
-        _h._mat(size, (B, 1, H, W), torch.int32, "segment: size")
-        d.size = size.data_ptr()
-    if mask is not None:
-        _h._mat(mask, (B, 1, H, W), torch.uint8, "segment: mask")
-        d.mask = mask.data_ptr()
-    if disp_out is not None:
-        _h._mat(disp_out, (B, 1, Hp, Wp), torch.float32, "segment: disp_out")
-        d.disp_out = disp_out.data_ptr()
-    if stats is not None:
-        _h._mat(stats, (B, 4), torch.int32, "segment: stats")
-        d.stats = stats.data_ptr()
+    d.label = _h._opt(label, (B, 1, H, W), torch.int32, "segment: label")
+    d.size = _h._opt(size, (B, 1, H, W), torch.int32, "segment: size")
+    d.mask = _h._opt(mask, (B, 1, H, W), torch.uint8, "segment: mask")
+    d.disp_out = _h._opt(disp_out, (B, 1, d.cloud.Hp, d.cloud.Wp), torch.float32, "segment: disp_out")
+    d.stats = _h._opt(stats, (B, 4), torch.int32, "segment: stats")
     need = segment_workspace_bytes(B, H, W)
     if workspace is None or workspace.nbytes < need:
         raise ValueError(f"segment: a workspace of {need} bytes is required")
@@ -60,16 +42,9 @@ def segment(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: int
 
 
 def segment_workspace_bytes(B: int, H: int, W: int) -> int:
-    n = int(_h.load().s2m2_segment_workspace_bytes(B, H, W))
-    if n == 0:
-        raise ValueError(f"segment: bad extents B={B} H={H} W={W}")
-    return n
+    return _h._extent_query("s2m2_segment_workspace_bytes", "segment", B=B, H=H, W=W)
 
 
 def segment_tile(H: int, W: int) -> Tuple[int, int]:
     """(rows, columns) of the tile of K22's local pass at this image size"""
-    lib = _h.load()
-    tr, tc = int(lib.s2m2_segment_tile_rows(H, W)), int(lib.s2m2_segment_tile_cols(H, W))
-    if tr == 0 or tc == 0:
-        raise ValueError(f"segment: bad extents H={H} W={W}")
-    return tr, tc
+    return _h._extent_query("s2m2_segment_tile_rows", "segment", H=H, W=W), _h._extent_query("s2m2_segment_tile_cols", "segment", H=H, W=W)

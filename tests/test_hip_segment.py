@@ -6,6 +6,7 @@ integer sums, so nothing depends on the order in which the atomics arrive.
 The shapes are built from the tile of the local pass (``hip.segment_tile``): TR x TC.  Most scenes run at (2 TR + 3) x (3 TC + 5) inside padded
 maps with odd crop offsets, so that tile borders (which the crop offset shifts by ``ox & 3`` columns) cut every structure."""
 import functools
+import json
 import os
 import subprocess
 
@@ -471,6 +472,12 @@ def test_runner_filters_in_front_of_the_3d_outputs(hip, tmp_path):
     a, stdout = run("a", common + ["--min-size", "2", "--ply", str(tmp_path / "a.ply"), "--mesh", str(tmp_path / "a_mesh.ply"),
                                    "--labels", str(tmp_path / "a.i32"), "--segment-mask", str(tmp_path / "a.u8"), "--repeat", "2"])
     assert "segment_us_per_pair" in stdout and "segment_components" in stdout
+    # --repeat: one JSON line per timed stage, in the order forward, segment, mesh, cloud, each with exactly its keys
+    assert [set(json.loads(line)) for line in stdout.splitlines()] == [
+        {"B", "H", "W", "repeat", "ms_per_pair"},
+        {"segment_kept", "segment_components", "segment_surviving", "repeat", "segment_us_per_pair"},
+        {"mesh_vertices", "mesh_faces", "repeat", "mesh_us_per_pair"},
+        {"cloud_points", "repeat", "cloud_us_per_pair"}], stdout
     maps = maps_of(a)
     kw = dict(depth_trunc=3.0, conf_min=0.02, **k)
     s = cloud.segment(*maps, H=H, W=W, max_jump=INF, min_size=2, **kw)
