@@ -73,7 +73,10 @@ const char* s2m2_ln_corr_kernel_name(int C, int feat_dtype, int cv_dtype);
  *           s2m2_cv_lookup read the same pitch
  *   band    -1: the full volume.  >= 0 (use_positivity models): only columns j <= i + band are written (rounded up to the
  *           64-column store granule), the rest of the buffer is left untouched -- nothing downstream reads beyond band = 11: the Sinkhorn
- *           mask removes j > i (submodules.py:211-214), the +-4 tap lookups at both pyramid levels reach column i + 11 (submodules.py:39-60)
+ *           mask removes j > i (submodules.py:211-214), the +-4 tap lookups at both pyramid levels reach column i + 11 (submodules.py:39-60).
+ *           The lookup of pixel i can also read ROW i - 1 at that column (the fp32 coordinate round trip lands just below i, weight ~1e-6):
+ *           per row r the read set is j <= r + 12.  Row r + 12 > (r | 31) + 11 only where r % 32 == 31, and there the 64-column granule
+ *           holds both columns (tests/test_hip_k3_edges.py pins it)
  *   start_event, stop_event  optional hipEvent_t (s2m2_event_create): recorded on the kernel dispatch itself (hipExtLaunchKernel), i.e. they
  *           bracket the kernel's execution like a rocprofv3 kernel trace does, not the gaps around it (bench.py `roofline`); elapsed time
  *           is valid once the stream has been synchronised
@@ -233,6 +236,7 @@ int s2m2_sinkhorn_regress(const void* cv, float* disp, float* conf, float* occ, 
  *    batch_stride; channels-last: pix_stride=2r+1 (or larger), tap_stride=1)
  *   The reference's pixel -> normalised -> pixel fp32 coordinate round trip (grid_sample, align_corners=True,
  *   zeros padding) is reproduced on both axes.
+ *   w even and >= 4 (level 1 needs two columns); 0 <= r <= 16; B*h <= 65535 image rows per launch.
  */
 int s2m2_cv_lookup(const void* cv, const float* disp, void* corr1, void* corr2,
                    int B, int h, int w, int radius, int cv_dtype, int out_dtype,

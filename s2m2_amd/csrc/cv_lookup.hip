@@ -51,8 +51,9 @@ static int cv_lookup_impl(const void* cv, const float* disp, void* corr1, void* 
                               int cv_pitch, void* stream) {
     using namespace s2m2;
     S2M2_REQUIRE(cv && disp && corr1 && corr2, "cv_lookup: null pointer");
-    S2M2_REQUIRE(B > 0 && h > 0 && w > 1 && radius >= 0 && radius <= 16 && (long long)B * h <= 65535, "cv_lookup: bad arguments (B * h <= 65535 image rows per launch)");
-    S2M2_REQUIRE(w % 2 == 0, "cv_lookup: w=%d must be even", w);
+    S2M2_REQUIRE(B > 0 && h > 0 && w > 0 && radius >= 0 && radius <= 16 && (long long)B * h <= 65535, "cv_lookup: bad arguments (B * h <= 65535 image rows per launch)");
+    // level 1 is w / 2 columns wide and its coordinate round trip divides by w / 2 - 1: it needs two columns
+    S2M2_REQUIRE(w % 2 == 0 && w >= 4, "cv_lookup: w=%d must be even and at least 4", w);
     if (cv_pitch == 0) cv_pitch = w;
     S2M2_REQUIRE(cv_pitch >= w, "cv_lookup: cv_pitch=%d must be at least w=%d", cv_pitch, w);
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -374,7 +374,11 @@ __global__ __launch_bounds__(CFG::NWMAX * 64) void ln_corr_kernel(const T* __res
             ntile = ntile < TJ / 32 ? ntile : TJ / 32;
             int npair = (ntile + 1) >> 1;
             // banded volume (band >= 0, use_positivity models): only columns j <= i + band are ever read downstream (the masked
-            // Sinkhorn, the +-4 tap lookups at disparities >= 0), so this wave (rows i0 .. i0+31) stops at column i0 + 31 + band
+            // Sinkhorn, the +-4 tap lookups at disparities >= 0), so this wave (rows i0 .. i0+31) stops at column i0 + 31 + band.
+            // Per row r the lookups read j <= r + 12, not r + 11: pixel r + 1's fp32 coordinate round trip can land just below r + 1
+            // and then reads row r at its own last column.  Only row i0 + 31 gets past i0 + 31 + 11 that way, and column i0 + 43 is
+            // never the first of a 64-column granule (granules start at jbase + 64 n, and i0 and jbase are multiples of 32), so the
+            // granule that holds i0 + 42 holds it too.
             if (band >= 0) {
                 const int last_col = i0 + 31 + band - jbase;
                 const int need = last_col < 0 ? 0 : last_col / 64 + 1;

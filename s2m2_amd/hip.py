@@ -377,6 +377,32 @@ def _cv_pitch(cv: torch.Tensor, what: str) -> int:
     return pitch
 
 
+def _lookup_geometry(what: str, cv: torch.Tensor, disp: torch.Tensor, radius: int, buf: Optional[torch.Tensor] = None,
+                     off1: int = 0, off2: int = 0) -> int:
+    """the operands of K3 (s2m2_cv_lookup): cv a (B,h,w,w) fp16 / fp32 volume (_cv_pitch, returned), disp its contiguous fp32 (B,1,h,w)
+    map -- the kernel reads it through a float pointer whatever it holds --, 0 <= radius <= 16; and, writing into channel slots of a wider
+    tensor, buf contiguous (B,h,w,Cb) fp16 / fp32 with the 2r+1 channels at off1 and those at off2 inside a pixel and apart from each other."""
+    pitch = _cv_pitch(cv, what)
+    B, h, w, _ = cv.shape
+    if cv.dtype not in _DT:
+        raise ValueError(f"{what}: cv must be fp16 or fp32, got {cv.dtype}")
+    if not isinstance(radius, int) or not 0 <= radius <= 16:
+        raise ValueError(f"{what}: radius must be an integer in [0, 16], got {radius!r}")
+    _mat(disp, (B, 1, h, w), torch.float32, f"{what}: disp")
+    if buf is not None:
+        T = 2 * radius + 1
+        if buf.dim() != 4 or tuple(buf.shape[:3]) != (B, h, w) or buf.dtype not in _DT or not buf.is_contiguous():
+            raise ValueError(f"{what}: buf must be a contiguous ({B}, {h}, {w}, Cb) fp16 or fp32 tensor, got {tuple(buf.shape)} {buf.dtype} "
+                             f"strides {buf.stride()}")
+        cb = buf.shape[3]
+        for name, off in (("off1", off1), ("off2", off2)):
+            if not isinstance(off, int) or not 0 <= off <= cb - T:
+                raise ValueError(f"{what}: {name}={off!r}: the {T} taps must lie inside the {cb} channels of a pixel")
+        if abs(off1 - off2) < T:
+            raise ValueError(f"{what}: the tap ranges at off1={off1} and off2={off2} ({T} channels each) overlap")
+    return pitch
+
+
 def _vec(t: Optional[torch.Tensor], n: int, what: str, *, at_least: bool = False, dtype: torch.dtype = torch.float32,
          optional: bool = False) -> None:
     """a contiguous block of exactly ``n`` elements of ``dtype`` (at_least: ``n`` or more, the padded biases of K11 / K12); optional: None passes"""
@@ -581,8 +607,9 @@ def cv_lookup(cv: torch.Tensor, disp: torch.Tensor, radius: int = 4, channels_la
               out_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
     """cv (B,h,w,w), disp (B,1,h,w) fp32 -> corr1, corr2: (B,2r+1,h,w) planar or (B,h,w,2r+1) channels-last.  [A9+A10]"""
     _resident("cv_lookup", cv, disp)
-    _contig("cv_lookup", disp)
-    pitch = _cv_pitch(cv, "cv_lookup")
+    pitch = _lookup_geometry("cv_lookup", cv, disp, radius)
+    if out_dtype not in _DT:
+        raise ValueError(f"cv_lookup: out_dtype must be fp16 or fp32, got {out_dtype}")
     B, h, w, _ = cv.shape
     T = 2 * radius + 1
     if channels_last:
@@ -593,7 +620,7 @@ def cv_lookup(cv: torch.Tensor, disp: torch.Tensor, radius: int = 4, channels_la
         both = torch.empty((2, B, T, h, w), device=cv.device, dtype=out_dtype)
         c1, c2 = both[0], both[1]
         bs, ps, ts = T * h * w, 1, h * w
-    _check(load().s2m2_cv_lookup(cv.data_ptr(), disp.float().data_ptr(), c1.data_ptr(), c2.data_ptr(), B, h, w, radius,
+    _check(load().s2m2_cv_lookup(cv.data_ptr(), disp.data_ptr(), c1.data_ptr(), c2.data_ptr(), B, h, w, radius,
                                  _DT[cv.dtype], _DT[out_dtype], bs, ps, ts, pitch, _stream()), "s2m2_cv_lookup")
     return c1, c2
 
@@ -1080,10 +1107,10 @@ def resample2x(x: torch.Tensor, mode: int) -> torch.Tensor:
 
 def cv_lookup_into(cv: torch.Tensor, disp: torch.Tensor, buf: torch.Tensor, off1: int, off2: int, radius: int = 4) -> None:
     """K3 writing straight into channel slots of a wider NHWC tensor: taps of level 0 -> buf[..., off1:off1+2r+1], level 1 ->
-    buf[..., off2:off2+2r+1] (buf (B,h,w,Cb) contiguous; the other channels are left untouched)."""
+    buf[..., off2:off2+2r+1] (buf (B,h,w,Cb) contiguous, fp16 or fp32; the other channels are left untouched; the two ranges lie inside
+    a pixel's Cb channels and apart from each other: _lookup_geometry)."""
     _resident("cv_lookup_into", cv, disp, buf)
-    _contig("cv_lookup_into", disp, buf)
-    pitch = _cv_pitch(cv, "cv_lookup")
+    pitch = _lookup_geometry("cv_lookup_into", cv, disp, radius, buf, off1, off2)
     B, h, w, _ = cv.shape
     cb = buf.shape[-1]
     es = buf.element_size()

@@ -62,6 +62,84 @@ def test_cv_pitch_is_pure_geometry():
         hip._cv_pitch(torch.zeros(2, 6, 8, 8)[:, ::2], "t")
 
 
+def _lookup_operands(B=2, h=3, w=8, cb=32, buf_dtype=F16):
+    return torch.zeros(B, h, w, w, dtype=F16), torch.zeros(B, 1, h, w), torch.zeros(B, h, w, cb, dtype=buf_dtype)
+
+
+def test_lookup_geometry_accepts_what_the_engine_passes():
+    cv, disp, buf = _lookup_operands()
+    assert hip._lookup_geometry("t", cv, disp, 4) == 8
+    assert hip._lookup_geometry("t", cv, disp, 4, buf, 0, 16) == 8
+    assert hip._lookup_geometry("t", torch.zeros(2, 3, 8, 64)[..., :8], disp, 4, buf.float(), 16, 0) == 64
+    for r, cb, o1, o2 in ((0, 2, 0, 1), (0, 2, 1, 0), (16, 66, 0, 33), (4, 24, 3, 13), (4, 18, 9, 0), (4, 32, 23, 14)):
+        hip._lookup_geometry("t", cv, disp, r, torch.zeros(2, 3, 8, cb), o1, o2)
+
+
+def test_lookup_geometry_disp_is_the_fp32_map_of_the_volume():
+    cv, disp, buf = _lookup_operands()
+    for bad in (disp.half(), disp.double(), disp.int(),                  # read through a float pointer whatever it holds
+                torch.zeros(2, 3, 8), torch.zeros(2, 1, 3, 9), torch.zeros(2, 1, 4, 8), torch.zeros(1, 1, 3, 8), torch.zeros(2, 2, 3, 8),
+                torch.zeros(2, 1, 3, 16)[..., ::2], torch.zeros(2, 1, 8, 3).transpose(2, 3)):
+        with pytest.raises(ValueError, match="t: disp must be"):
+            hip._lookup_geometry("t", cv, bad, 4)
+        with pytest.raises(ValueError, match="t: disp must be"):
+            hip._lookup_geometry("t", cv, bad, 4, buf, 0, 16)
+    with pytest.raises(ValueError, match="cv must be fp16 or fp32"):
+        hip._lookup_geometry("t", cv.double(), disp, 4)
+    with pytest.raises(ValueError, match=r"cv must be a \(B,h,w,w\)"):
+        hip._lookup_geometry("t", torch.zeros(2, 3, 8, 10), disp, 4)
+
+
+@pytest.mark.parametrize("radius", [-1, 17, 4.0, None])
+def test_lookup_geometry_radius(radius):
+    cv, disp, buf = _lookup_operands(cb=80)
+    with pytest.raises(ValueError, match="radius"):
+        hip._lookup_geometry("t", cv, disp, radius)
+    with pytest.raises(ValueError, match="radius"):
+        hip._lookup_geometry("t", cv, disp, radius, buf, 0, 40)
+
+
+def test_lookup_geometry_buf_and_its_tap_ranges():
+    cv, disp, buf = _lookup_operands()
+    for bad in (torch.zeros(2, 3, 8, 32, dtype=torch.float64), torch.zeros(2, 3, 8, 32, dtype=torch.bfloat16), torch.zeros(2, 3, 9, 32),
+                torch.zeros(2, 4, 8, 32), torch.zeros(1, 3, 8, 32), torch.zeros(2 * 3 * 8, 32), torch.zeros(2, 3, 8, 64)[..., :32],
+                torch.zeros(2, 3, 8, 64)[..., ::2], torch.zeros(2, 3, 32, 8).transpose(2, 3)):
+        with pytest.raises(ValueError, match="t: buf must be"):
+            hip._lookup_geometry("t", cv, disp, 4, bad, 0, 16)
+    # radius 4: nine channels per level.  An offset past Cb - 9 writes into the next pixel and, at the last pixel, past the buffer
+    for o1, o2 in ((-1, 16), (0, -9), (24, 0), (0, 24), (32, 0), (0, 1 << 40), (0.0, 16), (None, 16)):
+        with pytest.raises(ValueError, match="must lie inside the 32 channels"):
+            hip._lookup_geometry("t", cv, disp, 4, buf, o1, o2)
+    for o1, o2 in ((0, 0), (0, 8), (8, 0), (10, 2), (23, 15)):
+        with pytest.raises(ValueError, match="overlap"):
+            hip._lookup_geometry("t", cv, disp, 4, buf, o1, o2)
+    with pytest.raises(ValueError, match="must lie inside the 8 channels"):
+        hip._lookup_geometry("t", cv, disp, 4, torch.zeros(2, 3, 8, 8), 0, 0)
+    with pytest.raises(ValueError, match="must lie inside the 32 channels"):
+        hip._lookup_geometry("t", cv, disp, 16, buf, 0, 16)               # 33 taps do not fit 32 channels
+
+
+def test_lookup_wrappers_refuse_bad_operands_before_the_library(monkeypatch):
+    """both wrappers go through the helper: on operands that pass the residency check the refusal comes before any library call"""
+    monkeypatch.setattr(hip, "_lib", _NoLibrary())
+    monkeypatch.setattr(hip, "_resident", lambda what, *ts: None)
+    cv, disp, buf = _lookup_operands()
+    with pytest.raises(ValueError, match="cv_lookup: disp must be"):
+        hip.cv_lookup(cv, disp.half())
+    with pytest.raises(ValueError, match="cv_lookup: radius"):
+        hip.cv_lookup(cv, disp, 17)
+    with pytest.raises(ValueError, match="out_dtype"):
+        hip.cv_lookup(cv, disp, 4, False, torch.bfloat16)
+    with pytest.raises(ValueError, match="cv_lookup_into: disp must be"):
+        hip.cv_lookup_into(cv, disp.half(), buf, 0, 16)
+    with pytest.raises(ValueError, match="cv_lookup_into: off2=24"):
+        hip.cv_lookup_into(cv, disp, buf, 0, 24)
+    with pytest.raises(ValueError, match="cv_lookup_into: .*overlap"):
+        hip.cv_lookup_into(cv, disp, buf, 0, 8)
+    with pytest.raises(ValueError, match="cv_lookup_into: buf must be"):
+        hip.cv_lookup_into(cv, disp, buf[:, :2], 0, 16)
+
+
 # ------------------------------------------------------------------------------------------------ _vec / _mat / _frag
 def test_vec_exact_and_at_least():
     v = torch.zeros(16)

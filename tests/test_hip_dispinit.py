@@ -163,7 +163,9 @@ def test_lookup_full_size_vs_oracle(hip):
 @pytest.mark.parametrize("shape", [(1, 6, 304, 128), (2, 3, 160, 128), (1, 2, 608, 64), (1, 4, 304, 256)])
 def test_ln_corr_banded_equals_full_inside_the_band(hip, shape, dtype):
     """s2m2_ln_corr_banded (use_positivity models): bit-identical to the full volume for j <= i + band, nothing written in tiles that
-    lie entirely beyond it (lookups and the masked Sinkhorn never read j > i + 11)."""
+    lie entirely beyond it.  SURVEY.md 8d: the masked Sinkhorn reads j <= i, the lookups of d >= 0 read j <= r + 12 on row r -- one past
+    i + 11, on the rows the fp32 coordinate round trip of pixel r + 1 lands on; the 64-column store granule holds that column wherever it
+    is read (tests/test_hip_k3_edges.py::test_banded_volume_holds_everything_the_lookups_read)."""
     B, h, w, C = shape
     g = torch.Generator(device="cuda").manual_seed(w + C)
     feat = (torch.randn(2 * B, h, w, C, device="cuda", generator=g) * 1.3 + 0.1).to(dtype)
