@@ -22,6 +22,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
+#include "row_coord.h"
 
 namespace s2m2 {
 
@@ -524,32 +525,41 @@ __global__ __launch_bounds__(CFG::NT, (CFG::DIRECT && CFG::C == 128) ? S2M2_CHAI
     if constexpr (CFG::DIRECT) ws.fetch_direct(wfirst, 0, 0);
     else ws.fetch(0, 0);
     raw16_t xr[CFG::X_IT];
+    if (!CFG::DIRECT || p.pool_w == 0) {                           // block-uniform (the host takes pool_h / pool_w with the direct form only)
 #pragma unroll
-    for (int it = 0; it < CFG::X_IT; ++it) {
-        const int idx = tid + CFG::NT * it, row = idx / CFG::PPR, pcx = idx - row * CFG::PPR;
-        const long long m = m0 + row;
-        if (p.pool_w == 0) {                                       // block-uniform
+        for (int it = 0; it < CFG::X_IT; ++it) {
+            const int idx = tid + CFG::NT * it, row = idx / CFG::PPR, pcx = idx - row * CFG::PPR;
+            const long long m = m0 + row;
             const T* src = m < p.rows ? static_cast<const T*>(p.x) + m * p.x_stride + pcx * VEC : static_cast<const T*>(p.zero);
             xr[it] = global_load16(src);
-        } else {
-            // AvgPool2d(2) in front of the chain (the down_conv of Unet / MRT, unet.py:24-29): the mean of four pixels, formed and rounded
-            // exactly as K7's pooling kernel and K5's pool2 operand load do ((a + b + c + d) * 0.25 in fp32, one rounding)
-            const int Wo = p.pool_w >> 1, Ho = p.pool_h >> 1;
-            const bool ok = m < p.rows;
-            const long long mm = ok ? m : 0;
-            const int xo = (int)(mm % Wo);
-            const long long t = mm / Wo;
-            const int yo = (int)(t % Ho);
-            const long long n = t / Ho;
-            const T* q = static_cast<const T*>(p.x) + ((n * p.pool_h + 2 * yo) * p.pool_w + 2 * xo) * p.x_stride + pcx * VEC;
-            const long long dx = p.x_stride, dy = (long long)p.pool_w * p.x_stride;
-            const Vec16<T> a = __builtin_bit_cast(Vec16<T>, global_load16(q)), b = __builtin_bit_cast(Vec16<T>, global_load16(q + dx));
-            const Vec16<T> c = __builtin_bit_cast(Vec16<T>, global_load16(q + dy)), d = __builtin_bit_cast(Vec16<T>, global_load16(q + dy + dx));
-            Vec16<T> o;
+        }
+    } else if constexpr (CFG::DIRECT) {
+        // AvgPool2d(2) in front of the chain (the down_conv of Unet / MRT, unet.py:24-29): the mean of four pixels, formed and rounded
+        // exactly as K7's pooling kernel and K5's pool2 operand load do ((a + b + c + d) * 0.25 in fp32, one rounding).  Row m = (n, yo, xo)
+        // of the pooled grid: one 32-bit division pair per thread, then a walk from piece to piece (row_coord.h); offsets inside an input
+        // image are 32-bit (the host checked the extent), the image base is one 64-bit product.
+        static_assert(CFG::NT % CFG::PPR == 0, "the pieces of a thread share their column");
+        constexpr int RSTEP = CFG::NT / CFG::PPR;
+        const int row0 = tid / CFG::PPR, pcx = tid - row0 * CFG::PPR;
+        const int left = (int)(p.rows - m0 < CFG::BM ? p.rows - m0 : CFG::BM);     // rows of this tile that exist (<= 0: none)
+        const RowWalk<RSTEP> walk((unsigned)(p.pool_h >> 1), (unsigned)(p.pool_w >> 1));
+        RowCoord rc = walk.decompose((unsigned)m0 + (unsigned)row0);
+        const unsigned dx = (unsigned)p.x_stride, dy = (unsigned)p.pool_w * dx, image = (unsigned)p.pool_h * dy;
+        const T* xc = static_cast<const T*>(p.x) + pcx * VEC;
+#pragma unroll
+        for (int it = 0; it < CFG::X_IT; ++it) {
+            const bool ok = row0 + RSTEP * it < left;                                // rows past the end read pixel (0, 0, 0) and hold zeros, as before
+            const unsigned n = ok ? rc.n : 0u, yo = ok ? rc.y : 0u, xo = ok ? rc.x : 0u;
+            walk.step(rc);
+            const T* q = xc + (unsigned long long)n * image;
+            const unsigned o = 2u * yo * dy + 2u * xo * dx;
+            const Vec16<T> a = __builtin_bit_cast(Vec16<T>, global_load16(q + o)), b = __builtin_bit_cast(Vec16<T>, global_load16(q + (o + dx)));
+            const Vec16<T> c = __builtin_bit_cast(Vec16<T>, global_load16(q + (o + dy))), d = __builtin_bit_cast(Vec16<T>, global_load16(q + (o + dy + dx)));
+            Vec16<T> o16;
 #pragma unroll
             for (int e = 0; e < VEC; ++e)
-                o.v[e] = ok ? from_f32<T>((to_f32(a.v[e]) + to_f32(b.v[e]) + to_f32(c.v[e]) + to_f32(d.v[e])) * 0.25f) : from_f32<T>(0.f);
-            xr[it] = __builtin_bit_cast(raw16_t, o);
+                o16.v[e] = ok ? from_f32<T>((to_f32(a.v[e]) + to_f32(b.v[e]) + to_f32(c.v[e]) + to_f32(d.v[e])) * 0.25f) : from_f32<T>(0.f);
+            xr[it] = __builtin_bit_cast(raw16_t, o16);
         }
     }
 #pragma unroll
@@ -634,6 +644,8 @@ static int mlp_chain_impl(const s2m2_chain_desc* d, void* stream) {
                  "mlp_chain: pool_h / pool_w need weight_frag, an input of at least 2x2 pixels and rows = N * (pool_h/2) * (pool_w/2)");
     S2M2_REQUIRE((d->pool_h == 0 && d->pool_w == 0) || (d->res_stage < 0 && !d->carry && !d->ln_out && d->xcd_group_rows == 0),
                  "mlp_chain: no residual, carry, ln_out or xcd_group_rows with a pooled tile load (pool_h / pool_w)");
+    S2M2_REQUIRE(d->pool_h == 0 || (d->rows < (1LL << 31) && image_extent_fits_u32((long long)d->pool_h * d->pool_w, d->x_stride)),
+                 "mlp_chain: a pooled input image of %d x %d pixels of stride %lld does not fit 32-bit element offsets", d->pool_h, d->pool_w, d->x_stride);
     if (d->nstage == 0 && d->weight_frag) {
         // fan-out only, direct form: the nfan layers read the x rows, their fragments straight from global memory (any row count)
         S2M2_REQUIRE(d->nfan >= 1 && d->nfan <= 4, "mlp_chain: nfan=%d (1..4)", d->nfan);

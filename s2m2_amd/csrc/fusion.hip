@@ -18,6 +18,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
+#include "row_coord.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -103,38 +104,52 @@ template <> struct Quad<float> { float4_t v; };
 template <typename CFG, typename T>
 __device__ __forceinline__ void fusion_request_rows(const FusionArgs& p, long long m0, int tid, raw16_t (&xr0)[CFG::X_IT], raw16_t (&xr1)[CFG::X_IT]) {
     constexpr int VEC = CFG::VEC;
+    // a thread's pieces: one 16-byte column (pcx), rows row0, row0 + RSTEP, ... of the tile -- all index arithmetic per THREAD (one 64-bit
+    // product for the tile, 32-bit offsets and pointer increments from there), nothing per piece but adds
+    static_assert(CFG::NT % CFG::PPR == 0, "the pieces of a thread share their column");
+    constexpr int RSTEP = CFG::NT / CFG::PPR;
+    const int row0 = tid / CFG::PPR, pcx = tid - row0 * CFG::PPR;
+    const int left = (int)(p.rows - m0 < CFG::BM ? p.rows - m0 : CFG::BM);           // rows of this tile that exist (>= 1)
+    const T* zero = static_cast<const T*>(p.zero);
+    const T* q0 = static_cast<const T*>(p.z0) + (m0 + row0) * p.z0_stride + pcx * VEC;
+    const long long dq0 = RSTEP * p.z0_stride;
+#pragma unroll
+    for (int it = 0; it < CFG::X_IT; ++it) xr0[it] = global_load16(row0 + RSTEP * it < left ? q0 + it * dq0 : zero);
+    if (p.up_h == 0) {                                                                // block-uniform, decided once for all pieces
+        const T* q1 = static_cast<const T*>(p.z1) + (m0 + row0) * p.z1_stride + pcx * VEC;
+        const long long dq1 = RSTEP * p.z1_stride;
+#pragma unroll
+        for (int it = 0; it < CFG::X_IT; ++it) xr1[it] = global_load16(row0 + RSTEP * it < left ? q1 + it * dq1 : zero);
+        return;
+    }
+    // the x2 bilinear resampling of K7 (upsample.hip, same arithmetic and rounding) folded into the tile load: row m = (n, Y, X) of the fine
+    // grid reads its four coarse neighbours.  (n, Y, X) comes from ONE 32-bit division pair per thread (row_coord.h: rows < 2^31) and walks
+    // from piece to piece; offsets inside a coarse image are 32-bit (the host checked the extent), the image base is one 64-bit product.
+    const RowWalk<RSTEP> walk(2u * (unsigned)p.up_h, 2u * (unsigned)p.up_w);
+    RowCoord rc = walk.decompose((unsigned)m0 + (unsigned)row0);
+    const unsigned s1 = (unsigned)p.z1_stride, pitch = (unsigned)p.up_w * s1, image = (unsigned)p.up_h * pitch;
+    const T* z1c = static_cast<const T*>(p.z1) + pcx * VEC;
 #pragma unroll
     for (int it = 0; it < CFG::X_IT; ++it) {
-        const int idx = tid + CFG::NT * it, row = idx / CFG::PPR, pcx = idx - row * CFG::PPR;
-        const long long m = m0 + row;
-        const bool ok = m < p.rows;
-        xr0[it] = global_load16(ok ? static_cast<const T*>(p.z0) + m * p.z0_stride + pcx * VEC : static_cast<const T*>(p.zero));
-        if (p.up_h == 0) {
-            xr1[it] = global_load16(ok ? static_cast<const T*>(p.z1) + m * p.z1_stride + pcx * VEC : static_cast<const T*>(p.zero));
-        } else {
-            // the x2 bilinear resampling of K7 (upsample.hip, same arithmetic and rounding) folded into the tile load: row m = (n, Y, X) of
-            // the fine grid reads its four coarse neighbours
-            const int Wo = 2 * p.up_w, Ho = 2 * p.up_h;
-            const long long mm = ok ? m : 0;
-            const int Xf = (int)(mm % Wo);
-            const long long t = mm / Wo;
-            const int Yf = (int)(t % Ho);
-            const long long n = t / Ho;
-            const float sy = fmaxf(((float)Yf + 0.5f) * 0.5f - 0.5f, 0.f), sx = fmaxf(((float)Xf + 0.5f) * 0.5f - 0.5f, 0.f);
-            const int y0 = (int)sy, x0 = (int)sx;
-            const int y1 = y0 + (y0 < p.up_h - 1), x1 = x0 + (x0 < p.up_w - 1);
-            const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-            const T* zb = static_cast<const T*>(p.z1) + n * p.up_h * p.up_w * p.z1_stride + pcx * VEC;
-            const Vec16<T> a = __builtin_bit_cast(Vec16<T>, global_load16(zb + ((long long)y0 * p.up_w + x0) * p.z1_stride));
-            const Vec16<T> b = __builtin_bit_cast(Vec16<T>, global_load16(zb + ((long long)y0 * p.up_w + x1) * p.z1_stride));
-            const Vec16<T> c = __builtin_bit_cast(Vec16<T>, global_load16(zb + ((long long)y1 * p.up_w + x0) * p.z1_stride));
-            const Vec16<T> d = __builtin_bit_cast(Vec16<T>, global_load16(zb + ((long long)y1 * p.up_w + x1) * p.z1_stride));
-            Vec16<T> o;
+        const bool ok = row0 + RSTEP * it < left;                                     // rows past the end read pixel (0, 0, 0), as before
+        const int Yf = ok ? (int)rc.y : 0, Xf = ok ? (int)rc.x : 0;
+        const unsigned n = ok ? rc.n : 0u;
+        walk.step(rc);
+        const float sy = fmaxf(((float)Yf + 0.5f) * 0.5f - 0.5f, 0.f), sx = fmaxf(((float)Xf + 0.5f) * 0.5f - 0.5f, 0.f);
+        const int y0 = (int)sy, x0 = (int)sx;
+        const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+        const unsigned o00 = (unsigned)y0 * pitch + (unsigned)x0 * s1;                // (y0, x0); the neighbours one column / one row on,
+        const unsigned ox = x0 < p.up_w - 1 ? s1 : 0u, oy = y0 < p.up_h - 1 ? pitch : 0u;   // clamped at the last column / row
+        const T* zb = z1c + (unsigned long long)n * image;
+        const Vec16<T> a = __builtin_bit_cast(Vec16<T>, global_load16(zb + o00));
+        const Vec16<T> b = __builtin_bit_cast(Vec16<T>, global_load16(zb + (o00 + ox)));
+        const Vec16<T> c = __builtin_bit_cast(Vec16<T>, global_load16(zb + (o00 + oy)));
+        const Vec16<T> d = __builtin_bit_cast(Vec16<T>, global_load16(zb + (o00 + oy + ox)));
+        Vec16<T> o;
 #pragma unroll
-            for (int e = 0; e < VEC; ++e)
-                o.v[e] = from_f32<T>(hy * (hx * to_f32(a.v[e]) + lx * to_f32(b.v[e])) + ly * (hx * to_f32(c.v[e]) + lx * to_f32(d.v[e])));
-            xr1[it] = __builtin_bit_cast(raw16_t, o);
-        }
+        for (int e = 0; e < VEC; ++e)
+            o.v[e] = from_f32<T>(hy * (hx * to_f32(a.v[e]) + lx * to_f32(b.v[e])) + ly * (hx * to_f32(c.v[e]) + lx * to_f32(d.v[e])));
+        xr1[it] = __builtin_bit_cast(raw16_t, o);
     }
 }
 template <typename CFG, typename T>
@@ -192,13 +207,15 @@ __device__ __forceinline__ void fusion_mix_store(const FusionArgs& p, const floa
         }
     }
     __syncthreads();
-    T* outp = static_cast<T*>(p.out);
+    constexpr int RSTEP = CFG::NT / CFG::PPR;                        // (pieces of a thread as in fusion_request_rows)
+    const int row0 = tid / CFG::PPR, pcx = tid - row0 * CFG::PPR;
+    const int left = (int)(p.rows - m0 < CFG::BM ? p.rows - m0 : CFG::BM);
+    T* outp = static_cast<T*>(p.out) + (m0 + row0) * p.out_stride + pcx * VEC;
+    const long long dout = RSTEP * p.out_stride;
 #pragma unroll
     for (int it = 0; it < CFG::X_IT; ++it) {
-        const int idx = tid + CFG::NT * it, row = idx / CFG::PPR, pcx = idx - row * CFG::PPR;
-        const long long m = m0 + row;
-        if (m < p.rows)
-            *reinterpret_cast<raw16_t*>(outp + m * p.out_stride + pcx * VEC) = *reinterpret_cast<const raw16_t*>(H + (size_t)row * HRS + pcx * VEC);
+        const int row = row0 + RSTEP * it;
+        if (row < left) *reinterpret_cast<raw16_t*>(outp + it * dout) = *reinterpret_cast<const raw16_t*>(H + (size_t)row * HRS + pcx * VEC);
     }
 }
 
@@ -454,6 +471,8 @@ static int feature_fusion_frag_impl(const void* z0, const void* z1, void* out, l
                  "feature_fusion_frag: row strides must be multiples of 8 and at least C");
     S2M2_REQUIRE((z1_coarse_h == 0 && z1_coarse_w == 0) || (z1_coarse_h > 0 && z1_coarse_w > 0 && rows % (4LL * z1_coarse_h * z1_coarse_w) == 0),
                  "feature_fusion_frag: rows=%lld is not a whole number of (2*%d) x (2*%d) images", rows, z1_coarse_h, z1_coarse_w);
+    S2M2_REQUIRE(z1_coarse_h == 0 || image_extent_fits_u32((long long)z1_coarse_h * z1_coarse_w, z1_stride),
+                 "feature_fusion_frag: a coarse image of %d x %d pixels of stride %lld does not fit 32-bit element offsets", z1_coarse_h, z1_coarse_w, z1_stride);
     FusionArgs a;
     a.z0 = z0; a.z1 = z1; a.out = out; a.z0_stride = z0_stride; a.z1_stride = z1_stride; a.out_stride = out_stride; a.rows = rows;
     a.w1 = w_stream; a.w2 = nullptr; a.b1 = b1; a.bg = bg; a.bf = bf;
@@ -491,6 +510,8 @@ static int feature_fusion_impl(const void* z0, const void* z1, void* out, long l
     a.up_h = z1_coarse_h; a.up_w = z1_coarse_w;
     S2M2_REQUIRE((z1_coarse_h == 0 && z1_coarse_w == 0) || (z1_coarse_h > 0 && z1_coarse_w > 0 && rows % (4LL * z1_coarse_h * z1_coarse_w) == 0),
                  "feature_fusion: rows=%lld is not a whole number of (2*%d) x (2*%d) images", rows, z1_coarse_h, z1_coarse_w);
+    S2M2_REQUIRE(z1_coarse_h == 0 || image_extent_fits_u32((long long)z1_coarse_h * z1_coarse_w, z1_stride),
+                 "feature_fusion: a coarse image of %d x %d pixels of stride %lld does not fit 32-bit element offsets", z1_coarse_h, z1_coarse_w, z1_stride);
     if (bind_zero_page(a, "feature_fusion")) return 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // measured end to end (same-box A/B): 32-row tiles (the 64-row tile of C = 128 needs 234 VGPRs for its three accumulator sets

@@ -19,6 +19,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "epilogue.h"
+#include "row_coord.h"
 
 namespace s2m2 {
 
@@ -116,26 +117,36 @@ __global__ __launch_bounds__(CFG::NT) void pw_direct_kernel(PwArgs p) {
         default: stage_tile<CFG, T, S2M2_ACT_NONE>(acc, A, bias, 1.0f, wm, wn, lane); break;
     }
     __syncthreads();
-    T* outp = static_cast<T*>(p.out);
+    // a thread's pieces: one 16-byte column of couts (pc), rows row0, row0 + RSTEP, ... -- its cout, and with it the sub-pixel of the shuffle,
+    // are fixed, and the output pixel walks from piece to piece (row_coord.h: one 32-bit division pair per thread, none per piece)
+    static_assert(CFG::NT % CFG::CPR == 0 && CFG::BM * CFG::CPR == CFG::NT * CFG::C_IT, "the pieces of a thread share their column");
+    constexpr int RSTEP = CFG::NT / CFG::CPR;
+    const int row0 = tid / CFG::CPR, pc = tid - row0 * CFG::CPR, co = pc * VEC;
+    const int left = (int)(p.rows - m0 < CFG::BM ? p.rows - m0 : CFG::BM);         // rows of this tile that exist (>= 1)
+    if (co >= p.Cout) return;
+    const T* stg = A + (size_t)row0 * CRS + co;
+    if (!p.shuffle2) {                                              // block-uniform
+        T* q = static_cast<T*>(p.out) + (m0 + row0) * p.out_stride + co;
+        const long long dq = RSTEP * p.out_stride;
+#pragma unroll
+        for (int it = 0; it < CFG::C_IT; ++it)
+            if (row0 + RSTEP * it < left) *reinterpret_cast<raw16_t*>(q + it * dq) = *reinterpret_cast<const raw16_t*>(stg + (size_t)it * RSTEP * CRS);
+        return;
+    }
+    // cout = (dy * 2 + dx) * C' + c' (same map as K5, conv.hip store_tile): input pixel (n, y, x) -> output pixel (n, 2y + dy, 2x + dx) of the
+    // (2 Ho, 2 Wo) grid; offsets inside an output image are 32-bit (the host checked the extent), the image base is one 64-bit product
+    const int sub = co / p.shuffle2, oc = co - sub * p.shuffle2;
+    const RowWalk<RSTEP> walk((unsigned)p.Ho, (unsigned)p.Wo);
+    RowCoord rc = walk.decompose((unsigned)m0 + (unsigned)row0);
+    const unsigned os = (unsigned)p.out_stride, pitch = 2u * (unsigned)p.Wo * os, image = 2u * (unsigned)p.Ho * pitch;
+    T* outc = static_cast<T*>(p.out) + oc;
+    const unsigned osub = (unsigned)(sub >> 1) * pitch + (unsigned)(sub & 1) * os;
 #pragma unroll
     for (int it = 0; it < CFG::C_IT; ++it) {
-        const int idx = tid + CFG::NT * it, row = idx / CFG::CPR, pc = idx - row * CFG::CPR;
-        const int co = pc * VEC;
-        const long long m = m0 + row;
-        if (idx >= CFG::BM * CFG::CPR || m >= p.rows || co >= p.Cout) continue;
-        const raw16_t v = *reinterpret_cast<const raw16_t*>(A + (size_t)row * CRS + co);
-        long long opix = m;
-        int oc = co;
-        if (p.shuffle2) {                                           // cout = (dy * 2 + dx) * C' + c' (same map as K5, conv.hip store_tile)
-            const int sub = co / p.shuffle2;
-            oc = co - sub * p.shuffle2;
-            const int x = (int)(m % p.Wo);
-            const long long t = m / p.Wo;
-            const int y = (int)(t % p.Ho);
-            const long long n = t / p.Ho;
-            opix = (n * (2 * p.Ho) + 2 * y + (sub >> 1)) * (2LL * p.Wo) + 2 * x + (sub & 1);
-        }
-        *reinterpret_cast<raw16_t*>(outp + opix * p.out_stride + oc) = v;
+        if (row0 + RSTEP * it < left)
+            *reinterpret_cast<raw16_t*>(outc + (unsigned long long)rc.n * image + (2u * rc.y * pitch + 2u * rc.x * os + osub)) =
+                *reinterpret_cast<const raw16_t*>(stg + (size_t)it * RSTEP * CRS);
+        walk.step(rc);
     }
 }
 
@@ -209,6 +220,8 @@ static int pw_direct_impl(const s2m2_pw_desc* d, void* stream) {
     S2M2_REQUIRE(d->shuffle2 == 0 || (d->shuffle2 % 8 == 0 && d->Cout == 4 * d->shuffle2 && d->Ho > 0 && d->Wo > 0 && d->rows % ((long long)d->Ho * d->Wo) == 0),
                  "pw_direct: shuffle2=%d needs Cout = 4 * shuffle2 (a multiple of 8 channels per sub-pixel) and rows = N * Ho * Wo", d->shuffle2);
     S2M2_REQUIRE(d->out_stride >= (d->shuffle2 ? d->shuffle2 : d->Cout), "pw_direct: out_stride=%lld is smaller than the output channels", d->out_stride);
+    S2M2_REQUIRE(d->shuffle2 == 0 || (d->rows < (1LL << 31) && image_extent_fits_u32(4LL * d->Ho * d->Wo, d->out_stride)),
+                 "pw_direct: shuffle2 needs rows < 2^31 and an output image (%d x %d pixels of stride %lld) that fits 32-bit element offsets", 2 * d->Ho, 2 * d->Wo, d->out_stride);
     PwArgs a;
     for (int i = 0; i < 4; ++i) {
         const int j = i < d->nsrc ? i : d->nsrc - 1;
