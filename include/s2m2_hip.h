@@ -46,7 +46,8 @@ enum { S2M2_F32 = 0, S2M2_F16 = 1 };
  * evaluation stage behind the forward), added the same way, and with s2m2_mesh, s2m2_mesh_workspace_bytes, s2m2_mesh_tile_rows and s2m2_mesh_desc
  * (K20, the surface mesh behind the 3D stage), and with s2m2_register, s2m2_register_workspace_bytes and s2m2_register_desc (K21, the depth
  * map registered to a second camera), and with s2m2_segment, s2m2_segment_workspace_bytes, s2m2_segment_tile_rows, s2m2_segment_tile_cols and
- * s2m2_segment_desc (K22, connected components and the speckle filter). */
+ * s2m2_segment_desc (K22, connected components and the speckle filter), and with s2m2_voxel, s2m2_voxel_workspace_bytes, s2m2_voxel_tile_rows,
+ * s2m2_voxel_home_slot and s2m2_voxel_desc (K23, voxel-grid downsampling of the point cloud). */
 #define S2M2_ABI_VERSION 800
 int s2m2_version(void);
 const char* s2m2_last_error(void);
@@ -1095,6 +1096,75 @@ size_t s2m2_segment_workspace_bytes(int B, int H, int W);   /* 0: bad extents */
 int s2m2_segment_tile_rows(int H, int W);                   /* the tile of launch A (at most H), so that tests can aim at its borders; 0: bad extents */
 int s2m2_segment_tile_cols(int H, int W);                   /* ... (at most W) */
 int s2m2_segment(const s2m2_segment_desc* desc, void* stream);
+
+/*
+ * K23 -- voxel-grid downsampling of K15's point cloud: one record per occupied voxel, the centroid and the mean colour of the kept points in it
+ *   (what open3d's voxel_down_sample and PCL's VoxelGrid do on the host).  Like K18 and K20 to K22 it has no counterpart in the reference: the
+ *   semantics are defined here and pinned by the numpy oracle of tests/voxel_oracle.py.  Still S2M2_ABI_VERSION 800: the entry points are
+ *   added, nothing changes in place.
+ *   `cloud` holds the INPUT fields of s2m2_cloud, with their meaning, as s2m2_segment takes them: the padded maps, the unpadded image (always
+ *   required here), H, W, Hp, Wp (fused crop), camera and filter parameters, unfiltered.  Its output fields are IGNORED.
+ *   Which points.  keep, z, x, y and the colour bytes of a pixel are K15's, formula for formula (the same device functions).
+ *   Quantisation.  vs = (float)voxel_size, in the units of z; q = vs / 1024.0f (exact).  Per axis X = rintf(x / q): one fp32 division, one
+ *     round-to-nearest-even, in float; Y and Z likewise.  A kept point is IN RANGE iff fabsf(X), fabsf(Y) and fabsf(Z) are all < 2^30; kept
+ *     points out of range are dropped and counted (with depth_trunc <= 0 K15 keeps d <= 0 at z = 1e9f / depth_scale: such points usually land
+ *     here).  With the integer X: the voxel index ix = X >> 10 (floor, also for negative X) and the local offset lx = X & 1023; iy, iz, ly, lz
+ *     likewise.  A voxel is the triple (ix, iy, iz), each in [-2^20, 2^20).  Everything behind the one division is integer arithmetic.
+ *   Per voxel, integer aggregates over its points: n (int32), the sums of lx, ly, lz and of the colour bytes r, g, b (64 bits each), and
+ *     first, the smallest raster index v * W + u of its points.
+ *   Record of a voxel (16 bytes, K15's format):
+ *       x = (float)(((double)ix * 1024.0 + (double)sum_lx / (double)n) * (double)q);    y, z likewise
+ *       colour byte = (2 * sum + n) / (2 * n) in integers (the mean rounded to nearest, halves up);    a = 255
+ *     The records of a pair are stored in ascending `first`: the raster order of the voxels' first points.  A pixel is its voxel's LEADER iff
+ *     its raster index equals first.
+ *   outputs, each optional (NULL), at least one:
+ *     records  (B, capacity) 16-byte records (16-byte aligned) at records + b * capacity
+ *     weights  (B, capacity) int32: n of each record
+ *     count    (B) int32: the number of voxels in the table -- the true number also above `capacity`; records and weights of rank >= capacity are
+ *              not stored and the rest of both buffers is left untouched
+ *     index    (B,1,H,W) int32: the record rank of the pixel's voxel (the true rank, also >= capacity); -1 where the pixel is not kept or was
+ *              dropped.  One more launch, only when requested
+ *     stats    (B,4) int32: kept points, points dropped out of range, points dropped because the table was full, voxels
+ *   Table.  max_voxels (per pair, 1 .. 2^29) sizes an open-addressing hash table of `slots` slots of 64 bytes per pair in the workspace, slots =
+ *     the smallest power of two >= 2 * max_voxels.  workspace: >= s2m2_voxel_workspace_bytes(B, H, W, max_voxels) bytes, 16-byte aligned: the
+ *     tables, an int32 plane (B,H,W) with every pixel's slot, the tile counts and the counters.  Nothing depends on what it held before: the
+ *     call clears what it needs.  A new voxel is claimed by the one thread that wins its slot, and only that thread asks the pair's occupancy
+ *     counter for room: a pair with at most max_voxels distinct voxels never loses a point (stats[2] == 0), however the insertions race, and
+ *     uses at most max_voxels slots, so its load stays <= 1/2.  If a pair has more than max_voxels distinct voxels, the winner that finds no
+ *     room sets the pair's full flag, and it and every later point that meets an empty slot give up and are counted in stats[2]; the
+ *     records, weights and index of THAT pair are unspecified (which points were dropped depends on arrival) and count <= slots.  Every probe
+ *     loop is bounded by `slots` whatever the load.
+ *   Launches: clear the table; insert (key compare-and-swap with linear probing from s2m2_voxel_home_slot, int32 / int64 atomic adds, an
+ *     atomic minimum for first; runs of neighbouring pixels in one voxel are summed in registers and across the lanes of a wave first and
+ *     insert once); count the leaders per raster tile; rank them and store; index when requested.  No host step, no synchronisation, no
+ *     waiting between blocks.  Integer sums and minima do not depend on the order or grouping of their operands, the record is a function of
+ *     them alone, and the order of the records is the raster order of the leaders: the outputs are bit-reproducible although this stage uses
+ *     atomics and although the slot a voxel lands in depends on arrival.
+ *   Launch plans: s2m2_voxel is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing;
+ *   the stage runs after s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ *   Errors (before any device call): null descriptor; everything s2m2_cloud checks on its inputs (maps, extents, fx, fy, depth_scale, image
+ *   dtype, alignment); a null image; voxel_size not finite or <= 0 in fp32; max_voxels < 1 or > 2^29 (the slot count would reach 2^31); no
+ *   output requested; negative capacity; records and weights both NULL with capacity > 0; records not 16-byte aligned; a missing workspace or
+ *   one not 16-byte aligned; weights, count, index or stats not 4-byte aligned.
+ */
+typedef struct s2m2_voxel_desc {
+    s2m2_cloud_desc cloud;
+    void*          records;
+    int32_t*       weights;
+    int32_t*       count;
+    int32_t*       index;
+    int32_t*       stats;
+    void*          workspace;
+    double         voxel_size; /* > 0, in the units of z */
+    long long      max_voxels; /* per pair, 1 .. 2^29 */
+    long long      capacity;   /* records (and weights) per pair */
+} s2m2_voxel_desc;
+size_t s2m2_voxel_workspace_bytes(int B, int H, int W, long long max_voxels);   /* 0: bad extents or max_voxels */
+int s2m2_voxel_tile_rows(int H, int W);                    /* rows of a raster tile (K15's, at most H), so that tests can aim at its borders; 0: bad extents */
+/* the slot where the probe chain of voxel (ix, iy, iz) starts in a table of `slots` slots (a power of two, 2 .. 2^30), so that tests can aim
+ * at probe chains; host code; -1: bad arguments */
+long long s2m2_voxel_home_slot(int ix, int iy, int iz, long long slots);
+int s2m2_voxel(const s2m2_voxel_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,13 @@
 //   component, -1 = not kept; --segment-mask: raw uint8 (B,1,H,W), 1 = survives.  With --repeat: {"segment_kept", "segment_components",
 //   "segment_surviving", "repeat", "segment_us_per_pair"} on a line of its own.  Without --min-size nothing here happens.
 //
+// --voxel SIZE --voxel-ply OUT.ply [--voxel-max N]: the point cloud downsampled on a voxel grid (s2m2_voxel) -- one vertex per occupied cell of
+//   SIZE (the unit of z: metres with a Middlebury calibration), the centroid and the mean colour of the cell's points, in --ply's layout and
+//   file naming.  Needs --calib, honours every option of --ply, comes behind --min-size exactly as --ply does, and may be given next to --ply
+//   / --mesh or without them.  --voxel-max: the distinct voxels a pair may have (default: a quarter of the image's pixels); a pair with more
+//   fails the run instead of leaving a thinned file.  With --repeat: {"voxel_points", "voxel_kept", "voxel_out_of_range", "repeat",
+//   "voxel_us_per_pair"} on a line of its own.
+//
 // Evaluation against ground truth (s2m2_disp_eval on the device buffers of the run; without --gt nothing below happens):
 //   --gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] [--thresholds a,b,c] [--conf-min X] [--occ-min X] --metrics OUT.json
 // --gt: a greyscale PFM (Pf) of W x (B * H) pixels, H <= out_h and W <= out_w of the engine: the ground truths of the B pairs stacked top to
@@ -248,6 +255,48 @@ static int stage_cloud(Context& c) {
     return 0;
 }
 
+// --voxel (K23): the downsampled cloud
+static int stage_voxel(Context& c) {
+    const Options& o = c.o;
+    const s2m2_engine_info& m = c.m;
+    const size_t npix = (size_t)m.H * m.W;
+    const long long max_voxels = o.voxel_max > 0 ? o.voxel_max : (npix / 4 > 0 ? (long long)(npix / 4) : 1);
+    const void* image = nullptr;
+    int image_dtype = 0;
+    if (left_image(c, &image, &image_dtype)) return 1;
+    const size_t ws_bytes = s2m2_voxel_workspace_bytes(m.B, m.H, m.W, max_voxels);
+    if (ws_bytes == 0) return fail("--voxel: extents or --voxel-max too large");
+    DeviceBuffer drec, dws, dcount, dstats;
+    if (DeviceBuffer::make(drec, (size_t)m.B * max_voxels * 16) || DeviceBuffer::make(dws, ws_bytes) || DeviceBuffer::make(dcount, m.B * sizeof(int32_t)) ||
+        DeviceBuffer::make(dstats, m.B * 4 * sizeof(int32_t)))
+        return 1;
+    s2m2_voxel_desc vd;
+    memset(&vd, 0, sizeof vd);
+    fill_cloud_inputs(vd.cloud, m, c.disp3d, c.maps[1], c.maps[2], image, image_dtype, c.unfiltered3d, c.cal, o);
+    vd.records = drec.h; vd.count = dcount.as<int32_t>(); vd.stats = dstats.as<int32_t>(); vd.workspace = dws.h;
+    vd.voxel_size = o.voxel_size; vd.max_voxels = max_voxels; vd.capacity = max_voxels;
+    const auto run = [&] { return s2m2_voxel(&vd, c.s) == 0 ? 0 : fail_lib("s2m2_voxel failed"); };
+    if (run()) return 1;
+    HIP_OK(hipStreamSynchronize(c.s), "s2m2_voxel");
+    std::vector<int32_t> hcount(m.B), hstats((size_t)m.B * 4);
+    HIP_OK(hipMemcpy(hcount.data(), dcount.h, m.B * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+    HIP_OK(hipMemcpy(hstats.data(), dstats.h, hstats.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+    std::vector<unsigned char> hrec;
+    for (int b = 0; b < m.B; ++b) {
+        if (hstats[(size_t)b * 4 + 2] != 0) return fail("--voxel: more voxels than --voxel-max (default: a quarter of the pixels): give a larger one");
+        hrec.resize((size_t)hcount[b] * 16);
+        HIP_OK(hipMemcpy(hrec.data(), drec.as<char>() + (size_t)b * max_voxels * 16, hrec.size(), hipMemcpyDeviceToHost), "download");
+        if (!write_ply(pair_path(o.voxel_ply_path, m.B, b), hrec.data(), hcount[b])) return fail("cannot write the voxel PLY file");
+    }
+    if (o.repeat > 0) {
+        float ms = 0.f;
+        if (time_calls(c.s, o.repeat, run, &ms, "timed voxel runs")) return 1;
+        printf("{\"voxel_points\": %d, \"voxel_kept\": %d, \"voxel_out_of_range\": %d, \"repeat\": %d, \"voxel_us_per_pair\": %.2f}\n", hcount[0],
+               hstats[0], hstats[1], o.repeat, 1000.f * ms / o.repeat / m.B);
+    }
+    return 0;
+}
+
 // --register (K21): the depth map, the winners' indices and their colours in the target camera
 static int stage_register(Context& c) {
     const Options& o = c.o;
@@ -407,12 +456,13 @@ int main(int argc, char** argv) {
         printf("{\"B\": %d, \"H\": %d, \"W\": %d, \"repeat\": %d, \"ms_per_pair\": %.4f}\n", m.B, m.H, m.W, o.repeat, ms / o.repeat / m.B);
     }
     const bool cloud = o.calib_path && (o.ply_path || o.mesh_path);
-    if (o.min_size_arg || cloud || o.register_cam) {                 // the calibration: once, in front of the first 3D stage
+    if (o.min_size_arg || cloud || o.register_cam || o.voxel_arg) {                 // the calibration: once, in front of the first 3D stage
         if (!read_calib(o.calib_path, c.cal)) return fail("--calib: cannot read cam0 and baseline from the file");
         if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
     }
     if (o.min_size_arg && stage_segment(c)) return 1;
     if (cloud && stage_cloud(c)) return 1;
+    if (o.voxel_arg && stage_voxel(c)) return 1;
     if (o.register_cam && stage_register(c)) return 1;
     if (o.gt_path && stage_eval(c, g)) return 1;
     return 0;

@@ -17,7 +17,7 @@ inline const char* const USAGE =
     "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
     "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
     "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]] "
-    "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]";
 
 // ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
@@ -30,11 +30,12 @@ struct Options {
     const char* max_jump_arg = nullptr;
     const char *register_cam = nullptr, *reg_depth_path = nullptr, *reg_image_path = nullptr, *reg_index_path = nullptr, *splat_arg = nullptr;
     const char *min_size_arg = nullptr, *labels_path = nullptr, *segmask_path = nullptr;
+    const char *voxel_arg = nullptr, *voxel_ply_path = nullptr, *voxel_max_arg = nullptr;
     const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr, *gt_min_arg = nullptr;
 
     int repeat = 0, splat = 2, unfiltered = 0;
-    long long min_size = 1;
-    double max_jump = 1.0;
+    long long min_size = 1, voxel_max = 0;               // voxel_max 0: a quarter of the image's pixels
+    double max_jump = 1.0, voxel_size = 0.0;
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5, gt_min = 0.0;
 };
 
@@ -62,6 +63,9 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--min-size", true, &Options::min_size_arg},
     {"--labels", true, &Options::labels_path},
     {"--segment-mask", true, &Options::segmask_path},
+    {"--voxel", true, &Options::voxel_arg},
+    {"--voxel-ply", true, &Options::voxel_ply_path},
+    {"--voxel-max", true, &Options::voxel_max_arg},
     {"--depth-trunc", true, &Options::depth_trunc_arg},
     {"--depth-scale", true, &Options::depth_scale_arg},
     {"--conf-min", true, &Options::conf_min_arg},
@@ -112,8 +116,21 @@ inline const char* check_options(Options& o) {
         o.min_size = strtoll(o.min_size_arg, &end, 10);
         if (end == o.min_size_arg || *end || o.min_size < 1 || o.min_size > (1LL << 30)) return "--min-size: an integer >= 1 (at most 2^30)";
     }
-    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && (o.calib_path == nullptr) != (o.ply_path == nullptr)) return "--calib and --ply come together";
-    if ((o.register_cam || o.min_size_arg) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
+    if ((o.voxel_arg == nullptr) != (o.voxel_ply_path == nullptr)) return "--voxel and --voxel-ply come together";
+    if (o.voxel_max_arg && !o.voxel_arg) return "--voxel-max needs --voxel";
+    if (o.voxel_arg && !o.calib_path) return "--voxel needs --calib";
+    if (o.voxel_arg) {
+        char* end = nullptr;
+        o.voxel_size = strtod(o.voxel_arg, &end);
+        if (end == o.voxel_arg || *end || !(o.voxel_size > 0.0) || !isfinite(o.voxel_size)) return "--voxel: a number > 0";
+    }
+    if (o.voxel_max_arg) {
+        char* end = nullptr;
+        o.voxel_max = strtoll(o.voxel_max_arg, &end, 10);
+        if (end == o.voxel_max_arg || *end || o.voxel_max < 1 || o.voxel_max > (1LL << 29)) return "--voxel-max: an integer >= 1 (at most 2^29)";
+    }
+    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && !o.voxel_arg && (o.calib_path == nullptr) != (o.ply_path == nullptr)) return "--calib and --ply come together";
+    if ((o.register_cam || o.min_size_arg || o.voxel_arg) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
     if (o.max_jump_arg && !o.mesh_path && !o.min_size_arg) return "--max-jump needs --mesh or --min-size";
     if (o.max_jump_arg) {
         char* end = nullptr;

@@ -17,6 +17,10 @@ the visibility of every left pixel from that camera (the rule: include/s2m2_hip.
 "joined" rule on the 4-neighbourhood, their sizes, and the disparity map with the components below ``min_size`` removed (the rule:
 include/s2m2_hip.h, K22).  Four launches, no synchronisation, capturable.
 
+``voxelize`` (K23, ``s2m2_voxel``) is the step every consumer of the cloud takes first: one point per occupied cell of a voxel grid, the centroid
+and the mean colour of the kept points in it, in K15's record format and in the raster order of the cells' first points (the rule:
+include/s2m2_hip.h, K23).  Four launches (five with the per-pixel index), no synchronisation, capturable, bit-reproducible.
+
 A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
@@ -348,3 +352,63 @@ def segment(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: int
                 max_jump=max_jump, min_size=min_size, workspace=workspace, label=label, size=size, mask=mask,
                 disp_out=out, stats=stats)
     return Segments(out, mask, label, size, stats)
+
+
+class VoxelCloud(PointCloud):
+    """What ``voxelize`` returns: a ``PointCloud`` whose records are voxels -- ``records`` (B, capacity, 4) int32 in the raster order of the
+    voxels' first points, ``count`` (B) int32 (the true number of voxels, also above capacity) -- plus ``weights_buf`` (B, capacity) int32 or
+    None (points per voxel), ``index`` (B,1,H,W) int32 or None (the record rank of every pixel's voxel, -1: not kept or dropped) and ``stats``
+    (B,4) int32: kept points, points dropped out of range, points dropped because the table was full, voxels."""
+
+    def __init__(self, records: torch.Tensor, count: torch.Tensor, weights_buf: Optional[torch.Tensor], index: Optional[torch.Tensor],
+                 stats: torch.Tensor):
+        super().__init__(records, count)
+        self.weights_buf, self.index, self.stats = weights_buf, index, stats
+
+    def weights(self, b: int = 0) -> torch.Tensor:
+        """(n) int32: the points of every stored voxel of pair b"""
+        if self.weights_buf is None:
+            raise ValueError("VoxelCloud.weights: voxelize was called with want_weights=False")
+        return self.weights_buf[b, :self.size(b)]
+
+    def complete(self, b: int = 0) -> bool:
+        """no point of pair b was dropped because the table was full -- reads ``stats`` on the host (synchronises).  False: the records of
+        this pair are unspecified; call again with a larger ``max_voxels``"""
+        return int(self.stats[b, 2].item()) == 0
+
+
+def voxelize(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, cx: float, cy: float,
+             baseline: float, doffs: float = 0.0, voxel_size: float, max_voxels: Optional[int] = None, capacity: Optional[int] = None,
+             fy: Optional[float] = None, depth_scale: float = 1000.0, depth_trunc: Optional[float] = None, conf_min: float = 0.1,
+             occ_min: float = 0.5, filtered: bool = True, want_weights: bool = True, want_index: bool = False) -> VoxelCloud:
+    """``reproject``'s operands and conventions -> VoxelCloud (K23, ``s2m2_voxel``): the kept points fall into the cells of a grid of
+    ``voxel_size`` (the unit of z) anchored at the camera origin, and every occupied cell gives one record: the centroid and the mean colour.
+    Points beyond 2^20 cells from the origin on any axis are dropped and counted (``stats[:, 1]``): with ``depth_trunc=None`` those are the
+    d <= 0 pixels K15 keeps at z = 1e9 / depth_scale.  Only allocates: no synchronisation, capturable.
+
+    ``max_voxels`` (distinct voxels a pair may have) and ``capacity`` (records stored per pair) default to H*W // 4.  Memory: the hash table
+    takes 64 bytes per slot and has 2 * max_voxels slots rounded up to a power of two -- 32 to 64 bytes per PIXEL at the default, 64 MiB at
+    1216x1024 --, the slot plane 4 bytes per pixel, records and weights 20 bytes per unit of capacity.  A pair with more voxels than
+    ``max_voxels`` drops points: ``complete(b)`` tells.
+
+    Composition with K22: ``s = segment(...)`` then ``voxelize(s.disp, occ, conf, image, ..., filtered=False)`` downsamples exactly the
+    surviving pixels (pass a real ``depth_trunc``, as for ``reproject`` behind ``segment``)."""
+    B = disp.shape[0]
+    H, W = image.shape[-2:]
+    mv = max(1, H * W // 4) if max_voxels is None else max_voxels
+    cap = max(1, H * W // 4) if capacity is None else int(capacity)
+    if cap < 0:
+        raise ValueError("voxelize: negative capacity")
+    if int(mv) != mv or not 1 <= mv <= 1 << 29:
+        raise ValueError(f"voxelize: max_voxels must be an integer in 1..2^29, got {max_voxels}")
+    mv = int(mv)
+    dev = disp.device
+    workspace = torch.empty((hip.voxel_workspace_bytes(B, H, W, mv),), device=dev, dtype=torch.uint8)
+    records = torch.empty((B, cap, 4), device=dev, dtype=torch.int32)
+    count = torch.empty((B,), device=dev, dtype=torch.int32)
+    weights = torch.empty((B, cap), device=dev, dtype=torch.int32) if want_weights else None
+    index = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_index else None
+    stats = torch.empty((B, 4), device=dev, dtype=torch.int32)
+    hip.voxel(disp, occ, conf, image, **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
+              voxel_size=voxel_size, max_voxels=mv, workspace=workspace, records=records, weights=weights, count=count, index=index, stats=stats)
+    return VoxelCloud(records, count, weights, index, stats)

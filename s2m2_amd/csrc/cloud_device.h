@@ -1,7 +1,7 @@
-// Device functions shared by K15 (cloud.hip) and K20 (mesh.hip): the per-pixel chain of include/s2m2_hip.h (keep, z, x, y, colour bytes) and the
-// record.  Both kernels compile THESE functions, so that the vertex records of s2m2_mesh are byte-identical to the records of s2m2_cloud
-// whatever the compiler does with the arithmetic.  The pixel -> thread map, the loads and stores of a thread's four pixels, the block
-// reductions and the rank step are raster_tiles.h's, which K18 shares.
+// Device functions shared by K15 (cloud.hip), K20 (mesh.hip) and K23 (voxel.hip): the per-pixel chain of include/s2m2_hip.h (keep, z, x, y,
+// colour bytes) and the record.  All three compile THESE functions, so that the vertex records of s2m2_mesh are byte-identical to the records
+// of s2m2_cloud, and the points s2m2_voxel sums are K15's, whatever the compiler does with the arithmetic.  The pixel -> thread map, the loads
+// and stores of a thread's four pixels, the block reductions and the rank step are raster_tiles.h's, which K18 shares.
 #pragma once
 #include "raster_tiles.h"
 
@@ -63,14 +63,26 @@ template <> __device__ __forceinline__ unsigned cloud_byte<unsigned char>(unsign
 template <> __device__ __forceinline__ unsigned cloud_byte<float>(float x) { return (unsigned)__float2int_rn(fminf(fmaxf(x, 0.f), 255.f)); }
 template <> __device__ __forceinline__ unsigned cloud_byte<half_t>(half_t x) { return cloud_byte<float>((float)x); }
 
-// the 16-byte record of the kept pixel (v, u) of one pair: img = the pair's planar image, plane = H * W, z = the pixel's z
+// x and y of the kept pixel (v, u) at depth z, and its colour bytes (img = the pair's planar image, plane = H * W): the arithmetic of the
+// record, which K23 (voxel.hip) quantises and sums instead of storing
+__device__ __forceinline__ void cloud_xy(const CloudParams& p, int v, int u, float z, float& x, float& y) {
+    const float fv = (float)v - p.cy;
+    x = ((float)u - p.cx) * z / p.fx;
+    y = fv * z / p.fy;
+}
+template <typename IT>
+__device__ __forceinline__ void cloud_colour(const CloudParams& p, const IT* img, size_t plane, int v, int u, unsigned& cr, unsigned& cg, unsigned& cb) {
+    const size_t px = (size_t)v * p.W + u;
+    cr = cloud_byte<IT>(img[px]); cg = cloud_byte<IT>(img[plane + px]); cb = cloud_byte<IT>(img[2 * plane + px]);
+}
+
+// the 16-byte record of the kept pixel (v, u) of one pair, z = the pixel's z
 template <typename IT>
 __device__ __forceinline__ uint4_t cloud_record(const CloudParams& p, const IT* img, size_t plane, int v, int u, float z) {
-    const size_t px = (size_t)v * p.W + u;
-    const unsigned cr = cloud_byte<IT>(img[px]), cg = cloud_byte<IT>(img[plane + px]), cb = cloud_byte<IT>(img[2 * plane + px]);
-    const float fv = (float)v - p.cy;
-    const float x = ((float)u - p.cx) * z / p.fx;
-    const float y = fv * z / p.fy;
+    unsigned cr, cg, cb;
+    cloud_colour<IT>(p, img, plane, v, u, cr, cg, cb);
+    float x, y;
+    cloud_xy(p, v, u, z, x, y);
     uint4_t o = {__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, y), __builtin_bit_cast(unsigned, z),
                  cr | (cg << 8) | (cb << 16) | 0xff000000u};
     return o;

@@ -142,6 +142,12 @@ class SegmentDesc(ctypes.Structure):
                 ("max_jump", ctypes.c_double), ("min_size", _ll)]
 
 
+class VoxelDesc(ctypes.Structure):
+    """mirror of s2m2_voxel_desc (include/s2m2_hip.h): K23, voxel-grid downsampling of the point cloud"""
+    _fields_ = [("cloud", CloudDesc), ("records", _vp), ("weights", _vp), ("count", _vp), ("index", _vp), ("stats", _vp), ("workspace", _vp),
+                ("voxel_size", ctypes.c_double), ("max_voxels", _ll), ("capacity", _ll)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -259,6 +265,10 @@ SIGNATURES = {
     "s2m2_segment_tile_rows": (_i, [_i, _i]),
     "s2m2_segment_tile_cols": (_i, [_i, _i]),
     "s2m2_segment": (_i, [ctypes.POINTER(SegmentDesc), _vp]),
+    "s2m2_voxel_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _ll]),
+    "s2m2_voxel_tile_rows": (_i, [_i, _i]),
+    "s2m2_voxel_home_slot": (_ll, [_i, _i, _i, _ll]),
+    "s2m2_voxel": (_i, [ctypes.POINTER(VoxelDesc), _vp]),
 }
 
 
@@ -1364,3 +1374,5 @@ from .hip_mesh import mesh, mesh_tile_rows, mesh_workspace_bytes  # noqa: E402,F
 from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
 # K22 (s2m2_segment): likewise, from hip_segment.py
 from .hip_segment import segment, segment_tile, segment_workspace_bytes  # noqa: E402,F401
+# K23 (s2m2_voxel): likewise, from hip_voxel.py
+from .hip_voxel import voxel, voxel_home_slot, voxel_slots, voxel_tile_rows, voxel_workspace_bytes  # noqa: E402,F401

@@ -11,6 +11,8 @@ image_utils.py) -- SURVEY.md section 8f rows 1-2: same names, arguments and retu
   pixels of similar disparity (HIP kernels ``s2m2_mesh``; ``s2m2_amd.cloud.mesh``)
 * ``filter_speckles``      no counterpart in the reference (its demos leave outlier removal to open3d on the host): ``get_pointcloud``'s
   conventions -> the disparity with the small connected components removed (HIP kernels ``s2m2_segment``; ``s2m2_amd.cloud.segment``)
+* ``voxel_down_sample``    no counterpart in the reference (its 3D demos hand the full cloud to open3d on the host): ``get_pointcloud``'s
+  arguments -> one point per occupied voxel, the centroid and the mean colour (HIP kernels ``s2m2_voxel``; ``s2m2_amd.cloud.voxelize``)
 * ``compute_confidence_scores``  the calibration objective (calibration/base.py:15-36 called 20 x 5 times one pair at a time by
   calibration/cem.py:66-72) for a whole population of rectified pairs at once: one batched forward, or sharded over the ranks of a
   ``torch.distributed`` group
@@ -184,6 +186,22 @@ def get_mesh(rgb, disp, calib, depth_trunc=None, max_jump=1.0):
         return cloud.mesh(disp_t, disp_t, disp_t, image, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
                           baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
                           max_jump=max_jump)
+
+
+def voxel_down_sample(rgb, disp, calib, voxel_size, depth_trunc=None):
+    """``get_pointcloud``'s arguments and conventions (halved intrinsics, fx for both focal lengths, no confidence filter) -> a
+    ``cloud.VoxelCloud`` on the device: one point per occupied cell of a grid of ``voxel_size`` (the unit of z: metres with a Middlebury
+    calibration) anchored at the camera, the centroid and the mean colour of the cell's points, with the number of points per cell."""
+    from . import cloud
+    disp_t = torch.as_tensor(disp)
+    device = disp_t.device if disp_t.is_cuda else torch.device("cuda")
+    disp_t = disp_t.to(device=device, dtype=torch.float32).contiguous()[None, None]
+    image = torch.as_tensor(rgb).to(device).permute(2, 0, 1).contiguous()[None]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(device):
+        return cloud.voxelize(disp_t, disp_t, disp_t, image, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
+                              baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
+                              voxel_size=voxel_size)
 
 
 def filter_speckles(disp, calib, depth_trunc=None, max_jump=1.0, min_size=100):
