@@ -2,7 +2,9 @@
 //
 // Replaces every stride-1 nn.Conv2d / nn.ConvTranspose2d / nn.Linear call site of the hot path outside the CNN backbone
 // (reference: refinenet.py:14-20,47-57,87-122; attentions.py:24-28,71-74,239-241,269-275; feature_fusion.py:15-21;
-// stacked_MRT.py:22-34; unet.py:25-37; submodules.py:104-108,127-135; s2m2.py:65-67) together with the elementwise
+// stacked_MRT.py:22-34; unet.py:25-37; submodules.py:104-108,127-135; s2m2.py:65-67) AND the backbone's strided layers, which the
+// engine sends through the v1 tiles of this file with stride = 2: cnn_backbone.conv2_down.0 (3x3, C -> C, submodules.py:86) in both
+// modes and conv1_down.0 (5x5, 16 -> 64, submodules.py:74) in fp32 (fp16: K12) -- together with the elementwise
 // ops PyTorch runs as separate kernels around them: torch.cat of the inputs, bias add, GELU / ReLU / sigmoid / tanh,
 // residual add, the ConvGRU gate arithmetic (refinenet.py:24-34) and the FeatureFusion gate mix (feature_fusion.py:24-31).
 //

@@ -59,6 +59,14 @@ conv N=1 H=256 W=304 Cin=512 Cout=128 KH=1 KW=1 stride=1 epi=0 korder=0 pool2=0 
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=3 korder=2 pool2=0 ln=0 shuffle2=0 tile=4 fp16=1 -> E:conv2d: K order 2 with 128-pixel blocks takes one-operand epilogues only (epi=3 has two)
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=1 KW=1 stride=1 epi=0 korder=0 pool2=0 ln=1 shuffle2=0 tile=7 fp16=1 -> E:conv2d: tile 7 has no pre-LayerNorm variant (2, 3, 6, 20 do)
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=28 fp16=1 -> E:conv2d: unknown tile id 28
+conv N=1 H=33 W=61 Cin=128 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=1 -> igemm 64 64 2 8 1 4 0
+conv N=2 H=1024 W=1216 Cin=16 Cout=64 KH=5 KW=5 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=0 -> igemm 64 64 2 4 1 4 0
+conv N=1 H=33 W=61 Cin=16 Cout=64 KH=5 KW=5 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=0 -> igemm 64 64 2 4 1 4 0
+conv N=2 H=256 W=304 Cin=32 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=1 -> igemm 128 128 2 4 1 8 0
+conv N=2 H=256 W=304 Cin=32 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=0 -> igemm 128 128 2 4 1 8 0
+conv N=2 H=256 W=296 Cin=32 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=1 -> igemm 64 64 2 4 1 4 0
+conv N=2 H=256 W=296 Cin=32 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=0 -> igemm 64 64 2 4 1 4 0
+conv N=1 H=33 W=61 Cin=32 Cout=64 KH=1 KW=1 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=14 fp16=1 -> E:conv2d: the pointwise kernel needs a 1x1 stride-1 layer
 chain C=128 dtype=1 rows=155648 nstage=2 nfan=0 weight_frag=1 xcd_group_rows=0 -> direct BM=64 NW=4 WP=0 xcd=0
 chain C=128 dtype=1 rows=38912 nstage=0 nfan=1 weight_frag=1 xcd_group_rows=0 -> fan_only BM=64 NW=4 WP=0 xcd=0
 chain C=128 dtype=1 rows=9728 nstage=0 nfan=2 weight_frag=1 xcd_group_rows=0 -> fan_only BM=32 NW=4 WP=0 xcd=0
