@@ -1166,6 +1166,91 @@ int s2m2_voxel_tile_rows(int H, int W);                    /* rows of a raster t
 long long s2m2_voxel_home_slot(int ix, int iy, int iz, long long slots);
 int s2m2_voxel(const s2m2_voxel_desc* desc, void* stream);
 
+/*
+ * K24 -- depth maps of a moving rig fused into a truncated signed distance (TSDF) volume, and the surface of that volume as a point cloud (what
+ *   open3d's TSDFVolume.integrate / extract_point_cloud do on the host).  The first stage that carries state from one pair to the next.  Like
+ *   K18 and K20 to K23 it has no counterpart in the reference: the semantics are defined here and pinned by the numpy oracle of
+ *   tests/tsdf_oracle.py.  Still S2M2_ABI_VERSION 800: the entry points are added, nothing changes in place.
+ *   The volume: a dense grid of Nx * Ny * Nz voxels in caller-owned device memory, 16 bytes per voxel, 16-byte aligned:
+ *       { float tsdf; int32 weight; uint16 r, g, b, pad; }        voxel (i, j, k) at lin = (k * Ny + j) * Nx + i;   Nx * Ny * Nz < 2^29
+ *     r, g, b are the colour as fixed-point 8.8 values; pad is kept as it is.  An all-zero buffer is an empty volume; there is no clear entry
+ *     point (hipMemsetAsync is the reset).  origin is the centre of voxel (0,0,0) in the world frame; voxel_size and trunc are in the unit of
+ *     z (i.e. after depth_scale).
+ *   s2m2_tsdf_integrate.  `cloud` holds the INPUT fields of s2m2_cloud, with their meaning, as s2m2_register takes them: the B padded maps,
+ *     the unpadded image (always required here), H, W, Hp, Wp (fused crop), camera and filter parameters, unfiltered.  Its output fields are
+ *     IGNORED.  poses is a DEVICE buffer (B, 12) fp32, row-major [R | t] per pair: p_cam = R p_world + t (t in the unit of z).  A captured graph
+ *     serves the next frames once that buffer (and the maps) are rewritten; no host pointer reaches a kernel.  The intrinsics, origin,
+ *     voxel_size and trunc are converted to fp32 once on the host.
+ *     per voxel (i, j, k), for the pairs b = 0 .. B-1 of the call in that order, all in fp32, every operation ONE IEEE rounding, nothing fused
+ *     into a multiply-add:
+ *       x = ox + (float)i * vs;   y = oy + (float)j * vs;   z = oz + (float)k * vs
+ *       X = ((r00*x + r01*y) + r02*z) + tx;   Y = ((r10*x + r11*y) + r12*z) + ty;   Z = ((r20*x + r21*y) + r22*z) + tz        (K21's form)
+ *       skip unless Z > 0 and Z is finite
+ *       up = (fx * X) / Z + cx;   vp = (fy * Y) / Z + cy;   fu = rintf(up);   fv = rintf(vp)                                  (half to even)
+ *       skip unless fu >= 0 && fu < W && fv >= 0 && fv < H     (float comparisons, before any conversion to int: a NaN skips)
+ *       pixel (fv, fu) of the UNPADDED image: keep, z_pix and the colour bytes are K15's (the same device functions, fused crop)
+ *       skip unless keep
+ *       sdf = z_pix - Z;   skip unless sdf >= -trunc;   skip if !carve && sdf > trunc
+ *       d = fminf(sdf / trunc, 1.0f)
+ *       Wf = (float)weight
+ *       tsdf   = (tsdf * Wf + d) / (Wf + 1.0f)                                             (three roundings: mul, add, div)
+ *       colour = (colour * weight + (byte << 8) + ((weight + 1) >> 1)) / (weight + 1)      per channel, unsigned 32-bit integers
+ *       weight = min(weight + 1, max_weight)
+ *     With weight <= 32767 a colour stays <= 65280 and the numerator below 2^32.  A voxel that no pair of the call updates is neither written
+ *     nor changed, whatever its bytes were.  A voxel is read and written at most once per call, however large B is: the loop over the pairs
+ *     runs inside the thread that owns the voxel.  One launch, no atomics, no workspace: bit-reproducible.
+ *     Errors (before any device call): null descriptor; everything s2m2_cloud checks on its inputs (maps, extents, fx, fy, depth_scale, image
+ *     dtype, alignment); a null volume, poses or image; a volume not 16-byte or poses not 4-byte aligned; non-positive dims or Nx*Ny*Nz >=
+ *     2^29; voxel_size or trunc not finite or <= 0 as fp32; a non-finite origin; max_weight outside 1 .. 32767.
+ *   s2m2_tsdf_extract.  A voxel is OBSERVED iff weight >= min_weight (min_weight >= 1).  For every observed voxel v0 = (i, j, k) in ascending
+ *     lin, and for the axes x, y, z in that order: v1 is v0's neighbour at +1 along the axis, t0 and t1 their tsdf, and a point is emitted iff
+ *     v1 is inside the grid and observed and (t0 < 0) != (t1 < 0).  Per emitted point, in fp32 with one rounding per operation:
+ *       s = t0 / (t0 - t1);   the coordinate along the axis is (o_a + (float)i_a * vs) + s * vs, the other two are the centre of v0
+ *       sel = fabsf(t1) < fabsf(t0) ? v1 : v0;   colour byte = (c_sel + 128) >> 8;   a = 255
+ *       gradient g_b = tp - tm per axis b: tp / tm are the tsdf of sel's +b / -b neighbour where that neighbour is inside the grid and
+ *       observed, t_sel otherwise.  Unnormalised; it points from the surface to free space.
+ *     outputs, each optional (NULL), at least one:
+ *       records    (capacity) K15's 16-byte records (16-byte aligned)
+ *       gradients  (capacity, 3) fp32
+ *       count      one int32: the true number of points, also above `capacity`; points of rank >= capacity are not stored and the rest of both
+ *                  buffers is left untouched
+ *     workspace: >= s2m2_tsdf_workspace_bytes(Nx, Ny, Nz) bytes, 4-byte aligned, always required.  Two launches as in K15, no host step, no
+ *     atomics: a block counts the points of a tile of s2m2_tsdf_tile_voxels(Nx, Ny, Nz) consecutive voxels, then the blocks rank and store.
+ *     Bit-reproducible.
+ *     Errors (before any device call): null descriptor; a null or misaligned volume; non-positive dims or Nx*Ny*Nz >= 2^29; voxel_size not
+ *     finite or <= 0 as fp32; a non-finite origin; min_weight < 1; no output requested; negative capacity; records and gradients both NULL
+ *     with capacity > 0; records not 16-byte aligned; gradients or count not 4-byte aligned; a missing or misaligned workspace.
+ *   Launch plans: s2m2_tsdf_integrate and s2m2_tsdf_extract are NOT recorded.  Called while the calling thread records a plan they fail with an
+ *   error and launch nothing; the stage runs after s2m2_plan_run / s2m2_engine_run on the same stream.  Safe under stream capture (hipGraph).
+ */
+typedef struct s2m2_tsdf_desc {
+    s2m2_cloud_desc cloud;
+    void*          volume;     /* Nx * Ny * Nz voxels of 16 bytes, 16-byte aligned */
+    const float*   poses;      /* DEVICE (B, 12) fp32: [R | t] row-major per pair, world -> camera */
+    int            Nx, Ny, Nz;
+    int            max_weight; /* 1 .. 32767 */
+    int            carve;      /* != 0: voxels in front of the band (sdf > trunc) are updated with d = 1 */
+    double         origin[3];  /* centre of voxel (0,0,0) */
+    double         voxel_size; /* > 0, in the unit of z */
+    double         trunc;      /* > 0, in the unit of z */
+} s2m2_tsdf_desc;
+typedef struct s2m2_tsdf_extract_desc {
+    const void*    volume;
+    void*          records;
+    float*         gradients;
+    int32_t*       count;
+    void*          workspace;
+    int            Nx, Ny, Nz;
+    int            min_weight; /* >= 1 */
+    long long      capacity;   /* records (and gradients) */
+    double         origin[3];
+    double         voxel_size;
+} s2m2_tsdf_extract_desc;
+size_t s2m2_tsdf_workspace_bytes(int Nx, int Ny, int Nz);   /* 0: bad dims */
+int s2m2_tsdf_tile_voxels(int Nx, int Ny, int Nz);          /* consecutive voxels of one extraction tile, so that tests can aim at its borders; 0: bad dims */
+int s2m2_tsdf_integrate(const s2m2_tsdf_desc* desc, void* stream);
+int s2m2_tsdf_extract(const s2m2_tsdf_extract_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

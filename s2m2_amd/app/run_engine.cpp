@@ -54,6 +54,17 @@
 //   bad_<t>, a50, a90, a95, a99, density, "kept": {the same after the filter}}, ...]}; a ratio of an empty set (0 / 0) or an infinite quantile
 //   is written as null.  The ground-truth files are parsed before the engine is loaded; their extents are compared with the engine's right after.
 // With --repeat the stage is timed (HIP events around N calls) and its microseconds per pair printed on a line of its own.
+//
+// A stream of pairs from a moving rig fused into one TSDF volume (s2m2_tsdf_integrate / s2m2_tsdf_extract), a mode of its own:
+//   s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T]
+//                   [--tsdf-min-weight N] [--tsdf-carve] --calib calib.txt --tsdf-ply OUT.ply
+// Every line of LIST names LEFT.f32 RIGHT.f32 IMAGE.u8 (as above; raw uint8 (1,3,H,W) for the colours) and the twelve numbers of the pose
+//   [R | t], row-major, world -> camera, t in the unit of z; empty lines and lines that start with # are skipped.  The engine (one pair per run)
+//   runs per line and the maps are fused behind it; one extraction follows the last line.  --tsdf-dims: the voxels; --tsdf-voxel: their
+//   size and --tsdf-origin the centre of voxel (0,0,0), both in the unit of z; --tsdf-trunc: the truncation distance (default 4 VS);
+//   --tsdf-min-weight: the frames a voxel needs to count as observed (default 1); --tsdf-carve: also free space in front of the band is
+//   fused.  Honours --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered.  --tsdf-ply: the surface points in --ply's layout.
+//   LIST is parsed before the engine is loaded.  Prints {"tsdf_frames", "tsdf_points"} on a line of its own.
 #include <hip/hip_runtime.h>
 
 #include <functional>
@@ -395,10 +406,80 @@ static int stage_eval(Context& c, const GroundTruth& g) {
     return 0;
 }
 
+// --tsdf-frames (K24): the engine per line of LIST, the maps fused into the volume behind it, one extraction at the end
+static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& m, const std::vector<TsdfFrame>& frames, hipStream_t s) {
+    if (m.B != 1) return fail("--tsdf-frames needs an engine of one pair per run");
+    if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
+    Calib cal;
+    if (!read_calib(o.calib_path, cal)) return fail("--calib: cannot read cam0 and baseline from the file");
+    const size_t img = (size_t)3 * m.H * m.W, map = (size_t)m.out_h * m.out_w;
+    const size_t voxels = (size_t)o.tsdf_dims[0] * o.tsdf_dims[1] * o.tsdf_dims[2];
+    const size_t ws_bytes = s2m2_tsdf_workspace_bytes(o.tsdf_dims[0], o.tsdf_dims[1], o.tsdf_dims[2]);
+    if (ws_bytes == 0) return fail("--tsdf-dims: too large");
+    DeviceBuffer dl, dr, dimage, dout[3], dvol, dpose, dws, dcount, drec;
+    if (DeviceBuffer::make(dl, img * sizeof(float)) || DeviceBuffer::make(dr, img * sizeof(float)) || DeviceBuffer::make(dimage, img) ||
+        DeviceBuffer::make(dvol, voxels * 16) || DeviceBuffer::make(dpose, 12 * sizeof(float)) || DeviceBuffer::make(dws, ws_bytes) ||
+        DeviceBuffer::make(dcount, sizeof(int32_t)))
+        return 1;
+    for (auto& p : dout)
+        if (DeviceBuffer::make(p, map * sizeof(float))) return 1;
+    HIP_OK(hipMemsetAsync(dvol.h, 0, voxels * 16, s), "hipMemsetAsync");
+    s2m2_tsdf_desc td;
+    memset(&td, 0, sizeof td);
+    fill_cloud_inputs(td.cloud, m, dout[0].as<float>(), dout[1].as<float>(), dout[2].as<float>(), dimage.h, 2, o.unfiltered, cal, o);
+    td.volume = dvol.h; td.poses = dpose.as<float>();
+    td.Nx = o.tsdf_dims[0]; td.Ny = o.tsdf_dims[1]; td.Nz = o.tsdf_dims[2];
+    td.max_weight = 32767; td.carve = o.tsdf_carve;
+    memcpy(td.origin, o.tsdf_origin, sizeof td.origin);
+    td.voxel_size = o.tsdf_voxel; td.trunc = o.tsdf_trunc;
+    std::vector<float> hl(img), hr(img);
+    std::vector<unsigned char> hi(img);
+    for (const TsdfFrame& fr : frames) {
+        if (!read_raw(fr.left.c_str(), hl) || !read_raw(fr.right.c_str(), hr) || !read_raw_u8(fr.image.c_str(), hi)) {
+            fprintf(stderr, "s2m2_run_engine: --tsdf-frames: %s and %s must be raw float32 and %s raw uint8 (1,3,%d,%d) files\n", fr.left.c_str(),
+                    fr.right.c_str(), fr.image.c_str(), m.H, m.W);
+            return 1;
+        }
+        HIP_OK(hipMemcpy(dl.h, hl.data(), img * sizeof(float), hipMemcpyHostToDevice), "upload");
+        HIP_OK(hipMemcpy(dr.h, hr.data(), img * sizeof(float), hipMemcpyHostToDevice), "upload");
+        HIP_OK(hipMemcpy(dimage.h, hi.data(), img, hipMemcpyHostToDevice), "upload");
+        HIP_OK(hipMemcpy(dpose.h, fr.pose, sizeof fr.pose, hipMemcpyHostToDevice), "upload");
+        if (s2m2_engine_run(eng, dl.h, dr.h, dout[0].as<float>(), dout[1].as<float>(), dout[2].as<float>(), s) != 0) return fail_lib("engine run failed");
+        if (s2m2_tsdf_integrate(&td, s) != 0) return fail_lib("s2m2_tsdf_integrate failed");
+        HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_integrate");       // the next line overwrites the inputs
+    }
+    s2m2_tsdf_extract_desc ed;
+    memset(&ed, 0, sizeof ed);
+    ed.volume = dvol.h; ed.count = dcount.as<int32_t>(); ed.workspace = dws.h;
+    ed.Nx = td.Nx; ed.Ny = td.Ny; ed.Nz = td.Nz; ed.min_weight = o.tsdf_min_weight;
+    memcpy(ed.origin, o.tsdf_origin, sizeof ed.origin);
+    ed.voxel_size = o.tsdf_voxel;
+    int32_t n = 0;                                                           // the count first, then records for exactly that many points
+    if (s2m2_tsdf_extract(&ed, s) != 0) return fail_lib("s2m2_tsdf_extract failed");
+    HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_extract");
+    HIP_OK(hipMemcpy(&n, dcount.h, sizeof n, hipMemcpyDeviceToHost), "download");
+    std::vector<unsigned char> hrec((size_t)n * 16);
+    if (n > 0) {
+        if (DeviceBuffer::make(drec, hrec.size())) return 1;
+        ed.records = drec.h; ed.capacity = n;
+        if (s2m2_tsdf_extract(&ed, s) != 0) return fail_lib("s2m2_tsdf_extract failed");
+        HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_extract");
+        HIP_OK(hipMemcpy(hrec.data(), drec.h, hrec.size(), hipMemcpyDeviceToHost), "download");
+    }
+    if (!write_ply(o.tsdf_ply_path, hrec.data(), n)) return fail("cannot write the TSDF PLY file");
+    printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d}\n", frames.size(), n);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     Options o;
     if (!parse_options(argc, argv, o)) return fail(USAGE);
     if (const char* msg = check_options(o)) return fail(msg);
+    std::vector<TsdfFrame> tsdf_frames;                   // LIST is parsed here, before the engine is loaded
+    if (o.tsdf_frames_path) {
+        const std::string msg = read_tsdf_frames(o.tsdf_frames_path, tsdf_frames);
+        if (!msg.empty()) return fail(msg.c_str());
+    }
     // the ground truth is parsed and validated here, before the engine is loaded and anything touches the device
     GroundTruth g;
     const std::string gt_msg = read_ground_truth(o, g);
@@ -414,6 +495,10 @@ int main(int argc, char** argv) {
     s2m2_engine_info& m = c.m;
     s2m2_engine_meta(eng.h, &m);
     if (m.image_dtype != S2M2_F32) return fail("this program feeds float32 images; the engine takes another image dtype");
+    if (o.tsdf_frames_path) {
+        HIP_OK(hipStreamCreateWithFlags(&stream.h, hipStreamNonBlocking), "hipStreamCreate");
+        return run_tsdf(o, eng.h, m, tsdf_frames, stream.h);
+    }
     if (o.gt_path && (g.rows % m.B != 0 || g.rows / m.B > m.out_h || g.w > m.out_w)) {
         fprintf(stderr, "s2m2_run_engine: --gt is %d x %d pixels; the engine needs B = %d stacked ground truths of at most %d x %d\n", g.w, g.rows,
                 m.B, m.out_w, m.out_h);

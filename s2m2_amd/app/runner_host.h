@@ -18,7 +18,10 @@ inline const char* const USAGE =
     "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
     "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]] "
     "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
-    "[--thresholds a,b,c] --metrics OUT.json]";
+    "[--thresholds a,b,c] --metrics OUT.json]"
+    " | s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T] "
+    "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
+    "[--unfiltered]";
 
 // ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
 struct Options {
@@ -32,7 +35,11 @@ struct Options {
     const char *min_size_arg = nullptr, *labels_path = nullptr, *segmask_path = nullptr;
     const char *voxel_arg = nullptr, *voxel_ply_path = nullptr, *voxel_max_arg = nullptr;
     const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr, *gt_min_arg = nullptr;
+    const char *tsdf_frames_path = nullptr, *tsdf_dims_arg = nullptr, *tsdf_voxel_arg = nullptr, *tsdf_origin_arg = nullptr;
+    const char *tsdf_trunc_arg = nullptr, *tsdf_min_weight_arg = nullptr, *tsdf_carve_arg = nullptr, *tsdf_ply_path = nullptr;
 
+    int tsdf_dims[3] = {0, 0, 0}, tsdf_min_weight = 1, tsdf_carve = 0;
+    double tsdf_voxel = 0.0, tsdf_trunc = 0.0, tsdf_origin[3] = {0, 0, 0};      // tsdf_trunc: 4 * tsdf_voxel unless --tsdf-trunc
     int repeat = 0, splat = 2, unfiltered = 0;
     long long min_size = 1, voxel_max = 0;               // voxel_max 0: a quarter of the image's pixels
     double max_jump = 1.0, voxel_size = 0.0;
@@ -76,7 +83,64 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--gt-min", true, &Options::gt_min_arg},
     {"--thresholds", true, &Options::thr_arg},
     {"--metrics", true, &Options::metrics_path},
+    {"--tsdf-frames", true, &Options::tsdf_frames_path},
+    {"--tsdf-dims", true, &Options::tsdf_dims_arg},
+    {"--tsdf-voxel", true, &Options::tsdf_voxel_arg},
+    {"--tsdf-origin", true, &Options::tsdf_origin_arg},
+    {"--tsdf-trunc", true, &Options::tsdf_trunc_arg},
+    {"--tsdf-min-weight", true, &Options::tsdf_min_weight_arg},
+    {"--tsdf-carve", false, &Options::tsdf_carve_arg},
+    {"--tsdf-ply", true, &Options::tsdf_ply_path},
 };
+
+// "a,b,c": exactly three numbers, nothing behind them
+inline bool parse_triple(const char* arg, double* v) {
+    for (int i = 0; i < 3; ++i) {
+        char* end = nullptr;
+        v[i] = strtod(arg, &end);
+        if (end == arg || *end != (i < 2 ? ',' : '\0')) return false;
+        arg = end + 1;
+    }
+    return true;
+}
+
+// a finite number > 0, nothing behind it
+inline bool parse_positive(const char* arg, double& v) {
+    char* end = nullptr;
+    v = strtod(arg, &end);
+    return end != arg && !*end && v > 0.0 && isfinite(v);
+}
+
+// the rules of the --tsdf-* options (K24); null: complete.  The mode takes ENGINE alone: its pairs come from LIST
+inline const char* check_tsdf_options(Options& o) {
+    if (!o.tsdf_frames_path) return "the --tsdf-* options need --tsdf-frames";
+    if (o.npos != 1) return "--tsdf-frames takes ENGINE alone: the pairs are named in LIST";
+    if (!o.tsdf_dims_arg || !o.tsdf_voxel_arg || !o.tsdf_origin_arg || !o.tsdf_ply_path || !o.calib_path)
+        return "--tsdf-frames needs --tsdf-dims, --tsdf-voxel, --tsdf-origin, --calib and --tsdf-ply";
+    if (o.out_dir || o.repeat_arg || o.image_path || o.ply_path || o.mesh_path || o.depth_path || o.register_cam || o.min_size_arg || o.voxel_arg ||
+        o.gt_path || o.max_jump_arg)
+        return "--tsdf-frames comes without the options of a single pair";
+    double d[3];
+    if (!parse_triple(o.tsdf_dims_arg, d)) return "--tsdf-dims: three integers >= 1, NX,NY,NZ with NX*NY*NZ < 2^29";
+    for (int i = 0; i < 3; ++i) {
+        if (!(d[i] >= 1.0 && d[i] < 536870912.0 && d[i] == floor(d[i]))) return "--tsdf-dims: three integers >= 1, NX,NY,NZ with NX*NY*NZ < 2^29";
+        o.tsdf_dims[i] = (int)d[i];
+    }
+    if (d[0] * d[1] * d[2] >= 536870912.0) return "--tsdf-dims: three integers >= 1, NX,NY,NZ with NX*NY*NZ < 2^29";
+    if (!parse_positive(o.tsdf_voxel_arg, o.tsdf_voxel)) return "--tsdf-voxel: a number > 0";
+    if (!parse_triple(o.tsdf_origin_arg, o.tsdf_origin) || !isfinite(o.tsdf_origin[0]) || !isfinite(o.tsdf_origin[1]) || !isfinite(o.tsdf_origin[2]))
+        return "--tsdf-origin: three finite numbers X,Y,Z";
+    o.tsdf_trunc = 4.0 * o.tsdf_voxel;
+    if (o.tsdf_trunc_arg && !parse_positive(o.tsdf_trunc_arg, o.tsdf_trunc)) return "--tsdf-trunc: a number > 0";
+    if (o.tsdf_min_weight_arg) {
+        char* end = nullptr;
+        const long long n = strtoll(o.tsdf_min_weight_arg, &end, 10);
+        if (end == o.tsdf_min_weight_arg || *end || n < 1 || n > 32767) return "--tsdf-min-weight: an integer in 1..32767";
+        o.tsdf_min_weight = (int)n;
+    }
+    o.tsdf_carve = o.tsdf_carve_arg != nullptr;
+    return nullptr;
+}
 
 // false: an unknown option, an option without its value or a fourth positional (the caller prints USAGE); a repeated option: the last one
 inline bool parse_options(int argc, char** argv, Options& o) {
@@ -101,6 +165,9 @@ inline const char* check_options(Options& o) {
     if (o.occ_min_arg) o.occ_min = atof(o.occ_min_arg);
     if (o.gt_min_arg) o.gt_min = atof(o.gt_min_arg);
     o.unfiltered = o.unfiltered_arg != nullptr;
+    if (o.tsdf_frames_path || o.tsdf_dims_arg || o.tsdf_voxel_arg || o.tsdf_origin_arg || o.tsdf_trunc_arg || o.tsdf_min_weight_arg || o.tsdf_carve_arg ||
+        o.tsdf_ply_path)
+        return check_tsdf_options(o);
     if (o.npos != 3 || o.repeat < 0) return USAGE;
     if (o.mesh_path && !o.calib_path) return "--calib and --mesh come together";
     if (o.register_cam && (!o.calib_path || !o.reg_depth_path)) return "--register needs --calib and --register-depth";
@@ -213,6 +280,45 @@ inline bool read_camera(const char* path, TargetCamera& c) {
     }
     fclose(f);
     return have_cam && c.width > 0 && c.height > 0;
+}
+
+// --tsdf-frames LIST: one frame per line -- LEFT.f32 RIGHT.f32 IMAGE.u8 and the twelve numbers of [R | t] row-major (world -> camera, t in the
+// unit of z); empty lines and lines that start with # are skipped.  The file names are used as they stand and hold no blanks
+struct TsdfFrame {
+    std::string left, right, image;
+    float pose[12];
+};
+
+// "": fine, else the message (with the line's number)
+inline std::string read_tsdf_frames(const char* path, std::vector<TsdfFrame>& frames) {
+    FILE* f = fopen(path, "r");
+    if (!f) return std::string("--tsdf-frames ") + path + ": cannot open the file";
+    char line[4096];
+    std::string msg;
+    for (int no = 1; msg.empty() && fgets(line, sizeof line, f); ++no) {
+        const char* c = line + strspn(line, " \t\r\n");
+        if (!*c || *c == '#') continue;
+        char name[3][1024];
+        int used = 0;
+        TsdfFrame fr;
+        bool ok = sscanf(c, "%1023s %1023s %1023s%n", name[0], name[1], name[2], &used) == 3;
+        c += used;
+        for (int i = 0; ok && i < 12; ++i) {
+            char* end = nullptr;
+            fr.pose[i] = strtof(c, &end);
+            ok = end != c && isfinite(fr.pose[i]);
+            c = end;
+        }
+        ok = ok && !c[strspn(c, " \t\r\n")];
+        if (!ok) msg = std::string("--tsdf-frames ") + path + ": line " + std::to_string(no) + ": LEFT.f32 RIGHT.f32 IMAGE.u8 and twelve finite pose numbers";
+        if (ok) {
+            fr.left = name[0]; fr.right = name[1]; fr.image = name[2];
+            frames.push_back(fr);
+        }
+    }
+    fclose(f);
+    if (msg.empty() && frames.empty()) msg = std::string("--tsdf-frames ") + path + ": no frame";
+    return msg;
 }
 
 // greyscale PFM: "Pf", "width height", "scale" (negative: little-endian), then the rows bottom to top -> rows top to bottom

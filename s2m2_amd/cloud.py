@@ -21,6 +21,11 @@ include/s2m2_hip.h, K22).  Four launches, no synchronisation, capturable.
 and the mean colour of the kept points in it, in K15's record format and in the raster order of the cells' first points (the rule:
 include/s2m2_hip.h, K23).  Four launches (five with the per-pixel index), no synchronisation, capturable, bit-reproducible.
 
+``TsdfVolume`` (K24, ``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``) is the first stage that carries state from one pair to the next: a dense
+truncated signed distance volume on the device that ``integrate`` fuses the depth maps of a moving rig into, pose by pose, and whose surface
+``extract`` returns as points with colours and gradients (the rule: include/s2m2_hip.h, K24).  One launch per call of ``integrate``, two per
+``extract``, no synchronisation, capturable, bit-reproducible.
+
 A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
@@ -412,3 +417,125 @@ def voxelize(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: t
     hip.voxel(disp, occ, conf, image, **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
               voxel_size=voxel_size, max_voxels=mv, workspace=workspace, records=records, weights=weights, count=count, index=index, stats=stats)
     return VoxelCloud(records, count, weights, index, stats)
+
+
+PLY_NORMALS_HEADER = PLY_HEADER.replace("property uchar red", "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red")
+NORMAL_RECORD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
+                                ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
+
+
+class TsdfSurface(PointCloud):
+    """What ``TsdfVolume.extract`` returns: a ``PointCloud`` with one pair (b = 0) whose records are the surface points of the volume in
+    ascending voxel order -- ``records`` (1, capacity, 4) int32, ``count`` (1) int32 (the true number of points, also above capacity) -- plus
+    ``gradients_buf`` (capacity, 3) fp32 or None: the unnormalised tsdf gradient at every point, from the surface to free space."""
+
+    def __init__(self, records: torch.Tensor, count: torch.Tensor, gradients_buf: Optional[torch.Tensor]):
+        super().__init__(records, count)
+        self.gradients_buf = gradients_buf
+
+    def gradients(self) -> torch.Tensor:
+        """(n,3) fp32: the tsdf gradient at every stored point"""
+        if self.gradients_buf is None:
+            raise ValueError("TsdfSurface.gradients: extract was called with want_gradients=False")
+        return self.gradients_buf[:self.size()]
+
+    def normals(self) -> torch.Tensor:
+        """(n,3) fp32: the gradients normalised in torch (a zero gradient stays zero); not part of the exact contract"""
+        g = self.gradients()
+        return g / g.norm(dim=1, keepdim=True).clamp_min(1e-30)
+
+    def write_ply(self, path: str, b: int = 0, normals: bool = False) -> int:
+        if not normals:
+            return super().write_ply(path, b)
+        rec = self.records[0, :self.size()].cpu().numpy().view(RECORD_DTYPE).ravel()
+        out = np.empty(len(rec), dtype=NORMAL_RECORD_DTYPE)
+        for name in RECORD_DTYPE.names:
+            out[name] = rec[name]
+        nrm = self.normals().cpu().numpy()
+        out["nx"], out["ny"], out["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+        with open(path, "wb") as f:
+            f.write((PLY_NORMALS_HEADER % len(out)).encode("ascii"))
+            f.write(out.tobytes())
+        return len(out)
+
+
+class TsdfVolume:
+    """A truncated signed distance volume on the device (K24, ``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``; the rule: include/s2m2_hip.h,
+    K24): ``dims`` = (Nx, Ny, Nz) voxels of ``voxel_size`` (the unit of z), ``origin`` the centre of voxel (0,0,0) in the world frame,
+    ``trunc`` the truncation distance (None: 4 * voxel_size), ``max_weight`` the cap of a voxel's frame count.  ``buffer`` is the
+    (Nz, Ny, Nx, 4) int32 tensor the kernels work on, 16 bytes per voxel; all zero = empty."""
+
+    def __init__(self, dims, voxel_size: float, origin, trunc: Optional[float] = None, max_weight: int = 64, device="cuda"):
+        Nx, Ny, Nz = (int(n) for n in dims)
+        if min(Nx, Ny, Nz) < 1 or Nx * Ny * Nz >= 1 << 29:
+            raise ValueError(f"TsdfVolume: bad dims {tuple(dims)} (positive, Nx*Ny*Nz < 2^29)")
+        if not (np.isfinite(float(voxel_size)) and voxel_size > 0):
+            raise ValueError(f"TsdfVolume: voxel_size must be finite and > 0, got {voxel_size}")
+        trunc = 4.0 * float(voxel_size) if trunc is None else float(trunc)
+        if not (np.isfinite(trunc) and trunc > 0):
+            raise ValueError(f"TsdfVolume: trunc must be finite and > 0, got {trunc}")
+        if int(max_weight) != max_weight or not 1 <= max_weight <= 32767:
+            raise ValueError(f"TsdfVolume: max_weight must be an integer in 1..32767, got {max_weight}")
+        self.dims, self.voxel_size, self.trunc, self.max_weight = (Nx, Ny, Nz), float(voxel_size), trunc, int(max_weight)
+        self.origin = tuple(float(x) for x in origin)
+        if len(self.origin) != 3 or not all(np.isfinite(self.origin)):
+            raise ValueError("TsdfVolume: origin is three finite numbers")
+        self.device = torch.device(device)
+        self.buffer = torch.zeros((Nz, Ny, Nx, 4), device=self.device, dtype=torch.int32)
+        self._workspace = None
+
+    def reset(self) -> None:
+        self.buffer.zero_()
+
+    def tsdf(self) -> torch.Tensor:
+        """(Nz, Ny, Nx) fp32 strided view"""
+        return self.buffer.view(torch.float32)[..., 0]
+
+    def weight(self) -> torch.Tensor:
+        """(Nz, Ny, Nx) int32 strided view"""
+        return self.buffer[..., 1]
+
+    def colour(self) -> torch.Tensor:
+        """(Nz, Ny, Nx, 3) int16 strided view of the 8.8 fixed-point r, g, b (read them as unsigned: value & 0xffff)"""
+        return self.buffer.view(torch.int16)[..., 4:7]
+
+    def _poses(self, R, t, B: int) -> torch.Tensor:
+        """R (3,3) or (B,3,3), t (3,) or (B,3), tensors on any device or anything ``torch.as_tensor`` takes -> (B,12) fp32 on the device"""
+        R = torch.as_tensor(R).to(device=self.device, dtype=torch.float32)
+        t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32)
+        if tuple(R.shape) not in ((3, 3), (B, 3, 3)) or tuple(t.shape) not in ((3,), (B, 3)):
+            raise ValueError(f"TsdfVolume.integrate: R is (3,3) or ({B},3,3) and t is (3,) or ({B},3), got {tuple(R.shape)} and {tuple(t.shape)}")
+        R = R.expand(B, 3, 3) if R.dim() == 2 else R
+        t = t.expand(B, 3) if t.dim() == 1 else t
+        return torch.cat([R, t[:, :, None]], dim=2).reshape(B, 12).contiguous()
+
+    def integrate(self, disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, left_u8: torch.Tensor, *, R, t, fx: float, cx: float,
+                  cy: float, baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
+                  depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True,
+                  carve: bool = False) -> "TsdfVolume":
+        """``reproject``'s operands and conventions plus the pose of every pair (``p_cam = R @ p_world + t``, ``t`` in the unit of z): the B
+        depth maps are fused into the volume in the order of the batch.  ``carve``: also the voxels between the camera and the band take the
+        free-space value 1.  One launch, no synchronisation, capturable; composes with ``segment(...).disp`` via ``filtered=False``."""
+        poses = self._poses(R, t, disp.shape[0])
+        hip.tsdf_integrate(self.buffer, disp, occ, conf, left_u8, poses,
+                           **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
+                           origin=self.origin, voxel_size=self.voxel_size, trunc=self.trunc, max_weight=self.max_weight, carve=carve)
+        return self
+
+    def extract(self, min_weight: int = 1, capacity: Optional[int] = None, want_gradients: bool = True) -> TsdfSurface:
+        """The surface as a point cloud: one point per sign change of the tsdf between two neighbouring voxels that both have at least
+        ``min_weight`` frames.  capacity None = Nx*Ny*Nz points (a crossing needs two voxels, three axes: the true bound is 3 per voxel, which
+        no surface reaches).  Two launches, no synchronisation, capturable."""
+        Nx, Ny, Nz = self.dims
+        cap = Nx * Ny * Nz if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError("TsdfVolume.extract: negative capacity")
+        if self._workspace is None:
+            self._workspace = torch.empty((hip.tsdf_workspace_bytes(Nx, Ny, Nz),), device=self.device, dtype=torch.uint8)
+        records = torch.empty((cap, 4), device=self.device, dtype=torch.int32)
+        gradients = torch.empty((cap, 3), device=self.device, dtype=torch.float32) if want_gradients else None
+        count = torch.empty((1,), device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            hip.tsdf_extract(self.buffer, origin=self.origin, voxel_size=self.voxel_size, min_weight=min_weight, workspace=self._workspace,
+                             records=records, gradients=gradients, count=count)
+        return TsdfSurface(records[None], count, gradients)

@@ -148,6 +148,18 @@ class VoxelDesc(ctypes.Structure):
                 ("voxel_size", ctypes.c_double), ("max_voxels", _ll), ("capacity", _ll)]
 
 
+class TsdfDesc(ctypes.Structure):
+    """mirror of s2m2_tsdf_desc (include/s2m2_hip.h): K24, depth maps fused into a TSDF volume"""
+    _fields_ = [("cloud", CloudDesc), ("volume", _vp), ("poses", _vp), ("Nx", _i), ("Ny", _i), ("Nz", _i), ("max_weight", _i), ("carve", _i),
+                ("origin", ctypes.c_double * 3), ("voxel_size", ctypes.c_double), ("trunc", ctypes.c_double)]
+
+
+class TsdfExtractDesc(ctypes.Structure):
+    """mirror of s2m2_tsdf_extract_desc (include/s2m2_hip.h): K24, the surface points of a TSDF volume"""
+    _fields_ = [("volume", _vp), ("records", _vp), ("gradients", _vp), ("count", _vp), ("workspace", _vp), ("Nx", _i), ("Ny", _i), ("Nz", _i),
+                ("min_weight", _i), ("capacity", _ll), ("origin", ctypes.c_double * 3), ("voxel_size", ctypes.c_double)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -269,6 +281,10 @@ SIGNATURES = {
     "s2m2_voxel_tile_rows": (_i, [_i, _i]),
     "s2m2_voxel_home_slot": (_ll, [_i, _i, _i, _ll]),
     "s2m2_voxel": (_i, [ctypes.POINTER(VoxelDesc), _vp]),
+    "s2m2_tsdf_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_tsdf_tile_voxels": (_i, [_i, _i, _i]),
+    "s2m2_tsdf_integrate": (_i, [ctypes.POINTER(TsdfDesc), _vp]),
+    "s2m2_tsdf_extract": (_i, [ctypes.POINTER(TsdfExtractDesc), _vp]),
 }
 
 
@@ -1376,3 +1392,5 @@ from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
 from .hip_segment import segment, segment_tile, segment_workspace_bytes  # noqa: E402,F401
 # K23 (s2m2_voxel): likewise, from hip_voxel.py
 from .hip_voxel import voxel, voxel_home_slot, voxel_slots, voxel_tile_rows, voxel_workspace_bytes  # noqa: E402,F401
+# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract): likewise, from hip_tsdf.py
+from .hip_tsdf import tsdf_extract, tsdf_integrate, tsdf_tile_voxels, tsdf_workspace_bytes  # noqa: E402,F401

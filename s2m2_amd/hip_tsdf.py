@@ -1,0 +1,104 @@
+"""K24 (``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``, csrc/tsdf.hip): depth maps fused into a TSDF volume, and the volume's surface points.
+The descriptor mirrors and the signatures are in hip.py with all the others (``hip.load()`` binds every symbol there); this module holds the
+wrappers, which hip.py re-exports as ``hip.tsdf_integrate``, ``hip.tsdf_extract``, ``hip.tsdf_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
+import ctypes
+import math
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import hip as _h
+
+
+def _volume(what: str, volume: torch.Tensor) -> Tuple[int, int, int]:
+    """the volume operand: a contiguous (Nz, Ny, Nx, 4) int32 tensor = 16 bytes per voxel, voxel (i, j, k) at [k, j, i] -> (Nx, Ny, Nz)"""
+    if volume is None or volume.dtype != torch.int32 or volume.dim() != 4 or volume.shape[3] != 4 or not volume.is_contiguous():
+        raise ValueError(f"{what}: the volume must be a contiguous (Nz, Ny, Nx, 4) int32 tensor")
+    Nz, Ny, Nx = volume.shape[:3]
+    if min(Nx, Ny, Nz) < 1 or Nx * Ny * Nz >= 1 << 29:
+        raise ValueError(f"{what}: bad dims Nx={Nx} Ny={Ny} Nz={Nz} (positive, Nx*Ny*Nz < 2^29)")
+    return Nx, Ny, Nz
+
+
+def _placement(what: str, origin: Sequence[float], voxel_size: float):
+    """the grid's placement: three finite numbers and a finite size > 0 -> (ctypes origin, voxel_size)"""
+    origin = [float(x) for x in origin]
+    if len(origin) != 3 or not all(math.isfinite(x) for x in origin):
+        raise ValueError(f"{what}: origin is three finite numbers")
+    if not (math.isfinite(float(voxel_size)) and voxel_size > 0):
+        raise ValueError(f"{what}: voxel_size must be finite and > 0, got {voxel_size}")
+    return (ctypes.c_double * 3)(*origin), float(voxel_size)
+
+
+def tsdf_integrate(volume: torch.Tensor, disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, poses: torch.Tensor, *,
+                   fx: float, fy: float, cx: float, cy: float, baseline: float, doffs: float = 0.0, depth_scale: float = 1000.0,
+                   depth_trunc: float = 0.0, conf_min: float = 0.1, occ_min: float = 0.5, unfiltered: bool = False, origin: Sequence[float],
+                   voxel_size: float, trunc: float, max_weight: int = 64, carve: bool = False) -> None:
+    """s2m2_tsdf_integrate (K24): the B padded maps (B,1,Hp,Wp) fp32, the UNPADDED left images (B,3,H,W) uint8 / fp16 / fp32 and the DEVICE
+    pose buffer ``poses`` (B,12) fp32 ([R | t] row-major, world -> camera) are fused into ``volume`` (Nz,Ny,Nx,4) int32 in place, pair by
+    pair in the order of the batch.  Thin: no allocation, no synchronisation."""
+    _h._resident("tsdf_integrate", volume, disp, occ, conf, image, poses)
+    _h._contig("tsdf_integrate", volume, disp, occ, conf, image, poses)
+    d = _h.TsdfDesc()
+    d.Nx, d.Ny, d.Nz = _volume("tsdf_integrate", volume)
+    if image is None:
+        raise ValueError("tsdf_integrate: the image is required")
+    B, _, _ = _h._cloud_inputs("tsdf_integrate", d.cloud, disp, occ, conf, image, None, None, fx, fy, cx, cy, baseline, doffs, depth_scale,
+                               depth_trunc, conf_min, occ_min, unfiltered)
+    _h._mat(poses, (B, 12), torch.float32, "tsdf_integrate: poses")
+    d.origin, d.voxel_size = _placement("tsdf_integrate", origin, voxel_size)
+    if not (math.isfinite(float(trunc)) and trunc > 0):
+        raise ValueError(f"tsdf_integrate: trunc must be finite and > 0, got {trunc}")
+    if int(max_weight) != max_weight or not 1 <= max_weight <= 32767:
+        raise ValueError(f"tsdf_integrate: max_weight must be an integer in 1..32767, got {max_weight}")
+    d.trunc, d.max_weight, d.carve = float(trunc), int(max_weight), int(bool(carve))
+    d.volume, d.poses = volume.data_ptr(), poses.data_ptr()
+    with torch.cuda.device(disp.device):
+        _h._check(_h.load().s2m2_tsdf_integrate(ctypes.byref(d), _h._stream()), "s2m2_tsdf_integrate")
+
+
+def tsdf_extract(volume: torch.Tensor, *, origin: Sequence[float], voxel_size: float, min_weight: int = 1, workspace: torch.Tensor,
+                 records: Optional[torch.Tensor] = None, gradients: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None) -> None:
+    """s2m2_tsdf_extract (K24): the surface points of ``volume`` (Nz,Ny,Nx,4) int32 -> the outputs the caller allocated: ``records``
+    (capacity, 4) int32 = 16-byte records, ``gradients`` (capacity, 3) fp32, ``count`` (1) int32; ``records`` and ``gradients`` share one
+    capacity; ``workspace``: ``tsdf_workspace_bytes`` bytes.  Thin: no allocation, no synchronisation."""
+    _h._resident("tsdf_extract", volume, workspace, records, gradients, count)
+    _h._contig("tsdf_extract", volume, workspace, records, gradients, count)
+    d = _h.TsdfExtractDesc()
+    d.Nx, d.Ny, d.Nz = _volume("tsdf_extract", volume)
+    d.origin, d.voxel_size = _placement("tsdf_extract", origin, voxel_size)
+    if int(min_weight) != min_weight or min_weight < 1:
+        raise ValueError(f"tsdf_extract: min_weight must be an integer >= 1, got {min_weight}")
+    d.min_weight = int(min_weight)
+    capacity = None
+    if records is not None:
+        if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 4:
+            raise ValueError("tsdf_extract: records must be a (capacity, 4) int32 tensor")
+        capacity = records.shape[0]
+    if gradients is not None:
+        if gradients.dtype != torch.float32 or gradients.dim() != 2 or gradients.shape[1] != 3 or capacity not in (None, gradients.shape[0]):
+            raise ValueError("tsdf_extract: gradients must be a (capacity, 3) fp32 tensor, with the capacity of records")
+        capacity = gradients.shape[0]
+    d.capacity = capacity or 0
+    if capacity:
+        d.records, d.gradients = _h._ptr(records), _h._ptr(gradients)
+    if count is not None:
+        _h._vec(count, 1, "tsdf_extract: count", dtype=torch.int32)
+        d.count = count.data_ptr()
+    if not capacity and count is None:
+        raise ValueError("tsdf_extract: no output requested")
+    need = tsdf_workspace_bytes(d.Nx, d.Ny, d.Nz)
+    if workspace is None or workspace.nbytes < need:
+        raise ValueError(f"tsdf_extract: a workspace of {need} bytes is required")
+    d.workspace, d.volume = workspace.data_ptr(), volume.data_ptr()
+    with torch.cuda.device(volume.device):
+        _h._check(_h.load().s2m2_tsdf_extract(ctypes.byref(d), _h._stream()), "s2m2_tsdf_extract")
+
+
+def tsdf_workspace_bytes(Nx: int, Ny: int, Nz: int) -> int:
+    return _h._extent_query("s2m2_tsdf_workspace_bytes", "tsdf", Nx=Nx, Ny=Ny, Nz=Nz)
+
+
+def tsdf_tile_voxels(Nx: int, Ny: int, Nz: int) -> int:
+    """consecutive voxels of one tile of the extraction launches at these dims"""
+    return _h._extent_query("s2m2_tsdf_tile_voxels", "tsdf", Nx=Nx, Ny=Ny, Nz=Nz)

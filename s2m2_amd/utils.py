@@ -204,6 +204,20 @@ def voxel_down_sample(rgb, disp, calib, voxel_size, depth_trunc=None):
                               voxel_size=voxel_size)
 
 
+def integrate_tsdf(volume, rgb, disp, calib, R, t, depth_trunc=None):
+    """``get_pointcloud``'s arguments and conventions (halved intrinsics, fx for both focal lengths, no confidence filter) for one frame of a
+    moving rig: the frame's depth map is fused into ``volume`` (a ``cloud.TsdfVolume``) from the pose ``R`` (3,3), ``t`` (3,) -- world ->
+    camera, ``t`` in the unit of z (metres with a Middlebury calibration).  Returns ``volume``."""
+    disp_t = torch.as_tensor(disp).to(device=volume.device, dtype=torch.float32).contiguous()[None, None]
+    image = torch.as_tensor(rgb).to(volume.device).permute(2, 0, 1).contiguous()[None]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(volume.device):
+        volume.integrate(disp_t, disp_t, disp_t, image, R=R, t=t, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0,
+                         cy=float(cam0[1, 2]) / 2.0, baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc,
+                         filtered=False)
+    return volume
+
+
 def filter_speckles(disp, calib, depth_trunc=None, max_jump=1.0, min_size=100):
     """``get_pointcloud``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter: ``disp`` (H,W) arrives filtered, -1
     where invalid) -> the (H,W) fp32 disparity on the device with -1 also wherever the pixel's 4-connected component of similar disparity

@@ -291,6 +291,65 @@ int main(int argc, char** argv) {
         CHECK(o.splat == 2 && o.depth_scale == 1000.0 && o.occ_min == 0.5 && o.gt_min == 0.0 && !o.ply_path && !o.gt_path);
     }
 
+    // ---- --tsdf-frames (K24): the mode's rules, the numbers it parses, and LIST
+    {
+        const auto tsdf = [&](std::vector<std::string> args, Options& o) -> std::string {
+            args.insert(args.begin(), {"s2m2_run_engine", "absent.s2m2"});
+            std::vector<char*> av;
+            for (std::string& s : args) av.push_back(&s[0]);
+            if (!parse_options((int)av.size(), av.data(), o)) return USAGE;
+            const char* msg = check_options(o);
+            return msg ? msg : "engine";
+        };
+        const std::vector<std::string> full = {"--tsdf-frames", "l.txt", "--tsdf-dims", "19,13,11", "--tsdf-voxel", "0.1", "--tsdf-origin", "-0.9,-0.6,1.5",
+                                               "--calib", golden_calib, "--tsdf-ply", "t.ply"};
+        Options o;
+        CHECK(tsdf(full, o) == "engine");
+        CHECK(o.tsdf_dims[0] == 19 && o.tsdf_dims[1] == 13 && o.tsdf_dims[2] == 11 && o.tsdf_voxel == 0.1 && o.tsdf_trunc == 0.4 && o.tsdf_min_weight == 1);
+        CHECK(o.tsdf_origin[0] == -0.9 && o.tsdf_origin[1] == -0.6 && o.tsdf_origin[2] == 1.5 && !o.tsdf_carve);
+        std::vector<std::string> more = full;
+        more.insert(more.end(), {"--tsdf-trunc", "0.25", "--tsdf-min-weight", "3", "--tsdf-carve"});
+        Options o2;
+        CHECK(tsdf(more, o2) == "engine" && o2.tsdf_trunc == 0.25 && o2.tsdf_min_weight == 3 && o2.tsdf_carve == 1);
+        const auto with = [&](const char* flag, const char* value) {
+            std::vector<std::string> a = full;
+            for (size_t i = 0; i + 1 < a.size(); ++i)
+                if (a[i] == flag) a[i + 1] = value;
+            Options x;
+            return tsdf(a, x);
+        };
+        for (const char* bad : {"19,13", "19,13,11,2", "19,13,0", "1.5,2,3", "1024,1024,512", "", ",,", "19,13,11x"})
+            CHECK(with("--tsdf-dims", bad).find("--tsdf-dims: three integers") == 0);
+        for (const char* bad : {"0", "-1", "nan", "inf", "1e400", "", "5cm"}) CHECK(with("--tsdf-voxel", bad) == "--tsdf-voxel: a number > 0");
+        for (const char* bad : {"0,0", "0,0,nan", "0,0,inf", "a,b,c", "0,0,0,0"}) CHECK(with("--tsdf-origin", bad).find("--tsdf-origin: three finite numbers") == 0);
+        Options o3;
+        CHECK(tsdf({"--tsdf-dims", "1,1,1"}, o3).find("need --tsdf-frames") != std::string::npos);
+        Options o4;
+        std::vector<std::string> pair = full;
+        pair.insert(pair.begin(), {"l.f32", "r.f32"});
+        CHECK(tsdf(pair, o4).find("takes ENGINE alone") != std::string::npos);
+
+        std::vector<TsdfFrame> fr;
+        put("frames.txt", "# head\n\nl0.f32 r0.f32 i0.u8 1 0 0 0.5 0 1 0 -0.25 0 0 1 2\n   l1.f32 r1.f32 i1.u8 1 0 0 0 0 1 0 0 0 0 1 0   \n");
+        CHECK(read_tsdf_frames(in_dir("frames.txt").c_str(), fr).empty() && fr.size() == 2);
+        CHECK(fr.size() == 2 && fr[0].left == "l0.f32" && fr[0].image == "i0.u8" && fr[0].pose[3] == 0.5f && fr[0].pose[7] == -0.25f && fr[0].pose[11] == 2.f &&
+              fr[1].right == "r1.f32");
+        const auto list_says = [&](const std::string& text, const char* want) {
+            std::vector<TsdfFrame> x;
+            put("frames.txt", text);
+            return read_tsdf_frames(in_dir("frames.txt").c_str(), x).find(want) != std::string::npos;
+        };
+        CHECK(list_says("", "no frame") && list_says("# only\n", "no frame"));
+        CHECK(list_says("l r i 1 0 0 0 0 1 0 0 0 0 1\n", "line 1: "));                       // eleven numbers
+        CHECK(list_says("l r i 1 0 0 0 0 1 0 0 0 0 1 0 9\n", "line 1: "));                   // thirteen
+        CHECK(list_says("l r 1 0 0 0 0 1 0 0 0 0 1 0\n", "line 1: "));                       // two names
+        CHECK(list_says("l r i 1 0 0 0 0 1 0 0 0 0 1 0\nl r i 1 0 0 inf 0 1 0 0 0 0 1 0\n", "line 2: "));
+        CHECK(list_says(std::string(5000, 'x') + " r i 1 0 0 0 0 1 0 0 0 0 1 0\n", "line 1: "));     // a name longer than the line buffer
+        std::vector<TsdfFrame> none;
+        CHECK(read_tsdf_frames(in_dir("absent.txt").c_str(), none).find("cannot open") != std::string::npos);
+        unlink(in_dir("frames.txt").c_str());
+    }
+
     for (const char* name : {"le.pfm", "be.pfm", "short.pfm", "long.pfm", "colour.pfm", "scale0.pfm", "width0.pfm", "huge.pfm", "nobase.txt", "longline.txt",
                              "cam_min.txt", "cam_full.txt", "cam_nocam.txt", "cam_nowidth.txt", "cam_width0.txt", "cam_widthneg.txt", "n.json", "c.ply", "m.ply",
                              "m0.ply", "p.ppm", "r6.u8", "r5.u8", "one.f32"})

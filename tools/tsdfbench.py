@@ -1,0 +1,218 @@
+"""K24 (s2m2_tsdf_integrate / s2m2_tsdf_extract: depth maps fused into a TSDF volume, and its surface points) against the same results composed
+from torch ops, same box, same process, alternated.
+
+Integrate: B = 1 and 4 frames of 1216x1024 into volumes of 256^3 and 512^3 voxels that span the view at 2 m, for a plane at 2 m (`plane`) and
+for two surfaces at 1.5 m and 2.5 m side by side (`two`), with carve 0 and 1.  The torch composition is the header's formulas as whole-volume
+tensor ops -- the projection, three gathers from the maps and three from the image, and `torch.where` over every field -- frame by frame; its
+result is compared with K24's before anything is timed: the voxels whose weight differs, and among the others those whose colour differs
+and the largest tsdf difference.  (torch's device arithmetic is not the header's bit for bit: where 100 / disp is not exact, as for the 1.5 m surface of
+`two`, its tsdf differs in the last bits (measured); the voxels with another weight appear only in that scene, which fits a voxel
+whose sdf sits on a band edge falling on the other side of it -- whole slices of a grid that is aligned with the surface -- but that
+cause is supposed, not shown.  K24 itself is pinned bit for bit by
+tests/test_hip_tsdf.py against the numpy oracle.)  The timed calls go on fusing
+the same frames into the same volume (the weights run up to the cap of 64; the voxels a call updates do not change), and neither side is
+charged a clear.  K24 is timed with events around `--steps` replays of a hipGraph that holds one call; the composition with events around
+`--torch-steps` eager calls after a warm-up call, in the same alternated windows.  Figures are the median of `--repeats` windows with minimum
+and maximum.
+
+TRAFFIC: a voxel that a call updates is read and written once: 32 bytes.  `updated x 32 B / time` is the rate at which K24 moves the voxels
+it has to move, printed as a share of the HBM rate a float4 copy reaches on this part (6.29 TB/s; 8.0 TB/s is the specification).  It is NOT the
+kernel's whole traffic: every voxel is also projected and gathers three map values per frame whether or not it is updated, which the figure
+leaves out, so a low share with carve 0 says that the launch is bound by the voxels it skips.
+
+Extract: the surface points of the volumes above after the B = 4 call, against nonzero + gathers in torch (which synchronises to size its
+result); the counts are compared.
+
+    python tools/tsdfbench.py [--steps 20] [--torch-steps 3] [--repeats 5] [--forward] [--dims 256,512] [--out profiles/tsdf/tsdfbench.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W = 1024, 1216
+CAM = dict(fx=1000.0, fy=1000.0, cx=608.0, cy=512.0, baseline=100.0, doffs=0.0, depth_scale=1000.0, depth_trunc=10.0, conf_min=0.1, occ_min=0.5)
+HBM_COPY_TBS = 6.29
+
+
+def torch_integrate(torch, vol, disp, occ, conf, img, poses, origin, vs, trunc, max_weight, carve):
+    """the header's formulas over the whole volume, pair by pair; vol (Nz,Ny,Nx,4) int32 is updated in place"""
+    Nz, Ny, Nx, _ = vol.shape
+    dev = vol.device
+    f32 = torch.float32
+    x = (origin[0] + torch.arange(Nx, device=dev, dtype=f32) * vs)[None, None, :]
+    y = (origin[1] + torch.arange(Ny, device=dev, dtype=f32) * vs)[None, :, None]
+    z = (origin[2] + torch.arange(Nz, device=dev, dtype=f32) * vs)[:, None, None]
+    tsdf, weight = vol[..., 0].view(f32).clone(), vol[..., 1].clone()
+    col = [vol[..., 2] & 0xffff, (vol[..., 2] >> 16) & 0xffff, vol[..., 3] & 0xffff]
+    pad = vol[..., 3] & ~0xffff
+    bf = CAM["baseline"] * CAM["fx"]
+    for b in range(disp.shape[0]):
+        q = poses[b].tolist()
+        X = ((q[0] * x + q[1] * y) + q[2] * z) + q[3]
+        Y = ((q[4] * x + q[5] * y) + q[6] * z) + q[7]
+        Z = ((q[8] * x + q[9] * y) + q[10] * z) + q[11]
+        fu = torch.round((CAM["fx"] * X) / Z + CAM["cx"])
+        fv = torch.round((CAM["fy"] * Y) / Z + CAM["cy"])
+        inside = (Z > 0) & torch.isfinite(Z) & (fu >= 0) & (fu < W) & (fv >= 0) & (fv < H)
+        pix = torch.where(inside, fv * W + fu, 0.0).long().reshape(-1)
+        d = disp[b, 0].reshape(-1)[pix].reshape(Z.shape)
+        valid = (conf[b, 0].reshape(-1)[pix].reshape(Z.shape) > CAM["conf_min"]) & (occ[b, 0].reshape(-1)[pix].reshape(Z.shape) > CAM["occ_min"])
+        d = torch.where(valid, d, -1.0)
+        zp = torch.where(d <= 0, 1e9, bf / (d + CAM["doffs"])) / CAM["depth_scale"]
+        keep = inside & (zp > 0) & (zp < CAM["depth_trunc"])
+        sdf = zp - Z
+        upd = keep & (sdf >= -trunc)
+        if not carve:
+            upd &= ~(sdf > trunc)
+        dd = torch.clamp_max(sdf / trunc, 1.0)
+        Wf = weight.float()
+        tsdf = torch.where(upd, (tsdf * Wf + dd) / (Wf + 1.0), tsdf)
+        for ch in range(3):
+            byte = img[b, ch].reshape(-1)[pix].reshape(Z.shape).int()
+            new = (col[ch].long() * weight + (byte << 8) + ((weight + 1) >> 1)) // (weight + 1)
+            col[ch] = torch.where(upd, new.int(), col[ch])
+        weight = torch.where(upd, torch.clamp_max(weight + 1, max_weight), weight)
+    vol[..., 0] = tsdf.view(torch.int32)
+    vol[..., 1] = weight
+    vol[..., 2] = col[0] | (col[1] << 16)
+    vol[..., 3] = col[2] | pad
+
+
+def torch_extract(torch, vol, origin, vs, min_weight):
+    """the surface points from nonzero + gathers -> (xyz (n,3) fp32, rgb (n,3) uint8, gradients (n,3) fp32); points run by axis, then by
+    voxel (K24 runs by voxel, then by axis: the same set)"""
+    Nz, Ny, Nx, _ = vol.shape
+    f32 = torch.float32
+    t, obs = vol[..., 0].view(f32), vol[..., 1] >= min_weight
+    colour = torch.stack([vol[..., 2] & 0xffff, (vol[..., 2] >> 16) & 0xffff, vol[..., 3] & 0xffff], -1)
+    tpad = torch.nn.functional.pad(torch.where(obs, t, float("nan")), (1, 1, 1, 1, 1, 1), value=float("nan"))      # NaN: outside or unobserved
+    out = []
+    for a, dim in enumerate((2, 1, 0)):                                # x, y, z are the tensor dims 2, 1, 0
+        n = vol.shape[dim]
+        t0, t1 = t.narrow(dim, 0, n - 1), t.narrow(dim, 1, n - 1)
+        emit = obs.narrow(dim, 0, n - 1) & obs.narrow(dim, 1, n - 1) & ((t0 < 0) != (t1 < 0))
+        idx = torch.nonzero(emit)                                      # synchronises
+        k, j, i = idx[:, 0], idx[:, 1], idx[:, 2]
+        a0, a1 = t0[k, j, i], t1[k, j, i]
+        s = a0 / (a0 - a1)
+        xyz = torch.stack([origin[0] + i.float() * vs, origin[1] + j.float() * vs, origin[2] + k.float() * vs], 1)
+        xyz[:, a] = xyz[:, a] + s * vs
+        far = (a1.abs() < a0.abs()).long()
+        sel = [k + far * (dim == 0), j + far * (dim == 1), i + far * (dim == 2)]
+        rgb = ((colour[sel[0], sel[1], sel[2]] + 128) >> 8).to(torch.uint8)
+        ts = torch.where(far.bool(), a1, a0)
+        grad = []
+        for off in ((0, 0, 1), (0, 1, 0), (1, 0, 0)):
+            tp = tpad[sel[0] + 1 + off[0], sel[1] + 1 + off[1], sel[2] + 1 + off[2]]
+            tm = tpad[sel[0] + 1 - off[0], sel[1] + 1 - off[1], sel[2] + 1 - off[2]]
+            grad.append(torch.where(torch.isnan(tp), ts, tp) - torch.where(torch.isnan(tm), ts, tm))
+        out.append((xyz, rgb, torch.stack(grad, 1)))
+    return tuple(torch.cat([o[c] for o in out]) for c in range(3))
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--torch-steps", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--forward", action="store_true")
+    ap.add_argument("--dims", default="256,512")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tsdf", "tsdfbench.txt"))
+    a = ap.parse_args()
+    import torch
+    from s2m2_amd import hip
+    from tools.kbench import captured, spread, timed
+    lines = []
+
+    def say(s: str) -> None:
+        print(s, flush=True)
+        lines.append(s)
+
+    forward_us = None
+    if a.forward:
+        from s2m2_amd.model import build_model
+        from s2m2_amd.spec import MODEL_CONFIGS
+        from s2m2_amd.weights import seeded_state_dict, synthetic_pair
+        C, ntr = MODEL_CONFIGS["S"]
+        m = build_model("S")
+        m.load_state_dict(seeded_state_dict(C, 1, ntr, 0), strict=True)
+        m = m.cuda().eval()
+        l, r = (t.cuda().contiguous() for t in synthetic_pair(H, W, 1, 32, 0))
+        with torch.autocast("cuda", dtype=torch.float16):
+            for _ in range(3):
+                m(l, r)
+            forward_us = statistics.median(timed(lambda: m(l, r), 50) for _ in range(a.repeats))
+        say(f"S forward {W}x{H} fp16 (hipGraph replay, same session): {forward_us / 1000.0:.3f} ms")
+        del m
+
+    g = torch.Generator(device="cuda").manual_seed(7)
+    vv, uu = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32), indexing="ij")
+    depth = dict(plane=torch.full((H, W), 2.0, device="cuda"), two=torch.where(uu < W // 2, 1.5, 2.5))
+    one = torch.ones((4, 1, H, W), device="cuda")
+    img = torch.randint(0, 256, (4, 3, H, W), device="cuda", dtype=torch.uint8, generator=g)
+    poses = torch.tensor([[1, 0, 0, 0.01 * b, 0, 1, 0, -0.005 * b, 0, 0, 1, 0.02 * b] for b in range(4)], device="cuda", dtype=torch.float32)
+    for N in (int(x) for x in a.dims.split(",")):
+        vs = 2.048 / N
+        origin, trunc = (-1.024 + vs / 2, -1.024 + vs / 2, 1.0), 4 * vs
+        place = dict(origin=origin, voxel_size=vs)
+        ws = torch.empty(hip.tsdf_workspace_bytes(N, N, N), device="cuda", dtype=torch.uint8)
+        for scene, z in depth.items():
+            disp = (100.0 / z)[None, None].repeat(4, 1, 1, 1).contiguous()
+            for B in (1, 4):
+                for carve in (False, True):
+                    maps = (disp[:B], one[:B], one[:B], img[:B], poses[:B])
+                    kw = dict(**CAM, **place, trunc=trunc, max_weight=64, carve=carve)
+                    vol = torch.zeros((N, N, N, 4), device="cuda", dtype=torch.int32)
+                    ref = torch.zeros_like(vol)
+                    hip.tsdf_integrate(vol, *maps, **kw)
+                    torch_integrate(torch, ref, *maps, origin, vs, trunc, 64, carve)
+                    torch.cuda.synchronize()
+                    updated = int((vol[..., 1] > 0).sum())
+                    same = vol[..., 1] == ref[..., 1]
+                    diff_w = int((~same).sum())
+                    err = float(torch.where(same, vol[..., 0].view(torch.float32) - ref[..., 0].view(torch.float32), 0.0).abs().max())
+                    diff_c = int((same & (vol[..., 2:] != ref[..., 2:]).any(-1)).sum())
+                    graph = captured(lambda: hip.tsdf_integrate(vol, *maps, **kw))
+                    tk, tt = [], []
+                    for _ in range(a.repeats):
+                        tk.append(timed(graph.replay, a.steps))
+                        tt.append(timed(lambda: torch_integrate(torch, ref, *maps, origin, vs, trunc, 64, carve), a.torch_steps))
+                    uk, ut = statistics.median(tk), statistics.median(tt)
+                    say(f"integrate {N}^3 {scene:5s} B={B} carve={int(carve)}: {updated} voxels updated of {N ** 3} "
+                        f"(torch: {diff_w} voxels with another weight; among the others {diff_c} with another colour, max |tsdf difference| {err:.2e})")
+                    say(f"    K24                {spread(tk)}   {updated * 32 / uk / 1e6:6.3f} TB/s of updated voxels = "
+                        f"{updated * 32 / uk / 1e6 / HBM_COPY_TBS * 100:5.1f} % of the {HBM_COPY_TBS} TB/s copy rate" +
+                        (f"   {uk / B / forward_us * 100:.2f} % of an S forward per frame" if forward_us else ""))
+                    say(f"    torch composition  {spread(tt)}   {ut / uk:6.1f}x K24")
+                    del graph
+            # extraction of the last volume of the scene (B = 4, carve 1 on top of what the timing loops added)
+            cap = N * N * N // 4
+            rec = torch.empty((cap, 4), device="cuda", dtype=torch.int32)
+            grd = torch.empty((cap, 3), device="cuda", dtype=torch.float32)
+            cnt = torch.zeros((1,), device="cuda", dtype=torch.int32)
+            run = lambda: hip.tsdf_extract(vol, **place, min_weight=1, workspace=ws, records=rec, gradients=grd, count=cnt)      # noqa: E731
+            run()
+            n = int(cnt[0])
+            nt = torch_extract(torch, vol, origin, vs, 1)[0].shape[0]
+            graph = captured(run)
+            tk, tt = [], []
+            for _ in range(a.repeats):
+                tk.append(timed(graph.replay, a.steps))
+                tt.append(timed(lambda: torch_extract(torch, vol, origin, vs, 1), a.torch_steps))
+            uk, ut = statistics.median(tk), statistics.median(tt)
+            say(f"extract   {N}^3 {scene:5s}: {n} points (torch: {nt}), capacity {cap}")
+            say(f"    K24                {spread(tk)}   {N ** 3 * 16 / uk / 1e6:6.3f} TB/s of volume read = {N ** 3 * 16 / uk / 1e6 / HBM_COPY_TBS * 100:5.1f} % "
+                f"of the copy rate" + (f"   {uk / forward_us * 100:.2f} % of an S forward" if forward_us else ""))
+            say(f"    torch composition  {spread(tt)}   {ut / uk:6.1f}x K24")
+            del graph, vol, ref, rec, grd
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
