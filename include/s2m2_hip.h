@@ -1251,6 +1251,53 @@ int s2m2_tsdf_tile_voxels(int Nx, int Ny, int Nz);          /* consecutive voxel
 int s2m2_tsdf_integrate(const s2m2_tsdf_desc* desc, void* stream);
 int s2m2_tsdf_extract(const s2m2_tsdf_extract_desc* desc, void* stream);
 
+/*
+ * K25 -- the surface of K24's volume as a triangle mesh (what open3d's TSDFVolume.extract_triangle_mesh does on the host): marching cubes on
+ *   the device, "K20 for the volume".  No counterpart in the reference: the semantics are defined here and pinned by the numpy oracle of
+ *   tests/tsdf_mesh_oracle.py.  Still S2M2_ABI_VERSION 800: the entry points are added, nothing changes in place.
+ *   Cells.  A cell is (i, j, k) with 0 <= i < Nx-1, 0 <= j < Ny-1, 0 <= k < Nz-1; its corner c = dx + 2 dy + 4 dz is voxel (i+dx, j+dy, k+dz).
+ *     A cell is VALID iff all eight corners are observed (weight >= min_weight, K24's predicate).  Its case is the sum of (t_c < 0) << c, the
+ *     sign predicate of K24: +0.0 and -0.0 are not negative.  A grid with an extent of 1 has no cells.
+ *   Vertices.  Exactly the points of s2m2_tsdf_extract for the same volume, origin, voxel_size and min_weight: records, gradients and count are
+ *     BYTE-IDENTICAL to what s2m2_tsdf_extract writes, the capacity rule included (both entry points compile the same device functions).  Every
+ *     point is a vertex, also one that no face references.  Edge e = (axis a, base corner b with bit a clear) of a cell carries the vertex that
+ *     K24 emits for voxel (cell + b) along axis a; its index is that point's rank.  The edges are numbered axis-major: for a in 0..2, the bases b
+ *     in ascending order.  In a valid cell every sign-changing edge joins two observed voxels, so its point exists.
+ *   Faces.  The valid cells are visited in ascending lin = (k * Ny + j) * Nx + i; inside a cell the triangles come in the order of the case
+ *     table.  A face is three int32 vertex ranks, wound so that its normal points to free space (the positive side, where K24's gradients
+ *     point).  The indices are true ranks also when count > capacity: the caller compares, as for K20.
+ *   Case table.  256 cases, each a list of at most 5 triangles over the 12 edge numbers, 820 in all, GENERATED by s2m2_amd/mc_table.py
+ *     (csrc/mc_table.h is its output; the oracle imports the same build_table()).  The construction: on each cube face two sign-changing edges
+ *     are joined by a segment, and four (diagonal corners alike) by two segments that cut off the two NEGATIVE corners separately -- this depends
+ *     on the face's four signs alone, so the two cells sharing a face agree; the segments close into loops, taken in the order of their lowest
+ *     edge and oriented to the positive side; a loop is triangulated as a fan from the first apex (rotating from its lowest edge) for which no
+ *     fan diagonal lies in a cube face.  The meshes are closed oriented 2-manifolds wherever the cells around the surface are valid.
+ *   Degenerate input.  A tsdf of exactly zero puts several vertices on one voxel centre; the zero-area triangles that result are emitted and
+ *     are part of the contract.
+ *   `extract`: every field with K24's meaning; records, gradients and count are each optional, and all three may be NULL (a faces-only call).
+ *     faces       (face_capacity, 3) int32, 4-byte aligned; may be NULL with face_capacity 0
+ *     face_count  one int32, REQUIRED: the true number of faces, also above face_capacity; faces of rank >= face_capacity are not stored and
+ *                 memory behind min(face_count, face_capacity) faces is left untouched
+ *     workspace (extract.workspace): >= s2m2_tsdf_mesh_workspace_bytes(Nx, Ny, Nz) bytes, 4-byte aligned: 4 bytes per voxel (the rank map: the
+ *     rank of a voxel's first point) plus 8 bytes per tile of s2m2_tsdf_tile_voxels voxels, each part rounded up to 256 bytes.
+ *     face_count is an int32, so Nx*Ny*Nz <= (2^31 - 1) / 5 = 429 496 729 (tighter than K24's 2^29; 512^3 passes).
+ *     Three launches, no host step, no atomics, no waiting between blocks: a block counts the points and the faces of a tile, the blocks rank
+ *     and store the points (K24's store launch, which also writes the rank map), then rank and store the faces.  Bit-reproducible.
+ *     Errors (before any device call): null descriptor; everything s2m2_tsdf_extract checks except "no output requested"; a null or misaligned
+ *     face_count; misaligned faces; negative face_capacity; faces NULL with face_capacity > 0; the size limit above; a missing or misaligned
+ *     workspace.
+ *   Launch plans: s2m2_tsdf_mesh is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing.
+ *   Safe under stream capture (hipGraph).
+ */
+typedef struct s2m2_tsdf_mesh_desc {
+    s2m2_tsdf_extract_desc extract;   /* every field with K24's meaning; workspace >= s2m2_tsdf_mesh_workspace_bytes */
+    void*          faces;             /* (face_capacity, 3) int32, 4-byte aligned; may be NULL with face_capacity 0 */
+    int32_t*       face_count;        /* one int32, REQUIRED: the true number of faces, also above face_capacity */
+    long long      face_capacity;
+} s2m2_tsdf_mesh_desc;
+size_t s2m2_tsdf_mesh_workspace_bytes(int Nx, int Ny, int Nz);   /* 0: bad dims, or more voxels than the size limit */
+int s2m2_tsdf_mesh(const s2m2_tsdf_mesh_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,13 +57,15 @@
 //
 // A stream of pairs from a moving rig fused into one TSDF volume (s2m2_tsdf_integrate / s2m2_tsdf_extract), a mode of its own:
 //   s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T]
-//                   [--tsdf-min-weight N] [--tsdf-carve] --calib calib.txt --tsdf-ply OUT.ply
+//                   [--tsdf-min-weight N] [--tsdf-carve] --calib calib.txt --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply]
 // Every line of LIST names LEFT.f32 RIGHT.f32 IMAGE.u8 (as above; raw uint8 (1,3,H,W) for the colours) and the twelve numbers of the pose
 //   [R | t], row-major, world -> camera, t in the unit of z; empty lines and lines that start with # are skipped.  The engine (one pair per run)
 //   runs per line and the maps are fused behind it; one extraction follows the last line.  --tsdf-dims: the voxels; --tsdf-voxel: their
 //   size and --tsdf-origin the centre of voxel (0,0,0), both in the unit of z; --tsdf-trunc: the truncation distance (default 4 VS);
 //   --tsdf-min-weight: the frames a voxel needs to count as observed (default 1); --tsdf-carve: also free space in front of the band is
 //   fused.  Honours --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered.  --tsdf-ply: the surface points in --ply's layout.
+//   --tsdf-mesh (K25, s2m2_tsdf_mesh): also the surface as a triangle mesh in --mesh's layout, the vertices being --tsdf-ply's points; one
+//   call behind the extraction; "tsdf_faces" joins the printed line.
 //   LIST is parsed before the engine is loaded.  Prints {"tsdf_frames", "tsdf_points"} on a line of its own.
 #include <hip/hip_runtime.h>
 
@@ -467,7 +469,33 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
         HIP_OK(hipMemcpy(hrec.data(), drec.h, hrec.size(), hipMemcpyDeviceToHost), "download");
     }
     if (!write_ply(o.tsdf_ply_path, hrec.data(), n)) return fail("cannot write the TSDF PLY file");
-    printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d}\n", frames.size(), n);
+    if (!o.tsdf_mesh_path) {
+        printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d}\n", frames.size(), n);
+        return 0;
+    }
+    // --tsdf-mesh (K25): one faces-only call -- the vertices are the records above.  A face takes three of a cell's points, a cell with p points
+    // has at most p - 2 faces and a point lies on the edge of at most four cells: 4 n faces always suffice.
+    const size_t mesh_ws_bytes = s2m2_tsdf_mesh_workspace_bytes(td.Nx, td.Ny, td.Nz);
+    if (mesh_ws_bytes == 0) return fail("--tsdf-mesh: --tsdf-dims too large");
+    const long long fcap = 4LL * n;
+    DeviceBuffer dmws, dfaces, dfcount;
+    if (DeviceBuffer::make(dmws, mesh_ws_bytes) || DeviceBuffer::make(dfcount, sizeof(int32_t)) ||
+        (fcap > 0 && DeviceBuffer::make(dfaces, (size_t)fcap * 3 * sizeof(int32_t))))
+        return 1;
+    s2m2_tsdf_mesh_desc md;
+    memset(&md, 0, sizeof md);
+    md.extract = ed;
+    md.extract.records = nullptr; md.extract.count = nullptr; md.extract.capacity = 0; md.extract.workspace = dmws.h;
+    md.faces = fcap > 0 ? dfaces.h : nullptr; md.face_count = dfcount.as<int32_t>(); md.face_capacity = fcap;
+    if (s2m2_tsdf_mesh(&md, s) != 0) return fail_lib("s2m2_tsdf_mesh failed");
+    HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_mesh");
+    int32_t nf = 0;
+    HIP_OK(hipMemcpy(&nf, dfcount.h, sizeof nf, hipMemcpyDeviceToHost), "download");
+    if (nf > fcap) return fail("--tsdf-mesh: more faces than four per point");
+    std::vector<int32_t> hfaces((size_t)nf * 3);
+    if (nf > 0) HIP_OK(hipMemcpy(hfaces.data(), dfaces.h, hfaces.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+    if (!write_ply_mesh(o.tsdf_mesh_path, hrec.data(), n, hfaces.data(), nf)) return fail("cannot write the TSDF mesh PLY file");
+    printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d, \"tsdf_faces\": %d}\n", frames.size(), n, nf);
     return 0;
 }
 

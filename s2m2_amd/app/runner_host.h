@@ -20,7 +20,7 @@ inline const char* const USAGE =
     "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]"
     " | s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T] "
-    "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
+    "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
     "[--unfiltered]";
 
 // ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
@@ -37,6 +37,7 @@ struct Options {
     const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr, *gt_min_arg = nullptr;
     const char *tsdf_frames_path = nullptr, *tsdf_dims_arg = nullptr, *tsdf_voxel_arg = nullptr, *tsdf_origin_arg = nullptr;
     const char *tsdf_trunc_arg = nullptr, *tsdf_min_weight_arg = nullptr, *tsdf_carve_arg = nullptr, *tsdf_ply_path = nullptr;
+    const char* tsdf_mesh_path = nullptr;
 
     int tsdf_dims[3] = {0, 0, 0}, tsdf_min_weight = 1, tsdf_carve = 0;
     double tsdf_voxel = 0.0, tsdf_trunc = 0.0, tsdf_origin[3] = {0, 0, 0};      // tsdf_trunc: 4 * tsdf_voxel unless --tsdf-trunc
@@ -91,6 +92,7 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--tsdf-min-weight", true, &Options::tsdf_min_weight_arg},
     {"--tsdf-carve", false, &Options::tsdf_carve_arg},
     {"--tsdf-ply", true, &Options::tsdf_ply_path},
+    {"--tsdf-mesh", true, &Options::tsdf_mesh_path},
 };
 
 // "a,b,c": exactly three numbers, nothing behind them
@@ -139,6 +141,8 @@ inline const char* check_tsdf_options(Options& o) {
         o.tsdf_min_weight = (int)n;
     }
     o.tsdf_carve = o.tsdf_carve_arg != nullptr;
+    // K25's size limit: an int32 face count, at most 5 faces per cell
+    if (o.tsdf_mesh_path && d[0] * d[1] * d[2] > 429496729.0) return "--tsdf-mesh: NX*NY*NZ <= 429496729 (an int32 face count)";
     return nullptr;
 }
 
@@ -166,7 +170,7 @@ inline const char* check_options(Options& o) {
     if (o.gt_min_arg) o.gt_min = atof(o.gt_min_arg);
     o.unfiltered = o.unfiltered_arg != nullptr;
     if (o.tsdf_frames_path || o.tsdf_dims_arg || o.tsdf_voxel_arg || o.tsdf_origin_arg || o.tsdf_trunc_arg || o.tsdf_min_weight_arg || o.tsdf_carve_arg ||
-        o.tsdf_ply_path)
+        o.tsdf_ply_path || o.tsdf_mesh_path)
         return check_tsdf_options(o);
     if (o.npos != 3 || o.repeat < 0) return USAGE;
     if (o.mesh_path && !o.calib_path) return "--calib and --mesh come together";

@@ -24,7 +24,8 @@ include/s2m2_hip.h, K23).  Four launches (five with the per-pixel index), no syn
 ``TsdfVolume`` (K24, ``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``) is the first stage that carries state from one pair to the next: a dense
 truncated signed distance volume on the device that ``integrate`` fuses the depth maps of a moving rig into, pose by pose, and whose surface
 ``extract`` returns as points with colours and gradients (the rule: include/s2m2_hip.h, K24).  One launch per call of ``integrate``, two per
-``extract``, no synchronisation, capturable, bit-reproducible.
+``extract``, no synchronisation, capturable, bit-reproducible.  ``extract_mesh`` (K25, ``s2m2_tsdf_mesh``) returns that surface as a triangle
+mesh: ``extract``'s points as vertices and the marching-cubes faces between them (the rule: include/s2m2_hip.h, K25).  Three launches.
 
 A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
@@ -43,6 +44,10 @@ PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty
 PLY_MESH_HEADER = PLY_HEADER.replace("end_header\n", "element face %d\nproperty list uchar int vertex_indices\nend_header\n")
 FACE_DISK_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])        # 13 bytes per face on disk
 RECORD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
+PLY_NORMALS_HEADER = PLY_HEADER.replace("property uchar red", "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red")
+NORMAL_RECORD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
+                                ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
+PLY_MESH_NORMALS_HEADER = PLY_NORMALS_HEADER.replace("end_header\n", "element face %d\nproperty list uchar int vertex_indices\nend_header\n")
 
 
 def write_ply_records(path: str, records) -> int:
@@ -73,47 +78,53 @@ def read_ply_records(path: str) -> np.ndarray:
     return np.frombuffer(body, dtype=RECORD_DTYPE)
 
 
-def write_ply_mesh(path: str, records, faces) -> tuple:
-    """Host function: n vertex records (as for ``write_ply_records``) and an (m,3) integer array of vertex indices -> binary little-endian
-    PLY with ``element face m`` / ``property list uchar int vertex_indices``; returns (n, m)."""
+def write_ply_mesh(path: str, records, faces, normals: bool = False) -> tuple:
+    """Host function: n vertex records (as for ``write_ply_records``; with ``normals`` 28-byte ``NORMAL_RECORD_DTYPE`` records, nx ny nz
+    between the position and the colour) and an (m,3) integer array of vertex indices -> binary little-endian PLY with ``element face m`` /
+    ``property list uchar int vertex_indices``; returns (n, m)."""
     raw = records if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records).tobytes()
-    if len(raw) % 16:
-        raise ValueError("write_ply_mesh: the vertex buffer is not a whole number of 16-byte records")
+    size = NORMAL_RECORD_DTYPE.itemsize if normals else 16
+    if len(raw) % size:
+        raise ValueError(f"write_ply_mesh: the vertex buffer is not a whole number of {size}-byte records")
     faces = np.asarray(faces)
     if faces.size == 0:
         faces = faces.reshape(0, 3)
     if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
         raise ValueError("write_ply_mesh: faces must be an (m,3) integer array")
-    n, m = len(raw) // 16, faces.shape[0]
+    n, m = len(raw) // size, faces.shape[0]
     if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
         raise ValueError(f"write_ply_mesh: a face references a vertex outside 0..{n - 1}")
     disk = np.empty(m, dtype=FACE_DISK_DTYPE)
     disk["n"], disk["v"] = 3, faces
     with open(path, "wb") as f:
-        f.write((PLY_MESH_HEADER % (n, m)).encode("ascii"))
+        f.write(((PLY_MESH_NORMALS_HEADER if normals else PLY_MESH_HEADER) % (n, m)).encode("ascii"))
         f.write(raw)
         f.write(disk.tobytes())
     return n, m
 
 
 def read_ply_mesh(path: str) -> tuple:
-    """The inverse of ``write_ply_mesh`` for files with exactly that layout -> (``RECORD_DTYPE`` array, (m,3) int32 array)."""
+    """The inverse of ``write_ply_mesh`` for files with exactly its layouts -> (``RECORD_DTYPE`` array, or ``NORMAL_RECORD_DTYPE`` for a
+    file with normals, (m,3) int32 array)."""
     raw = open(path, "rb").read()
     end = raw.find(b"end_header\n")
     if not raw.startswith(b"ply\n") or end < 0:
         raise ValueError(f"{path}: not a PLY file")
     head = raw[:end + len(b"end_header\n")].decode("ascii")
     counts = [int(line.split()[2]) for line in head.split("\n") if line.startswith("element")]
-    if len(counts) != 2 or head != PLY_MESH_HEADER % tuple(counts):
+    layouts = [(h, t) for h, t in ((PLY_MESH_HEADER, RECORD_DTYPE), (PLY_MESH_NORMALS_HEADER, NORMAL_RECORD_DTYPE))
+               if len(counts) == 2 and head == h % tuple(counts)]
+    if not layouts:
         raise ValueError(f"{path}: not the vertex + triangle layout of write_ply_mesh")
     n, m = counts
+    vertex = layouts[0][1]
     body = raw[len(head):]
-    if len(body) != 16 * n + 13 * m:
+    if len(body) != vertex.itemsize * n + 13 * m:
         raise ValueError(f"{path}: {n} vertices and {m} faces declared, {len(body)} bytes of data")
-    disk = np.frombuffer(body, dtype=FACE_DISK_DTYPE, offset=16 * n)
+    disk = np.frombuffer(body, dtype=FACE_DISK_DTYPE, offset=vertex.itemsize * n)
     if m and not (disk["n"] == 3).all():
         raise ValueError(f"{path}: a face is not a triangle")
-    return np.frombuffer(body, dtype=RECORD_DTYPE, count=n), np.ascontiguousarray(disk["v"])
+    return np.frombuffer(body, dtype=vertex, count=n), np.ascontiguousarray(disk["v"])
 
 
 def read_calib_file(path: str) -> Dict[str, object]:
@@ -419,11 +430,6 @@ def voxelize(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: t
     return VoxelCloud(records, count, weights, index, stats)
 
 
-PLY_NORMALS_HEADER = PLY_HEADER.replace("property uchar red", "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red")
-NORMAL_RECORD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
-                                ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
-
-
 class TsdfSurface(PointCloud):
     """What ``TsdfVolume.extract`` returns: a ``PointCloud`` with one pair (b = 0) whose records are the surface points of the volume in
     ascending voxel order -- ``records`` (1, capacity, 4) int32, ``count`` (1) int32 (the true number of points, also above capacity) -- plus
@@ -459,6 +465,47 @@ class TsdfSurface(PointCloud):
         return len(out)
 
 
+class TsdfMesh(TsdfSurface):
+    """What ``TsdfVolume.extract_mesh`` returns: a ``TsdfSurface`` (the vertices: exactly ``extract``'s points) plus ``faces_buf``
+    (face_capacity, 3) int32 vertex ranks, in ascending order of their cells and wound so that the normals point to free space, and
+    ``face_count`` (1) int32 on the device (the true number of faces, also above face_capacity)."""
+
+    def __init__(self, records: torch.Tensor, count: torch.Tensor, gradients_buf: Optional[torch.Tensor], faces_buf: torch.Tensor,
+                 face_count: torch.Tensor):
+        super().__init__(records, count, gradients_buf)
+        self.faces_buf, self.face_count = faces_buf, face_count
+
+    def face_capacity(self) -> int:
+        return self.faces_buf.shape[0]
+
+    def face_size(self) -> int:
+        """faces stored: min(face_count, face_capacity) -- reads ``face_count`` on the host (synchronises)"""
+        return min(int(self.face_count.item()), self.face_capacity())
+
+    def faces(self) -> torch.Tensor:
+        """(n,3) int32 view of the stored faces.  Raises when the vertices overflowed: the faces hold true ranks and would reference vertices
+        that were not stored."""
+        n = int(self.count[0].item())
+        if n > self.capacity:
+            raise ValueError(f"TsdfMesh.faces: {n} vertices but a capacity of {self.capacity}: the faces reference unstored vertices")
+        return self.faces_buf[:self.face_size()]
+
+    def write_ply(self, path: str, normals: bool = False) -> tuple:
+        """vertices and faces in ``write_ply_mesh``'s layout -> (vertices, faces) written; ``normals``: nx, ny, nz per vertex from the
+        normalised gradients, between the position and the colour"""
+        faces = self.faces().cpu().numpy()
+        rec = self.records[0, :self.size()].cpu().numpy()
+        if not normals:
+            return write_ply_mesh(path, rec, faces)
+        rec = rec.view(RECORD_DTYPE).ravel()
+        out = np.empty(len(rec), dtype=NORMAL_RECORD_DTYPE)
+        for name in RECORD_DTYPE.names:
+            out[name] = rec[name]
+        nrm = self.normals().cpu().numpy()
+        out["nx"], out["ny"], out["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+        return write_ply_mesh(path, out, faces, normals=True)
+
+
 class TsdfVolume:
     """A truncated signed distance volume on the device (K24, ``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``; the rule: include/s2m2_hip.h,
     K24): ``dims`` = (Nx, Ny, Nz) voxels of ``voxel_size`` (the unit of z), ``origin`` the centre of voxel (0,0,0) in the world frame,
@@ -483,6 +530,7 @@ class TsdfVolume:
         self.device = torch.device(device)
         self.buffer = torch.zeros((Nz, Ny, Nx, 4), device=self.device, dtype=torch.int32)
         self._workspace = None
+        self._mesh_workspace = None
 
     def reset(self) -> None:
         self.buffer.zero_()
@@ -539,3 +587,26 @@ class TsdfVolume:
             hip.tsdf_extract(self.buffer, origin=self.origin, voxel_size=self.voxel_size, min_weight=min_weight, workspace=self._workspace,
                              records=records, gradients=gradients, count=count)
         return TsdfSurface(records[None], count, gradients)
+
+    def extract_mesh(self, min_weight: int = 1, capacity: Optional[int] = None, face_capacity: Optional[int] = None,
+                     want_gradients: bool = True) -> TsdfMesh:
+        """The surface as a triangle mesh (K25, ``s2m2_tsdf_mesh``): ``extract``'s points as vertices, joined by marching cubes over the cells
+        whose eight voxels all have at least ``min_weight`` frames.  capacity None = Nx*Ny*Nz vertices as for ``extract``; face_capacity None =
+        2*Nx*Ny*Nz faces (the true bound is 5 per cell, which no surface reaches; ``face_count`` tells).  It keeps a workspace of its own (4
+        bytes per voxel).  Three launches, no synchronisation, capturable."""
+        Nx, Ny, Nz = self.dims
+        cap = Nx * Ny * Nz if capacity is None else int(capacity)
+        fcap = 2 * Nx * Ny * Nz if face_capacity is None else int(face_capacity)
+        if cap < 0 or fcap < 0:
+            raise ValueError("TsdfVolume.extract_mesh: negative capacity")
+        if self._mesh_workspace is None:
+            self._mesh_workspace = torch.empty((hip.tsdf_mesh_workspace_bytes(Nx, Ny, Nz),), device=self.device, dtype=torch.uint8)
+        records = torch.empty((cap, 4), device=self.device, dtype=torch.int32)
+        gradients = torch.empty((cap, 3), device=self.device, dtype=torch.float32) if want_gradients else None
+        count = torch.empty((1,), device=self.device, dtype=torch.int32)
+        faces = torch.empty((fcap, 3), device=self.device, dtype=torch.int32)
+        face_count = torch.empty((1,), device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            hip.tsdf_mesh(self.buffer, origin=self.origin, voxel_size=self.voxel_size, min_weight=min_weight, workspace=self._mesh_workspace,
+                          records=records, gradients=gradients, count=count, faces=faces, face_count=face_count)
+        return TsdfMesh(records[None], count, gradients, faces, face_count)

@@ -10,17 +10,12 @@
 //   tsdf_count_kernel        a block owns a tile of kTsdfTileVoxels consecutive voxels and counts its surface points
 //   tsdf_store_kernel        K15's scatter: tile_prefix, raster_rank_step with the three axis flags of a voxel, records and gradients
 // A surface point is a sign change of the tsdf between an observed voxel and its observed +1 neighbour along x, y or z (tsdf_crossings), which
-// both extraction launches evaluate alike.
+// both extraction launches evaluate alike.  The extraction's device functions and descriptor checks are in tsdf_device.h, which K25
+// (tsdf_mesh.hip) shares.
 #include "cloud_device.h"
-#include "launch.h"
-#include "plan.h"
-
-#include <math.h>
+#include "tsdf_device.h"
 
 namespace s2m2 {
-
-constexpr int kTsdfTileVoxels = 8192;                    // voxels of one extraction tile (32 block steps)
-constexpr long long kTsdfMaxVoxels = 1LL << 29;          // voxel indices, 3 points per voxel and 16 bytes per voxel from 32-bit indices
 
 struct TsdfParams {
     CloudParams c;              // the inputs of K15 (its outputs are null)
@@ -29,18 +24,6 @@ struct TsdfParams {
     int B, Nx, Ny, Nz;
     int max_weight, carve;
     float gx, gy, gz, vs, trunc;    // centre of voxel (0,0,0), voxel size, truncation distance
-};
-
-struct TsdfExtractParams {
-    const uint4_t* volume;
-    uint4_t* records;
-    float* gradients;
-    int* count;
-    int* tile_counts;
-    int Nx, Ny, Nz, n, tiles;   // n = Nx * Ny * Nz
-    int min_weight;
-    long long capacity;
-    float gx, gy, gz, vs;
 };
 
 // ---------------------------------------------------------------------------------------------------------------- integrate
@@ -111,141 +94,23 @@ __global__ __launch_bounds__(kRasterThreads) void tsdf_integrate_kernel(const Ts
 
 // ---------------------------------------------------------------------------------------------------------------- extract
 
-// tsdf and weight of voxel lin (the first 8 bytes of its record)
-__device__ __forceinline__ void tsdf_tw(const TsdfExtractParams& p, int lin, float& t, int& w) {
-    typedef unsigned uint2_t __attribute__((ext_vector_type(2)));
-    const uint2_t o = *(const __attribute__((address_space(1))) uint2_t*)(p.volume + lin);
-    t = __builtin_bit_cast(float, o[0]);
-    w = (int)o[1];
-}
-
-// voxel lin = (i, j, k), lin < n: its tsdf t0, whether it is observed, and per axis a the tsdf t1[a] of the +1 neighbour and whether the pair
-// (v0, v1) emits a point: v1 inside the grid and observed, and a sign change between them
-__device__ __forceinline__ void tsdf_crossings(const TsdfExtractParams& p, int lin, int i, int j, int k, float& t0, float (&t1)[3], bool (&emit)[3]) {
-    int w0;
-    tsdf_tw(p, lin, t0, w0);
-    const bool inside[3] = {i + 1 < p.Nx, j + 1 < p.Ny, k + 1 < p.Nz};
-    const int step[3] = {1, p.Nx, p.Nx * p.Ny};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        emit[a] = false;
-        t1[a] = 0.f;
-        if (w0 >= p.min_weight && inside[a]) {
-            int w1;
-            tsdf_tw(p, lin + step[a], t1[a], w1);
-            emit[a] = w1 >= p.min_weight && ((t0 < 0.f) != (t1[a] < 0.f));
-        }
-    }
-}
-
-// lin -> (i, j, k): 32-bit divisions (lin < 2^29)
-__device__ __forceinline__ void tsdf_coords(const TsdfExtractParams& p, int lin, int& i, int& j, int& k) {
-    const unsigned t = (unsigned)lin / (unsigned)p.Nx;
-    i = lin - (int)t * p.Nx;
-    k = (int)(t / (unsigned)p.Ny);
-    j = (int)t - k * p.Ny;
-}
-
 __global__ __launch_bounds__(kRasterThreads) void tsdf_count_kernel(const TsdfExtractParams p) {
     __shared__ int red[kRasterWaves];
     const int tile = blockIdx.x;
     const int end = min(p.n, (tile + 1) * kTsdfTileVoxels);
     int n = 0;
-    for (int lin = tile * kTsdfTileVoxels + threadIdx.x; lin < end; lin += kRasterThreads) {
-        int i, j, k;
-        tsdf_coords(p, lin, i, j, k);
-        float t0, t1[3];
-        bool emit[3];
-        tsdf_crossings(p, lin, i, j, k, t0, t1, emit);
-        n += (int)emit[0] + (int)emit[1] + (int)emit[2];
-    }
+    for (int lin = tile * kTsdfTileVoxels + threadIdx.x; lin < end; lin += kRasterThreads) n += tsdf_points_of(p, lin);
     n = block_sum_int(n, red);
     if (threadIdx.x == 0) p.tile_counts[tile] = n;
 }
 
-// the tsdf of the neighbour of sel = (i, j, k) at distance `d` voxels along an axis (step = the axis' stride in voxels, pos / extent = sel's
-// coordinate and the grid's size along it): the neighbour's where it is inside the grid and observed, ts otherwise
-__device__ __forceinline__ float tsdf_neighbour(const TsdfExtractParams& p, int lin, int step, int pos, int extent, int d, float ts) {
-    if (pos + d < 0 || pos + d >= extent) return ts;
-    float t;
-    int w;
-    tsdf_tw(p, lin + d * step, t, w);
-    return w >= p.min_weight ? t : ts;
-}
-
 __global__ __launch_bounds__(kRasterThreads) void tsdf_store_kernel(const TsdfExtractParams p) {
-#pragma clang fp contract(off)
     __shared__ int red[kRasterWaves];
     __shared__ int wave_n[2][kRasterWaves];
-    const int tile = blockIdx.x;
-    long long base = tile_prefix(p.tile_counts, tile, red);
-    const int first = tile * kTsdfTileVoxels, end = min(p.n, first + kTsdfTileVoxels);
-    int step = 0;
-    for (int lin0 = first; lin0 < end; lin0 += kRasterThreads) {        // block-uniform: every thread takes every step
-        const int lin = lin0 + threadIdx.x;
-        int i = 0, j = 0, k = 0;
-        float t0 = 0.f, t1[3] = {0.f, 0.f, 0.f};
-        bool emit[3] = {false, false, false};
-        if (lin < end) {
-            tsdf_coords(p, lin, i, j, k);
-            tsdf_crossings(p, lin, i, j, k, t0, t1, emit);
-        }
-        long long r = raster_rank_step(emit, wave_n, step++, base);
-        const int stride[3] = {1, p.Nx, p.Nx * p.Ny};
-        const int pos[3] = {i, j, k};
-        const int extent[3] = {p.Nx, p.Ny, p.Nz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (!emit[a]) continue;
-            if (r < p.capacity) {
-                const float s = t0 / (t0 - t1[a]);
-                float xyz[3] = {p.gx + (float)i * p.vs, p.gy + (float)j * p.vs, p.gz + (float)k * p.vs};
-                xyz[a] = xyz[a] + s * p.vs;
-                const bool far = fabsf(t1[a]) < fabsf(t0);               // sel = v1
-                const int ls = far ? lin + stride[a] : lin;
-                const float ts = far ? t1[a] : t0;
-                if (p.records) {
-                    const uint4_t o = *(const __attribute__((address_space(1))) uint4_t*)(p.volume + ls);
-                    const unsigned cr = ((o[2] & 0xffffu) + 128u) >> 8, cg = ((o[2] >> 16) + 128u) >> 8, cb = ((o[3] & 0xffffu) + 128u) >> 8;
-                    const uint4_t rec = {__builtin_bit_cast(unsigned, xyz[0]), __builtin_bit_cast(unsigned, xyz[1]), __builtin_bit_cast(unsigned, xyz[2]),
-                                         cr | (cg << 8) | (cb << 16) | 0xff000000u};
-                    p.records[r] = rec;
-                }
-                if (p.gradients) {
-#pragma unroll
-                    for (int b = 0; b < 3; ++b) {
-                        const int ps = pos[b] + (far && a == b ? 1 : 0);
-                        const float tp = tsdf_neighbour(p, ls, stride[b], ps, extent[b], 1, ts);
-                        const float tm = tsdf_neighbour(p, ls, stride[b], ps, extent[b], -1, ts);
-                        p.gradients[(size_t)r * 3 + b] = tp - tm;
-                    }
-                }
-            }
-            ++r;
-        }
-    }
-    if (p.count && tile == p.tiles - 1 && threadIdx.x == 0) *p.count = (int)base;
+    tsdf_store_tile<false>(p, nullptr, red, wave_n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-
-static bool tsdf_finite_f32(double x) { return isfinite(x) && isfinite((float)x); }
-static bool tsdf_positive_f32(double x) { return tsdf_finite_f32(x) && x > 0.0 && (float)x > 0.f; }
-
-static bool tsdf_dims_ok(int Nx, int Ny, int Nz) {
-    return Nx > 0 && Ny > 0 && Nz > 0 && (long long)Nx * Ny < kTsdfMaxVoxels && (long long)Nx * Ny * Nz < kTsdfMaxVoxels;
-}
-
-// the checks that both entry points make of a volume: the buffer, the dims, the grid's placement
-static int tsdf_check_volume(const char* what, const void* volume, int Nx, int Ny, int Nz, const double* origin, double voxel_size) {
-    S2M2_REQUIRE(volume != nullptr, "%s: null pointer (volume)", what);
-    S2M2_REQUIRE(((uintptr_t)volume & 15) == 0, "%s: the volume must be 16-byte aligned", what);
-    S2M2_REQUIRE(Nx > 0 && Ny > 0 && Nz > 0, "%s: non-positive dims Nx=%d Ny=%d Nz=%d", what, Nx, Ny, Nz);
-    S2M2_REQUIRE(tsdf_dims_ok(Nx, Ny, Nz), "%s: dims too large (Nx*Ny*Nz < 2^29)", what);
-    S2M2_REQUIRE(tsdf_positive_f32(voxel_size), "%s: voxel_size must be finite and > 0 in fp32 (%g)", what, voxel_size);
-    S2M2_REQUIRE(tsdf_finite_f32(origin[0]) && tsdf_finite_f32(origin[1]) && tsdf_finite_f32(origin[2]), "%s: the origin must be finite (also in fp32)", what);
-    return 0;
-}
 
 static int tsdf_integrate_impl(const s2m2_tsdf_desc* d, void* stream) {
     S2M2_REQUIRE(d != nullptr, "tsdf_integrate: null descriptor");
@@ -288,29 +153,11 @@ static int tsdf_integrate_impl(const s2m2_tsdf_desc* d, void* stream) {
 static int tsdf_extract_impl(const s2m2_tsdf_extract_desc* d, void* stream) {
     S2M2_REQUIRE(d != nullptr, "tsdf_extract: null descriptor");
     if (int rc = refuse_while_recording("tsdf_extract")) return rc;
-    if (int rc = tsdf_check_volume("tsdf_extract", d->volume, d->Nx, d->Ny, d->Nz, d->origin, d->voxel_size)) return rc;
-    S2M2_REQUIRE(d->min_weight >= 1, "tsdf_extract: min_weight must be >= 1 (%d)", d->min_weight);
-    S2M2_REQUIRE(d->records || d->gradients || d->count, "tsdf_extract: no output requested (records, gradients and count are all null pointers)");
-    S2M2_REQUIRE(d->capacity >= 0, "tsdf_extract: negative capacity %lld", d->capacity);
-    S2M2_REQUIRE(d->records || d->gradients || d->capacity == 0, "tsdf_extract: null pointers (records and gradients) with capacity %lld", d->capacity);
-    S2M2_REQUIRE(((uintptr_t)d->records & 15) == 0, "tsdf_extract: records must be 16-byte aligned");
-    S2M2_REQUIRE((((uintptr_t)d->gradients | (uintptr_t)d->count) & 3) == 0, "tsdf_extract: gradients and count must be 4-byte aligned");
+    TsdfExtractParams p;
+    if (int rc = tsdf_extract_params("tsdf_extract", d, true, p)) return rc;
     S2M2_REQUIRE(d->workspace != nullptr, "tsdf_extract: null workspace (s2m2_tsdf_workspace_bytes)");
     S2M2_REQUIRE(((uintptr_t)d->workspace & 3) == 0, "tsdf_extract: the workspace must be 4-byte aligned");
-
-    TsdfExtractParams p;
-    p.volume = static_cast<const uint4_t*>(d->volume);
-    p.records = static_cast<uint4_t*>(d->records);
-    p.gradients = d->gradients;
-    p.count = d->count;
     p.tile_counts = static_cast<int*>(d->workspace);
-    p.Nx = d->Nx; p.Ny = d->Ny; p.Nz = d->Nz;
-    p.n = d->Nx * d->Ny * d->Nz;
-    p.tiles = (p.n + kTsdfTileVoxels - 1) / kTsdfTileVoxels;
-    p.min_weight = d->min_weight;
-    p.capacity = d->capacity;
-    p.gx = (float)d->origin[0]; p.gy = (float)d->origin[1]; p.gz = (float)d->origin[2];
-    p.vs = (float)d->voxel_size;
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(p.tiles), block(kRasterThreads);

@@ -160,6 +160,11 @@ class TsdfExtractDesc(ctypes.Structure):
                 ("min_weight", _i), ("capacity", _ll), ("origin", ctypes.c_double * 3), ("voxel_size", ctypes.c_double)]
 
 
+class TsdfMeshDesc(ctypes.Structure):
+    """mirror of s2m2_tsdf_mesh_desc (include/s2m2_hip.h): K25, the surface of a TSDF volume as a triangle mesh"""
+    _fields_ = [("extract", TsdfExtractDesc), ("faces", _vp), ("face_count", _vp), ("face_capacity", _ll)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -285,6 +290,8 @@ SIGNATURES = {
     "s2m2_tsdf_tile_voxels": (_i, [_i, _i, _i]),
     "s2m2_tsdf_integrate": (_i, [ctypes.POINTER(TsdfDesc), _vp]),
     "s2m2_tsdf_extract": (_i, [ctypes.POINTER(TsdfExtractDesc), _vp]),
+    "s2m2_tsdf_mesh_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_tsdf_mesh": (_i, [ctypes.POINTER(TsdfMeshDesc), _vp]),
 }
 
 
@@ -1392,5 +1399,5 @@ from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
 from .hip_segment import segment, segment_tile, segment_workspace_bytes  # noqa: E402,F401
 # K23 (s2m2_voxel): likewise, from hip_voxel.py
 from .hip_voxel import voxel, voxel_home_slot, voxel_slots, voxel_tile_rows, voxel_workspace_bytes  # noqa: E402,F401
-# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract): likewise, from hip_tsdf.py
-from .hip_tsdf import tsdf_extract, tsdf_integrate, tsdf_tile_voxels, tsdf_workspace_bytes  # noqa: E402,F401
+# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract) and K25 (s2m2_tsdf_mesh): likewise, from hip_tsdf.py
+from .hip_tsdf import tsdf_extract, tsdf_integrate, tsdf_mesh, tsdf_mesh_workspace_bytes, tsdf_tile_voxels, tsdf_workspace_bytes  # noqa: E402,F401

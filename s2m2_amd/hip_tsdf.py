@@ -1,6 +1,8 @@
-"""K24 (``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``, csrc/tsdf.hip): depth maps fused into a TSDF volume, and the volume's surface points.
+"""K24 (``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``, csrc/tsdf.hip): depth maps fused into a TSDF volume, and the volume's surface points;
+K25 (``s2m2_tsdf_mesh``, csrc/tsdf_mesh.hip): that surface as a triangle mesh.
 The descriptor mirrors and the signatures are in hip.py with all the others (``hip.load()`` binds every symbol there); this module holds the
-wrappers, which hip.py re-exports as ``hip.tsdf_integrate``, ``hip.tsdf_extract``, ``hip.tsdf_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
+wrappers, which hip.py re-exports as ``hip.tsdf_integrate``, ``hip.tsdf_extract``, ``hip.tsdf_mesh``, ``hip.tsdf_workspace_bytes``,
+``hip.tsdf_mesh_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
 import ctypes
 import math
 from typing import Optional, Sequence, Tuple
@@ -57,6 +59,33 @@ def tsdf_integrate(volume: torch.Tensor, disp: torch.Tensor, occ: torch.Tensor, 
         _h._check(_h.load().s2m2_tsdf_integrate(ctypes.byref(d), _h._stream()), "s2m2_tsdf_integrate")
 
 
+def _extract_operands(what: str, d, volume: torch.Tensor, origin, voxel_size, min_weight, records, gradients, count) -> Optional[int]:
+    """the extraction descriptor ``d`` (a TsdfExtractDesc) but for its workspace, from the operands that tsdf_extract and tsdf_mesh share
+    -> the capacity of records / gradients (None: neither was passed)"""
+    d.Nx, d.Ny, d.Nz = _volume(what, volume)
+    d.origin, d.voxel_size = _placement(what, origin, voxel_size)
+    if int(min_weight) != min_weight or min_weight < 1:
+        raise ValueError(f"{what}: min_weight must be an integer >= 1, got {min_weight}")
+    d.min_weight = int(min_weight)
+    capacity = None
+    if records is not None:
+        if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 4:
+            raise ValueError(f"{what}: records must be a (capacity, 4) int32 tensor")
+        capacity = records.shape[0]
+    if gradients is not None:
+        if gradients.dtype != torch.float32 or gradients.dim() != 2 or gradients.shape[1] != 3 or capacity not in (None, gradients.shape[0]):
+            raise ValueError(f"{what}: gradients must be a (capacity, 3) fp32 tensor, with the capacity of records")
+        capacity = gradients.shape[0]
+    d.capacity = capacity or 0
+    if capacity:
+        d.records, d.gradients = _h._ptr(records), _h._ptr(gradients)
+    if count is not None:
+        _h._vec(count, 1, f"{what}: count", dtype=torch.int32)
+        d.count = count.data_ptr()
+    d.volume = volume.data_ptr()
+    return capacity
+
+
 def tsdf_extract(volume: torch.Tensor, *, origin: Sequence[float], voxel_size: float, min_weight: int = 1, workspace: torch.Tensor,
                  records: Optional[torch.Tensor] = None, gradients: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None) -> None:
     """s2m2_tsdf_extract (K24): the surface points of ``volume`` (Nz,Ny,Nx,4) int32 -> the outputs the caller allocated: ``records``
@@ -65,38 +94,52 @@ def tsdf_extract(volume: torch.Tensor, *, origin: Sequence[float], voxel_size: f
     _h._resident("tsdf_extract", volume, workspace, records, gradients, count)
     _h._contig("tsdf_extract", volume, workspace, records, gradients, count)
     d = _h.TsdfExtractDesc()
-    d.Nx, d.Ny, d.Nz = _volume("tsdf_extract", volume)
-    d.origin, d.voxel_size = _placement("tsdf_extract", origin, voxel_size)
-    if int(min_weight) != min_weight or min_weight < 1:
-        raise ValueError(f"tsdf_extract: min_weight must be an integer >= 1, got {min_weight}")
-    d.min_weight = int(min_weight)
-    capacity = None
-    if records is not None:
-        if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 4:
-            raise ValueError("tsdf_extract: records must be a (capacity, 4) int32 tensor")
-        capacity = records.shape[0]
-    if gradients is not None:
-        if gradients.dtype != torch.float32 or gradients.dim() != 2 or gradients.shape[1] != 3 or capacity not in (None, gradients.shape[0]):
-            raise ValueError("tsdf_extract: gradients must be a (capacity, 3) fp32 tensor, with the capacity of records")
-        capacity = gradients.shape[0]
-    d.capacity = capacity or 0
-    if capacity:
-        d.records, d.gradients = _h._ptr(records), _h._ptr(gradients)
-    if count is not None:
-        _h._vec(count, 1, "tsdf_extract: count", dtype=torch.int32)
-        d.count = count.data_ptr()
+    capacity = _extract_operands("tsdf_extract", d, volume, origin, voxel_size, min_weight, records, gradients, count)
     if not capacity and count is None:
         raise ValueError("tsdf_extract: no output requested")
     need = tsdf_workspace_bytes(d.Nx, d.Ny, d.Nz)
     if workspace is None or workspace.nbytes < need:
         raise ValueError(f"tsdf_extract: a workspace of {need} bytes is required")
-    d.workspace, d.volume = workspace.data_ptr(), volume.data_ptr()
+    d.workspace = workspace.data_ptr()
     with torch.cuda.device(volume.device):
         _h._check(_h.load().s2m2_tsdf_extract(ctypes.byref(d), _h._stream()), "s2m2_tsdf_extract")
 
 
+def tsdf_mesh(volume: torch.Tensor, *, origin: Sequence[float], voxel_size: float, min_weight: int = 1, workspace: torch.Tensor,
+              face_count: torch.Tensor, faces: Optional[torch.Tensor] = None, records: Optional[torch.Tensor] = None,
+              gradients: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None) -> None:
+    """s2m2_tsdf_mesh (K25): the surface of ``volume`` (Nz,Ny,Nx,4) int32 as a triangle mesh -> the outputs the caller allocated: ``faces``
+    (face_capacity, 3) int32 vertex ranks and ``face_count`` (1) int32 (required: the true number of faces), plus ``tsdf_extract``'s
+    ``records``, ``gradients`` and ``count`` (the vertices, each optional, byte-identical to ``tsdf_extract``'s); ``workspace``:
+    ``tsdf_mesh_workspace_bytes`` bytes.  Thin: no allocation, no synchronisation."""
+    _h._resident("tsdf_mesh", volume, workspace, face_count, faces, records, gradients, count)
+    _h._contig("tsdf_mesh", volume, workspace, face_count, faces, records, gradients, count)
+    d = _h.TsdfMeshDesc()
+    _extract_operands("tsdf_mesh", d.extract, volume, origin, voxel_size, min_weight, records, gradients, count)
+    if face_count is None:
+        raise ValueError("tsdf_mesh: face_count is required")
+    _h._vec(face_count, 1, "tsdf_mesh: face_count", dtype=torch.int32)
+    d.face_count = face_count.data_ptr()
+    if faces is not None:
+        if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise ValueError("tsdf_mesh: faces must be a (face_capacity, 3) int32 tensor")
+        d.face_capacity = faces.shape[0]
+        d.faces = _h._ptr(faces) if faces.shape[0] else None
+    need = tsdf_mesh_workspace_bytes(d.extract.Nx, d.extract.Ny, d.extract.Nz)
+    if workspace is None or workspace.nbytes < need:
+        raise ValueError(f"tsdf_mesh: a workspace of {need} bytes is required")
+    d.extract.workspace = workspace.data_ptr()
+    with torch.cuda.device(volume.device):
+        _h._check(_h.load().s2m2_tsdf_mesh(ctypes.byref(d), _h._stream()), "s2m2_tsdf_mesh")
+
+
 def tsdf_workspace_bytes(Nx: int, Ny: int, Nz: int) -> int:
     return _h._extent_query("s2m2_tsdf_workspace_bytes", "tsdf", Nx=Nx, Ny=Ny, Nz=Nz)
+
+
+def tsdf_mesh_workspace_bytes(Nx: int, Ny: int, Nz: int) -> int:
+    """bytes of ``tsdf_mesh``'s workspace: 4 per voxel and 8 per tile; refuses more than (2^31 - 1) / 5 voxels"""
+    return _h._extent_query("s2m2_tsdf_mesh_workspace_bytes", "tsdf_mesh", Nx=Nx, Ny=Ny, Nz=Nz)
 
 
 def tsdf_tile_voxels(Nx: int, Ny: int, Nz: int) -> int:

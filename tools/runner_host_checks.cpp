@@ -328,6 +328,16 @@ int main(int argc, char** argv) {
         std::vector<std::string> pair = full;
         pair.insert(pair.begin(), {"l.f32", "r.f32"});
         CHECK(tsdf(pair, o4).find("takes ENGINE alone") != std::string::npos);
+        // --tsdf-mesh (K25): an option of the mode, with the size limit of an int32 face count
+        std::vector<std::string> meshed = full;
+        meshed.insert(meshed.end(), {"--tsdf-mesh", "m.ply"});
+        Options o5, o6, o7;
+        CHECK(tsdf(meshed, o5) == "engine" && std::string(o5.tsdf_mesh_path) == "m.ply" && o.tsdf_mesh_path == nullptr);
+        CHECK(tsdf({"--tsdf-mesh", "m.ply"}, o6).find("need --tsdf-frames") != std::string::npos);
+        for (size_t i = 0; i + 1 < meshed.size(); ++i)
+            if (meshed[i] == "--tsdf-dims") meshed[i + 1] = "1024,1024,410";
+        CHECK(tsdf(meshed, o7).find("--tsdf-mesh: NX*NY*NZ <= 429496729") == 0);
+        CHECK(with("--tsdf-dims", "1024,1024,410") == "engine");
 
         std::vector<TsdfFrame> fr;
         put("frames.txt", "# head\n\nl0.f32 r0.f32 i0.u8 1 0 0 0.5 0 1 0 -0.25 0 0 1 2\n   l1.f32 r1.f32 i1.u8 1 0 0 0 0 1 0 0 0 0 1 0   \n");

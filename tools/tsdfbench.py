@@ -24,6 +24,14 @@ Extract: the surface points of the volumes above after the B = 4 call, against n
 result); the counts are compared.
 
     python tools/tsdfbench.py [--steps 20] [--torch-steps 3] [--repeats 5] [--forward] [--dims 256,512] [--out profiles/tsdf/tsdfbench.txt]
+
+--mesh (K25, s2m2_tsdf_mesh; default --out profiles/tsdf/tsdfmesh.txt) measures the triangle mesh instead, on the same volumes (the B = 4, carve 1
+call of each scene, fused once): K25, s2m2_tsdf_extract alone on the same volume (what the triangles cost on top of the vertices), and the same
+faces composed from torch ops -- the case index from eight shifted comparisons, a gather from the case table, `nonzero` over the cells, and the
+rank map by a `cumsum` over the emit flags -- which is what a user can do today without K25.  The composition's faces are compared with K25's
+once per volume, at the timed size.  MANDATORY BYTES of K25: the volume read once (16 B per voxel) plus the outputs written (16 + 12 B per vertex,
+12 B per face); over the time they are printed as a share of the same 6.29 TB/s copy rate.  K25 reads the volume in each of its three launches and
+writes and reads a rank map of 4 B per voxel, which the figure leaves out on purpose: it is the traffic a perfect kernel would need.
 """
 import argparse
 import os
@@ -114,6 +122,101 @@ def torch_extract(torch, vol, origin, vs, min_weight):
     return tuple(torch.cat([o[c] for o in out]) for c in range(3))
 
 
+def mesh_tables(torch, device="cuda"):
+    """the case table of s2m2_amd/mc_table.py as device tensors: triangles per case (256), their edges (256, 5, 3), and per edge its axis and the
+    offset (dz, dy, dx) of its base corner"""
+    from s2m2_amd import mc_table
+    table = mc_table.build_table()
+    most = mc_table.max_triangles(table)
+    count = torch.tensor([len(t) for t in table], device=device, dtype=torch.int64)
+    edges = torch.zeros((256, most, 3), device=device, dtype=torch.int64)
+    for case, tris in enumerate(table):
+        for n, tri in enumerate(tris):
+            edges[case, n] = torch.tensor(tri)
+    axis = torch.tensor([a for a, _ in mc_table.EDGES], device=device, dtype=torch.int64)
+    base = torch.tensor([[b >> 2, b >> 1 & 1, b & 1] for _, b in mc_table.EDGES], device=device, dtype=torch.int64)
+    return count, edges, axis, base
+
+
+def torch_mesh_faces(torch, vol, min_weight, tables):
+    """K25's faces from torch ops -> (m, 3) int32 vertex ranks, in K25's order"""
+    count, edges, axis, base = tables
+    Nz, Ny, Nx, _ = vol.shape
+    t, obs = vol[..., 0].view(torch.float32), vol[..., 1] >= min_weight
+    neg = t < 0
+    case = torch.zeros((Nz - 1, Ny - 1, Nx - 1), device=vol.device, dtype=torch.int64)
+    valid = torch.ones_like(case, dtype=torch.bool)
+    for c in range(8):
+        dx, dy, dz = c & 1, c >> 1 & 1, c >> 2
+        case |= neg[dz:Nz - 1 + dz, dy:Ny - 1 + dy, dx:Nx - 1 + dx].long() << c
+        valid &= obs[dz:Nz - 1 + dz, dy:Ny - 1 + dy, dx:Nx - 1 + dx]
+    emit = torch.zeros((Nz, Ny, Nx, 3), device=vol.device, dtype=torch.int32)
+    emit[:, :, :-1, 0] = obs[:, :, :-1] & obs[:, :, 1:] & (neg[:, :, :-1] != neg[:, :, 1:])
+    emit[:, :-1, :, 1] = obs[:, :-1] & obs[:, 1:] & (neg[:, :-1] != neg[:, 1:])
+    emit[:-1, :, :, 2] = obs[:-1] & obs[1:] & (neg[:-1] != neg[1:])
+    flat = emit.reshape(-1)
+    rank = torch.cumsum(flat, 0, dtype=torch.int32) - flat                # (voxel, axis) -> the rank of its point
+    per_cell = torch.where(valid, count[case], 0)
+    cells = torch.nonzero(per_cell)                                       # synchronises; ascending lin
+    k, j, i = cells[:, 0], cells[:, 1], cells[:, 2]
+    cs, per = case[k, j, i], per_cell[k, j, i]
+    which = torch.repeat_interleave(torch.arange(len(cs), device=vol.device), per)
+    tri = torch.arange(len(which), device=vol.device) - torch.repeat_interleave(torch.cumsum(per, 0) - per, per)
+    e = edges[cs[which], tri]                                             # (m, 3) edge numbers
+    off = base[e]                                                         # (m, 3, 3)
+    voxel = ((k[which, None] + off[..., 0]) * Ny + j[which, None] + off[..., 1]) * Nx + i[which, None] + off[..., 2]
+    return rank[voxel * 3 + axis[e]]
+
+
+def mesh_main(a, torch, hip, say) -> None:
+    from tools.kbench import captured, spread, timed
+    tables = mesh_tables(torch)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    vv, uu = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32), indexing="ij")
+    depth = dict(plane=torch.full((H, W), 2.0, device="cuda"), two=torch.where(uu < W // 2, 1.5, 2.5))
+    one = torch.ones((4, 1, H, W), device="cuda")
+    img = torch.randint(0, 256, (4, 3, H, W), device="cuda", dtype=torch.uint8, generator=g)
+    poses = torch.tensor([[1, 0, 0, 0.01 * b, 0, 1, 0, -0.005 * b, 0, 0, 1, 0.02 * b] for b in range(4)], device="cuda", dtype=torch.float32)
+    for N in (int(x) for x in a.dims.split(",")):
+        vs = 2.048 / N
+        origin, trunc = (-1.024 + vs / 2, -1.024 + vs / 2, 1.0), 4 * vs
+        place = dict(origin=origin, voxel_size=vs)
+        ws = torch.empty(hip.tsdf_workspace_bytes(N, N, N), device="cuda", dtype=torch.uint8)
+        mws = torch.empty(hip.tsdf_mesh_workspace_bytes(N, N, N), device="cuda", dtype=torch.uint8)
+        cap = N * N * N // 4
+        rec = torch.empty((cap, 4), device="cuda", dtype=torch.int32)
+        grd = torch.empty((cap, 3), device="cuda", dtype=torch.float32)
+        cnt = torch.zeros((1,), device="cuda", dtype=torch.int32)
+        faces = torch.empty((2 * cap, 3), device="cuda", dtype=torch.int32)
+        fcnt = torch.zeros((1,), device="cuda", dtype=torch.int32)
+        for scene, z in depth.items():
+            disp = (100.0 / z)[None, None].repeat(4, 1, 1, 1).contiguous()
+            vol = torch.zeros((N, N, N, 4), device="cuda", dtype=torch.int32)
+            hip.tsdf_integrate(vol, disp, one, one, img, poses, **CAM, **place, trunc=trunc, max_weight=64, carve=True)
+            mesh = lambda: hip.tsdf_mesh(vol, **place, min_weight=1, workspace=mws, records=rec, gradients=grd, count=cnt, faces=faces, face_count=fcnt)      # noqa: E731
+            extract = lambda: hip.tsdf_extract(vol, **place, min_weight=1, workspace=ws, records=rec, gradients=grd, count=cnt)      # noqa: E731
+            compose = lambda: torch_mesh_faces(torch, vol, 1, tables)      # noqa: E731
+            mesh()
+            n, nf = int(cnt[0]), int(fcnt[0])
+            ref = compose()
+            equal = nf <= len(faces) and ref.shape[0] == nf and bool((ref == faces[:nf]).all())
+            del ref
+            gm, gx = captured(mesh), captured(extract)
+            tm, tx, tt = [], [], []
+            for _ in range(a.repeats):
+                tm.append(timed(gm.replay, a.steps))
+                tx.append(timed(gx.replay, a.steps))
+                tt.append(timed(compose, a.torch_steps))
+            um, ux, ut = statistics.median(tm), statistics.median(tx), statistics.median(tt)
+            mandatory = N ** 3 * 16 + n * 28 + nf * 12 + 8
+            say(f"mesh      {N}^3 {scene:5s}: {n} vertices, {nf} faces (torch composition's faces equal K25's: {equal}), capacities {cap} / {2 * cap}")
+            say(f"    K25                {spread(tm)}   {mandatory} mandatory bytes = {mandatory / um / 1e6:6.3f} TB/s = "
+                f"{mandatory / um / 1e6 / HBM_COPY_TBS * 100:5.1f} % of the {HBM_COPY_TBS} TB/s copy rate")
+            say(f"    K24 extract alone  {spread(tx)}   K25 = {um / ux:5.2f}x the vertices alone")
+            say(f"    torch composition  {spread(tt)}   {ut / um:6.1f}x K25 (faces only: it computes no vertex)")
+            del gm, gx, vol
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -121,8 +224,11 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--dims", default="256,512")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tsdf", "tsdfbench.txt"))
+    ap.add_argument("--mesh", action="store_true", help="measure K25 (the triangle mesh) instead; default --out profiles/tsdf/tsdfmesh.txt")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "tsdf", "tsdfmesh.txt" if a.mesh else "tsdfbench.txt")
     import torch
     from s2m2_amd import hip
     from tools.kbench import captured, spread, timed
@@ -131,6 +237,13 @@ def main() -> None:
     def say(s: str) -> None:
         print(s, flush=True)
         lines.append(s)
+
+    if a.mesh:
+        mesh_main(a, torch, hip, say)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
 
     forward_us = None
     if a.forward:
