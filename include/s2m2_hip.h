@@ -1298,6 +1298,66 @@ typedef struct s2m2_tsdf_mesh_desc {
 size_t s2m2_tsdf_mesh_workspace_bytes(int Nx, int Ny, int Nz);   /* 0: bad dims, or more voxels than the size limit */
 int s2m2_tsdf_mesh(const s2m2_tsdf_mesh_desc* desc, void* stream);
 
+/*
+ * K26 -- K24's volume ray-cast into the depth, gradient and colour maps of a camera (what open3d's RaycastingScene or KinectFusion's surface
+ *   prediction do): what the volume holds, seen from a given pose, in K21's layout -- depth with 0 as the hole value, a uint8 image, a count.
+ *   No counterpart in the reference: the semantics are defined here and pinned by the numpy oracle of tests/tsdf_raycast_oracle.py.  Still
+ *   S2M2_ABI_VERSION 800: the entry point is added, nothing changes in place.
+ *   All in fp32, every operation ONE IEEE rounding, nothing fused into a multiply-add.  fx, fy, cx, cy, origin, voxel_size (vs), z_near, z_far
+ *   and step are converted to fp32 once on the host; n_steps = ceil((z_far - z_near) / step), computed on the host in double from the fp32
+ *   values, is the length of the march (at most 65536).  poses is K24's DEVICE buffer (B, 12): [R | t] row-major, world -> camera; R is taken
+ *   as given (nothing checks orthonormality).  Per pair b and target pixel (v, u):
+ *     ray      dx = ((float)u - cx) / fx;   dy = ((float)v - cy) / fy
+ *              wx = (r00*dx + r10*dy) + r20   (R^T applied to (dx, dy, 1));   wy, wz likewise with the columns 1 and 2 of R
+ *              ox_w = -((r00*tx + r10*ty) + r20*tz)   (the camera centre);    oy_w, oz_w likewise
+ *              a_x = (ox_w - origin_x) / vs;   b_x = wx / vs;   y and z likewise.   The position in voxel units at depth z: g = a + z * b
+ *     samples  z_k = z_near + (float)k * step,   k = 0 .. n_steps-1
+ *     observed f0 = floorf(g) per axis.  The sample is OBSERVED iff f0_a >= 0 && f0_a <= (float)(N_a - 2) on all three axes (float comparisons,
+ *              before any conversion to int: a NaN or Inf fails them and no address is formed) and all eight corners (i0+dx, j0+dy, k0+dz) of the
+ *              cell (i0, j0, k0) = f0 have weight >= min_weight (K24's predicate).  A grid with an extent of 1 has no observed sample.
+ *     value    fr_a = g_a - f0_a;   trilinear along x, then y, then z, each as lo + fr * (hi - lo) (sub, mul, add): four x-lerps c00, c10, c01,
+ *              c11 (index = dy, dz), two y-lerps c0, c1, one z-lerp t
+ *     march    have_prev = false; for ascending k: an unobserved sample sets have_prev = false; else if have_prev && !(t_prev < 0) && (t < 0) this
+ *              is the crossing (+0.0 and -0.0 are not negative: K24's sign predicate); else have_prev = true, t_prev = t, z_prev = z_k.  The
+ *              first crossing ends the march; no crossing within n_steps: the pixel is a hole.
+ *     hit      z_hit = z_prev + (t_prev / (t_prev - t)) * (z_k - z_prev);   the volume is sampled again at g_hit = a + z_hit * b.  Unobserved: the
+ *              pixel is a HOLE (the march does not resume).  Otherwise depth = z_hit.
+ *     gradient the analytic gradient of the trilinear interpolant in the hit cell, from the same eight corners: Gx from the four differences
+ *              t(1,y,z) - t(0,y,z), lerped along y with fr_y, then along z with fr_z, in the same lo + fr * (hi - lo) form; Gy lerped along x,
+ *              then z; Gz along x, then y.  WORLD frame, per voxel, unnormalised, pointing to free space as K24's gradients do.
+ *     colour   of the corner nearest to g_hit: per axis i0 + (fr_a >= 0.5f);   byte = (c + 128) >> 8 per channel (K24's rounding)
+ *   outputs, each optional (NULL), at least one; every pixel of every requested output is written, a hole as 0 / 0,0,0 / 0,0,0:
+ *     depth      (B,1,Ht,Wt) fp32, z in the camera
+ *     gradients  (B,3,Ht,Wt) fp32
+ *     image      (B,3,Ht,Wt) uint8
+ *     count      (B) int32 covered pixels: cleared on the stream by the entry point, then one atomic integer add per block.  The sum does not
+ *                depend on the order, so the stage stays bit-reproducible.
+ *   The kernel skips samples that a slab clip of the ray against the grid box proves to lie outside the grid; they are unobserved by the rule, so
+ *   no bit of the result depends on it.  One launch plus the clear of count, no workspace, no host step.
+ *   Errors (before any device call): null descriptor; everything K24 checks of a volume (null or misaligned, dims, voxel_size, origin); null or
+ *   misaligned poses; no output requested; depth, gradients or count not 4-byte aligned; B, Ht or Wt <= 0 or B*Ht*Wt >= 2^31; fx or fy not
+ *   finite or zero as fp32; non-finite cx or cy; min_weight < 1; z_near, z_far or step not finite or outside the ranges below as fp32;
+ *   n_steps > 65536.
+ *   Launch plans: s2m2_tsdf_raycast is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing.
+ *   Safe under stream capture (hipGraph).
+ */
+typedef struct s2m2_tsdf_raycast_desc {
+    const void*  volume;          /* K24's volume, 16-byte aligned */
+    const float* poses;           /* DEVICE (B, 12) fp32 [R | t] row-major, world -> camera: K24's convention */
+    float*       depth;           /* (B,1,Ht,Wt) fp32, z in the camera, 0 = hole; optional */
+    float*       gradients;       /* (B,3,Ht,Wt) fp32, WORLD frame, unnormalised, 0 at holes; optional */
+    uint8_t*     image;           /* (B,3,Ht,Wt) uint8, 0 at holes; optional */
+    int32_t*     count;           /* (B) covered pixels; optional */
+    int          B, Ht, Wt;
+    int          Nx, Ny, Nz;
+    int          min_weight;      /* >= 1, K24's OBSERVED predicate */
+    double       fx, fy, cx, cy;  /* target camera */
+    double       origin[3];
+    double       voxel_size;
+    double       z_near, z_far, step;  /* in the unit of z; 0 <= z_near < z_far, step > 0 */
+} s2m2_tsdf_raycast_desc;
+int s2m2_tsdf_raycast(const s2m2_tsdf_raycast_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,8 @@
 // A stream of pairs from a moving rig fused into one TSDF volume (s2m2_tsdf_integrate / s2m2_tsdf_extract), a mode of its own:
 //   s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T]
 //                   [--tsdf-min-weight N] [--tsdf-carve] --calib calib.txt --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply]
+//                   [--tsdf-render POSE [--tsdf-render-depth OUT.f32] [--tsdf-render-image OUT.u8] [--tsdf-render-step X]
+//                   [--tsdf-render-min-weight N]]
 // Every line of LIST names LEFT.f32 RIGHT.f32 IMAGE.u8 (as above; raw uint8 (1,3,H,W) for the colours) and the twelve numbers of the pose
 //   [R | t], row-major, world -> camera, t in the unit of z; empty lines and lines that start with # are skipped.  The engine (one pair per run)
 //   runs per line and the maps are fused behind it; one extraction follows the last line.  --tsdf-dims: the voxels; --tsdf-voxel: their
@@ -66,6 +68,11 @@
 //   fused.  Honours --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered.  --tsdf-ply: the surface points in --ply's layout.
 //   --tsdf-mesh (K25, s2m2_tsdf_mesh): also the surface as a triangle mesh in --mesh's layout, the vertices being --tsdf-ply's points; one
 //   call behind the extraction; "tsdf_faces" joins the printed line.
+//   --tsdf-render POSE (K26, s2m2_tsdf_raycast): the fused volume seen from POSE, twelve comma-separated numbers [R | t], row-major, world ->
+//   camera, through the calib's left intrinsics at the engine's H x W: --tsdf-render-depth, raw float32 (1,1,H,W) z (0: hole), and / or
+//   --tsdf-render-image, raw uint8 (1,3,H,W); the rays are sampled every --tsdf-render-step (default T / 2) from 0 to the farthest corner of the
+//   grid; --tsdf-render-min-weight: the frames a voxel needs (default --tsdf-min-weight's).  "tsdf_render_pixels" (the covered pixels) joins the
+//   printed line.
 //   LIST is parsed before the engine is loaded.  Prints {"tsdf_frames", "tsdf_points"} on a line of its own.
 #include <hip/hip_runtime.h>
 
@@ -408,6 +415,43 @@ static int stage_eval(Context& c, const GroundTruth& g) {
     return 0;
 }
 
+// --tsdf-render (K26): the volume seen from the option's pose through the calib's left camera at H x W -> the covered pixels in `pixels`
+static int render_tsdf(const Options& o, const s2m2_engine_info& m, const Calib& cal, const void* volume, hipStream_t s, int32_t& pixels) {
+    const size_t plane = (size_t)m.H * m.W;
+    DeviceBuffer dpose, ddepth, dimage, dcount;
+    if (DeviceBuffer::make(dpose, sizeof o.tsdf_render_pose) || DeviceBuffer::make(dcount, sizeof(int32_t)) ||
+        (o.tsdf_render_depth_path && DeviceBuffer::make(ddepth, plane * sizeof(float))) || (o.tsdf_render_image_path && DeviceBuffer::make(dimage, 3 * plane)))
+        return 1;
+    HIP_OK(hipMemcpy(dpose.h, o.tsdf_render_pose, sizeof o.tsdf_render_pose, hipMemcpyHostToDevice), "upload");
+    s2m2_tsdf_raycast_desc rd;
+    memset(&rd, 0, sizeof rd);
+    rd.volume = volume; rd.poses = dpose.as<float>();
+    rd.depth = o.tsdf_render_depth_path ? ddepth.as<float>() : nullptr;
+    rd.image = o.tsdf_render_image_path ? dimage.as<uint8_t>() : nullptr;
+    rd.count = dcount.as<int32_t>();
+    rd.B = 1; rd.Ht = m.H; rd.Wt = m.W;
+    rd.Nx = o.tsdf_dims[0]; rd.Ny = o.tsdf_dims[1]; rd.Nz = o.tsdf_dims[2];
+    rd.min_weight = o.tsdf_render_min_weight;
+    rd.fx = cal.fx; rd.fy = cal.fy; rd.cx = cal.cx; rd.cy = cal.cy;
+    memcpy(rd.origin, o.tsdf_origin, sizeof rd.origin);
+    rd.voxel_size = o.tsdf_voxel;
+    rd.z_near = 0.0; rd.z_far = tsdf_far_corner(o.tsdf_render_pose, o.tsdf_dims, o.tsdf_origin, o.tsdf_voxel); rd.step = o.tsdf_render_step;
+    if (s2m2_tsdf_raycast(&rd, s) != 0) return fail_lib("s2m2_tsdf_raycast failed");
+    HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_raycast");
+    HIP_OK(hipMemcpy(&pixels, dcount.h, sizeof pixels, hipMemcpyDeviceToHost), "download");
+    if (o.tsdf_render_depth_path) {
+        std::vector<float> h(plane);
+        HIP_OK(hipMemcpy(h.data(), ddepth.h, plane * sizeof(float), hipMemcpyDeviceToHost), "download");
+        if (!write_bytes(o.tsdf_render_depth_path, "", h.data(), plane * sizeof(float))) return fail("cannot write the --tsdf-render-depth file");
+    }
+    if (o.tsdf_render_image_path) {
+        std::vector<unsigned char> h(3 * plane);
+        HIP_OK(hipMemcpy(h.data(), dimage.h, 3 * plane, hipMemcpyDeviceToHost), "download");
+        if (!write_bytes(o.tsdf_render_image_path, "", h.data(), 3 * plane)) return fail("cannot write the --tsdf-render-image file");
+    }
+    return 0;
+}
+
 // --tsdf-frames (K24): the engine per line of LIST, the maps fused into the volume behind it, one extraction at the end
 static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& m, const std::vector<TsdfFrame>& frames, hipStream_t s) {
     if (m.B != 1) return fail("--tsdf-frames needs an engine of one pair per run");
@@ -469,8 +513,14 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
         HIP_OK(hipMemcpy(hrec.data(), drec.h, hrec.size(), hipMemcpyDeviceToHost), "download");
     }
     if (!write_ply(o.tsdf_ply_path, hrec.data(), n)) return fail("cannot write the TSDF PLY file");
+    std::string render;                                                      // what --tsdf-render adds to the printed line
+    if (o.tsdf_render_arg) {
+        int32_t pixels = 0;
+        if (int rc = render_tsdf(o, m, cal, dvol.h, s, pixels)) return rc;
+        render = ", \"tsdf_render_pixels\": " + std::to_string(pixels);
+    }
     if (!o.tsdf_mesh_path) {
-        printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d}\n", frames.size(), n);
+        printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d%s}\n", frames.size(), n, render.c_str());
         return 0;
     }
     // --tsdf-mesh (K25): one faces-only call -- the vertices are the records above.  A face takes three of a cell's points, a cell with p points
@@ -495,7 +545,7 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
     std::vector<int32_t> hfaces((size_t)nf * 3);
     if (nf > 0) HIP_OK(hipMemcpy(hfaces.data(), dfaces.h, hfaces.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
     if (!write_ply_mesh(o.tsdf_mesh_path, hrec.data(), n, hfaces.data(), nf)) return fail("cannot write the TSDF mesh PLY file");
-    printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d, \"tsdf_faces\": %d}\n", frames.size(), n, nf);
+    printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d, \"tsdf_faces\": %d%s}\n", frames.size(), n, nf, render.c_str());
     return 0;
 }
 

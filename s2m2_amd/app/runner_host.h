@@ -20,7 +20,8 @@ inline const char* const USAGE =
     "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]"
     " | s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T] "
-    "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
+    "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply] [--tsdf-render POSE [--tsdf-render-depth OUT.f32] "
+    "[--tsdf-render-image OUT.u8] [--tsdf-render-step X] [--tsdf-render-min-weight N]] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
     "[--unfiltered]";
 
 // ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
@@ -38,9 +39,14 @@ struct Options {
     const char *tsdf_frames_path = nullptr, *tsdf_dims_arg = nullptr, *tsdf_voxel_arg = nullptr, *tsdf_origin_arg = nullptr;
     const char *tsdf_trunc_arg = nullptr, *tsdf_min_weight_arg = nullptr, *tsdf_carve_arg = nullptr, *tsdf_ply_path = nullptr;
     const char* tsdf_mesh_path = nullptr;
+    const char *tsdf_render_arg = nullptr, *tsdf_render_depth_path = nullptr, *tsdf_render_image_path = nullptr;
+    const char *tsdf_render_step_arg = nullptr, *tsdf_render_min_weight_arg = nullptr;
 
     int tsdf_dims[3] = {0, 0, 0}, tsdf_min_weight = 1, tsdf_carve = 0;
     double tsdf_voxel = 0.0, tsdf_trunc = 0.0, tsdf_origin[3] = {0, 0, 0};      // tsdf_trunc: 4 * tsdf_voxel unless --tsdf-trunc
+    float tsdf_render_pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};          // --tsdf-render: [R | t] row-major, world -> camera
+    double tsdf_render_step = 0.0;                       // tsdf_trunc / 2 unless --tsdf-render-step
+    int tsdf_render_min_weight = 1;                      // tsdf_min_weight unless --tsdf-render-min-weight
     int repeat = 0, splat = 2, unfiltered = 0;
     long long min_size = 1, voxel_max = 0;               // voxel_max 0: a quarter of the image's pixels
     double max_jump = 1.0, voxel_size = 0.0;
@@ -93,6 +99,11 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--tsdf-carve", false, &Options::tsdf_carve_arg},
     {"--tsdf-ply", true, &Options::tsdf_ply_path},
     {"--tsdf-mesh", true, &Options::tsdf_mesh_path},
+    {"--tsdf-render", true, &Options::tsdf_render_arg},
+    {"--tsdf-render-depth", true, &Options::tsdf_render_depth_path},
+    {"--tsdf-render-image", true, &Options::tsdf_render_image_path},
+    {"--tsdf-render-step", true, &Options::tsdf_render_step_arg},
+    {"--tsdf-render-min-weight", true, &Options::tsdf_render_min_weight_arg},
 };
 
 // "a,b,c": exactly three numbers, nothing behind them
@@ -111,6 +122,17 @@ inline bool parse_positive(const char* arg, double& v) {
     char* end = nullptr;
     v = strtod(arg, &end);
     return end != arg && !*end && v > 0.0 && isfinite(v);
+}
+
+// "a,b,...": exactly twelve finite numbers that fit a float, nothing behind them
+inline bool parse_pose(const char* arg, float* v) {
+    for (int i = 0; i < 12; ++i) {
+        char* end = nullptr;
+        v[i] = strtof(arg, &end);
+        if (end == arg || *end != (i < 11 ? ',' : '\0') || !isfinite(v[i])) return false;
+        arg = end + 1;
+    }
+    return true;
 }
 
 // the rules of the --tsdf-* options (K24); null: complete.  The mode takes ENGINE alone: its pairs come from LIST
@@ -143,6 +165,22 @@ inline const char* check_tsdf_options(Options& o) {
     o.tsdf_carve = o.tsdf_carve_arg != nullptr;
     // K25's size limit: an int32 face count, at most 5 faces per cell
     if (o.tsdf_mesh_path && d[0] * d[1] * d[2] > 429496729.0) return "--tsdf-mesh: NX*NY*NZ <= 429496729 (an int32 face count)";
+    // --tsdf-render (K26): the pose, at least one of the two maps, the step and the weight a voxel needs
+    if (!o.tsdf_render_arg && (o.tsdf_render_depth_path || o.tsdf_render_image_path || o.tsdf_render_step_arg || o.tsdf_render_min_weight_arg))
+        return "the --tsdf-render-* options need --tsdf-render";
+    o.tsdf_render_step = 0.5 * o.tsdf_trunc;
+    o.tsdf_render_min_weight = o.tsdf_min_weight;
+    if (o.tsdf_render_arg) {
+        if (!o.tsdf_render_depth_path && !o.tsdf_render_image_path) return "--tsdf-render needs --tsdf-render-depth or --tsdf-render-image";
+        if (!parse_pose(o.tsdf_render_arg, o.tsdf_render_pose)) return "--tsdf-render: twelve finite numbers, [R | t] row-major, separated by commas";
+        if (o.tsdf_render_step_arg && !parse_positive(o.tsdf_render_step_arg, o.tsdf_render_step)) return "--tsdf-render-step: a number > 0";
+        if (o.tsdf_render_min_weight_arg) {
+            char* end = nullptr;
+            const long long n = strtoll(o.tsdf_render_min_weight_arg, &end, 10);
+            if (end == o.tsdf_render_min_weight_arg || *end || n < 1 || n > 32767) return "--tsdf-render-min-weight: an integer in 1..32767";
+            o.tsdf_render_min_weight = (int)n;
+        }
+    }
     return nullptr;
 }
 
@@ -170,7 +208,8 @@ inline const char* check_options(Options& o) {
     if (o.gt_min_arg) o.gt_min = atof(o.gt_min_arg);
     o.unfiltered = o.unfiltered_arg != nullptr;
     if (o.tsdf_frames_path || o.tsdf_dims_arg || o.tsdf_voxel_arg || o.tsdf_origin_arg || o.tsdf_trunc_arg || o.tsdf_min_weight_arg || o.tsdf_carve_arg ||
-        o.tsdf_ply_path || o.tsdf_mesh_path)
+        o.tsdf_ply_path || o.tsdf_mesh_path || o.tsdf_render_arg || o.tsdf_render_depth_path || o.tsdf_render_image_path || o.tsdf_render_step_arg ||
+        o.tsdf_render_min_weight_arg)
         return check_tsdf_options(o);
     if (o.npos != 3 || o.repeat < 0) return USAGE;
     if (o.mesh_path && !o.calib_path) return "--calib and --mesh come together";
@@ -323,6 +362,22 @@ inline std::string read_tsdf_frames(const char* path, std::vector<TsdfFrame>& fr
     fclose(f);
     if (msg.empty() && frames.empty()) msg = std::string("--tsdf-frames ") + path + ": no frame";
     return msg;
+}
+
+// the largest distance from the centre of the camera `pose` ([R | t] row-major, world -> camera: the centre is -R^T t) to a corner of the grid:
+// no surface of the volume lies deeper along any ray (--tsdf-render's z_far)
+inline double tsdf_far_corner(const float* pose, const int* dims, const double* origin, double voxel) {
+    double centre[3], far = 0.0;
+    for (int a = 0; a < 3; ++a) centre[a] = -((double)pose[a] * pose[3] + (double)pose[4 + a] * pose[7] + (double)pose[8 + a] * pose[11]);
+    for (int c = 0; c < 8; ++c) {
+        double d2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double x = origin[a] + ((c >> a) & 1) * (dims[a] - 1) * voxel - centre[a];
+            d2 += x * x;
+        }
+        far = fmax(far, sqrt(d2));
+    }
+    return far;
 }
 
 // greyscale PFM: "Pf", "width height", "scale" (negative: little-endian), then the rows bottom to top -> rows top to bottom

@@ -506,6 +506,30 @@ class TsdfMesh(TsdfSurface):
         return write_ply_mesh(path, out, faces, normals=True)
 
 
+class TsdfRender:
+    """What ``TsdfVolume.raycast`` returns, all on the device and in the target camera unless noted: ``depth`` (B,1,Ht,Wt) fp32 z of the first
+    surface along the ray (0: hole), ``gradients_buf`` (B,3,Ht,Wt) fp32 or None: the unnormalised tsdf gradient at the hit in the WORLD frame,
+    from the surface to free space (0 at holes), ``image`` (B,3,Ht,Wt) uint8 or None, ``count`` (B) int32 covered pixels or None; ``R``
+    (B,3,3) fp32: the rotations the maps were rendered with."""
+
+    def __init__(self, depth: torch.Tensor, gradients_buf: Optional[torch.Tensor], image: Optional[torch.Tensor], count: Optional[torch.Tensor],
+                 R: torch.Tensor):
+        self.depth, self.gradients_buf, self.image, self.count, self.R = depth, gradients_buf, image, count, R
+
+    def normals(self) -> torch.Tensor:
+        """(B,3,Ht,Wt) fp32 in the CAMERA frame: ``R @ G`` normalised in torch (a zero gradient stays zero); not part of the exact contract"""
+        if self.gradients_buf is None:
+            raise ValueError("TsdfRender.normals: raycast was called with want_gradients=False")
+        g = torch.einsum("bij,bjhw->bihw", self.R.to(self.gradients_buf.device), self.gradients_buf)
+        return g / g.norm(dim=1, keepdim=True).clamp_min(1e-30)
+
+    def holes(self, b: int = 0) -> int:
+        """pixels of pair b that no surface covers -- reads ``count`` on the host (synchronises)"""
+        if self.count is None:
+            raise ValueError("TsdfRender.holes: raycast was called with want_count=False")
+        return self.depth.shape[-2] * self.depth.shape[-1] - int(self.count[b].item())
+
+
 class TsdfVolume:
     """A truncated signed distance volume on the device (K24, ``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``; the rule: include/s2m2_hip.h,
     K24): ``dims`` = (Nx, Ny, Nz) voxels of ``voxel_size`` (the unit of z), ``origin`` the centre of voxel (0,0,0) in the world frame,
@@ -547,12 +571,12 @@ class TsdfVolume:
         """(Nz, Ny, Nx, 3) int16 strided view of the 8.8 fixed-point r, g, b (read them as unsigned: value & 0xffff)"""
         return self.buffer.view(torch.int16)[..., 4:7]
 
-    def _poses(self, R, t, B: int) -> torch.Tensor:
+    def _poses(self, R, t, B: int, what: str = "integrate") -> torch.Tensor:
         """R (3,3) or (B,3,3), t (3,) or (B,3), tensors on any device or anything ``torch.as_tensor`` takes -> (B,12) fp32 on the device"""
         R = torch.as_tensor(R).to(device=self.device, dtype=torch.float32)
         t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32)
         if tuple(R.shape) not in ((3, 3), (B, 3, 3)) or tuple(t.shape) not in ((3,), (B, 3)):
-            raise ValueError(f"TsdfVolume.integrate: R is (3,3) or ({B},3,3) and t is (3,) or ({B},3), got {tuple(R.shape)} and {tuple(t.shape)}")
+            raise ValueError(f"TsdfVolume.{what}: R is (3,3) or ({B},3,3) and t is (3,) or ({B},3), got {tuple(R.shape)} and {tuple(t.shape)}")
         R = R.expand(B, 3, 3) if R.dim() == 2 else R
         t = t.expand(B, 3) if t.dim() == 1 else t
         return torch.cat([R, t[:, :, None]], dim=2).reshape(B, 12).contiguous()
@@ -610,3 +634,39 @@ class TsdfVolume:
             hip.tsdf_mesh(self.buffer, origin=self.origin, voxel_size=self.voxel_size, min_weight=min_weight, workspace=self._mesh_workspace,
                           records=records, gradients=gradients, count=count, faces=faces, face_count=face_count)
         return TsdfMesh(records[None], count, gradients, faces, face_count)
+
+    def far_corner(self, R, t) -> float:
+        """the largest distance from the centre of a camera (``p_cam = R @ p_world + t``; (3,3) / (3,) or batched) to a corner of the grid, on
+        the host in double: no surface of the volume lies deeper along any ray"""
+        R = np.asarray(torch.as_tensor(R).detach().cpu(), dtype=np.float64).reshape(-1, 3, 3)
+        t = np.asarray(torch.as_tensor(t).detach().cpu(), dtype=np.float64).reshape(-1, 3)
+        n = max(len(R), len(t))
+        centre = -np.einsum("bji,bj->bi", np.broadcast_to(R, (n, 3, 3)), np.broadcast_to(t, (n, 3)))        # -R^T t
+        ext = (np.asarray(self.dims, dtype=np.float64) - 1.0) * self.voxel_size
+        corners = np.asarray(self.origin)[None] + np.array([[i, j, k] for i in (0, 1) for j in (0, 1) for k in (0, 1)], dtype=np.float64) * ext[None]
+        return float(np.linalg.norm(corners[None] - centre[:, None], axis=2).max())
+
+    def raycast(self, camera: Camera, R=None, t=None, *, min_weight: int = 1, z_near: float = 0.0, z_far: Optional[float] = None,
+                step: Optional[float] = None, want_gradients: bool = True, want_image: bool = True, want_count: bool = True) -> TsdfRender:
+        """What the volume holds, seen from ``camera`` (K26, ``s2m2_tsdf_raycast``; the rule: include/s2m2_hip.h, K26): the camera's size and
+        intrinsics, and the pose(s) ``R``, ``t`` in ``integrate``'s shapes and convention (world -> camera; default: ``camera.R``,
+        ``camera.t``).  Every ray is sampled at ``z_near + k * step`` below ``z_far`` and ends at the first change of the interpolated tsdf from
+        non-negative to negative between two samples whose eight voxels all have at least ``min_weight`` frames.  ``step`` None = trunc / 2;
+        ``z_far`` None = the largest distance from a camera centre to a corner of the grid (computed on the host: reads R and t there).  A
+        march of more than 65536 steps is refused.  One launch, no synchronisation, capturable."""
+        R = camera.R if R is None else R
+        t = camera.t if t is None else t
+        Rt = torch.as_tensor(R)
+        B = Rt.shape[0] if Rt.dim() == 3 else 1
+        poses = self._poses(R, t, B, "raycast")
+        step = self.trunc / 2.0 if step is None else float(step)
+        z_far = self.far_corner(R, t) if z_far is None else float(z_far)
+        Ht, Wt = camera.height, camera.width
+        depth = torch.empty((B, 1, Ht, Wt), device=self.device, dtype=torch.float32)
+        gradients = torch.empty((B, 3, Ht, Wt), device=self.device, dtype=torch.float32) if want_gradients else None
+        image = torch.empty((B, 3, Ht, Wt), device=self.device, dtype=torch.uint8) if want_image else None
+        count = torch.empty((B,), device=self.device, dtype=torch.int32) if want_count else None
+        hip.tsdf_raycast(self.buffer, poses, Ht=Ht, Wt=Wt, fx=camera.fx, fy=camera.fy, cx=camera.cx, cy=camera.cy, origin=self.origin,
+                         voxel_size=self.voxel_size, min_weight=min_weight, z_near=z_near, z_far=z_far, step=step, depth=depth,
+                         gradients=gradients, image=image, count=count)
+        return TsdfRender(depth, gradients, image, count, poses.view(B, 3, 4)[:, :, :3])

@@ -165,6 +165,14 @@ class TsdfMeshDesc(ctypes.Structure):
     _fields_ = [("extract", TsdfExtractDesc), ("faces", _vp), ("face_count", _vp), ("face_capacity", _ll)]
 
 
+class TsdfRaycastDesc(ctypes.Structure):
+    """mirror of s2m2_tsdf_raycast_desc (include/s2m2_hip.h): K26, a TSDF volume ray-cast into depth, gradient and colour maps"""
+    _fields_ = [("volume", _vp), ("poses", _vp), ("depth", _vp), ("gradients", _vp), ("image", _vp), ("count", _vp), ("B", _i), ("Ht", _i),
+                ("Wt", _i), ("Nx", _i), ("Ny", _i), ("Nz", _i), ("min_weight", _i), ("fx", ctypes.c_double), ("fy", ctypes.c_double),
+                ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("origin", ctypes.c_double * 3), ("voxel_size", ctypes.c_double),
+                ("z_near", ctypes.c_double), ("z_far", ctypes.c_double), ("step", ctypes.c_double)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -292,6 +300,7 @@ SIGNATURES = {
     "s2m2_tsdf_extract": (_i, [ctypes.POINTER(TsdfExtractDesc), _vp]),
     "s2m2_tsdf_mesh_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_tsdf_mesh": (_i, [ctypes.POINTER(TsdfMeshDesc), _vp]),
+    "s2m2_tsdf_raycast": (_i, [ctypes.POINTER(TsdfRaycastDesc), _vp]),
 }
 
 
@@ -1399,5 +1408,6 @@ from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
 from .hip_segment import segment, segment_tile, segment_workspace_bytes  # noqa: E402,F401
 # K23 (s2m2_voxel): likewise, from hip_voxel.py
 from .hip_voxel import voxel, voxel_home_slot, voxel_slots, voxel_tile_rows, voxel_workspace_bytes  # noqa: E402,F401
-# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract) and K25 (s2m2_tsdf_mesh): likewise, from hip_tsdf.py
-from .hip_tsdf import tsdf_extract, tsdf_integrate, tsdf_mesh, tsdf_mesh_workspace_bytes, tsdf_tile_voxels, tsdf_workspace_bytes  # noqa: E402,F401
+# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract), K25 (s2m2_tsdf_mesh) and K26 (s2m2_tsdf_raycast): likewise, from hip_tsdf.py
+from .hip_tsdf import (RAYCAST_MAX_STEPS, tsdf_extract, tsdf_integrate, tsdf_mesh, tsdf_mesh_workspace_bytes, tsdf_raycast, tsdf_raycast_steps,  # noqa: E402,F401
+                       tsdf_tile_voxels, tsdf_workspace_bytes)

@@ -1,8 +1,9 @@
 """K24 (``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``, csrc/tsdf.hip): depth maps fused into a TSDF volume, and the volume's surface points;
-K25 (``s2m2_tsdf_mesh``, csrc/tsdf_mesh.hip): that surface as a triangle mesh.
+K25 (``s2m2_tsdf_mesh``, csrc/tsdf_mesh.hip): that surface as a triangle mesh; K26 (``s2m2_tsdf_raycast``, csrc/tsdf_raycast.hip): the volume
+ray-cast into the depth, gradient and colour maps of a camera.
 The descriptor mirrors and the signatures are in hip.py with all the others (``hip.load()`` binds every symbol there); this module holds the
-wrappers, which hip.py re-exports as ``hip.tsdf_integrate``, ``hip.tsdf_extract``, ``hip.tsdf_mesh``, ``hip.tsdf_workspace_bytes``,
-``hip.tsdf_mesh_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
+wrappers, which hip.py re-exports as ``hip.tsdf_integrate``, ``hip.tsdf_extract``, ``hip.tsdf_mesh``, ``hip.tsdf_raycast``,
+``hip.tsdf_raycast_steps``, ``hip.tsdf_workspace_bytes``, ``hip.tsdf_mesh_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
 import ctypes
 import math
 from typing import Optional, Sequence, Tuple
@@ -131,6 +132,72 @@ def tsdf_mesh(volume: torch.Tensor, *, origin: Sequence[float], voxel_size: floa
     d.extract.workspace = workspace.data_ptr()
     with torch.cuda.device(volume.device):
         _h._check(_h.load().s2m2_tsdf_mesh(ctypes.byref(d), _h._stream()), "s2m2_tsdf_mesh")
+
+
+RAYCAST_MAX_STEPS = 65536
+
+
+def _f32(x: float) -> float:
+    return ctypes.c_float(float(x)).value
+
+
+def tsdf_raycast_steps(z_near: float, z_far: float, step: float) -> int:
+    """the length of ``tsdf_raycast``'s march as the entry point computes it: ceil((z_far - z_near) / step) in double from the fp32 values;
+    raises unless 0 <= z_near < z_far and step > 0 hold for the fp32 values and all three are finite"""
+    zn, zf, st = _f32(z_near), _f32(z_far), _f32(step)                  # (a double beyond the fp32 range becomes inf)
+    if not (math.isfinite(zn) and math.isfinite(zf) and math.isfinite(st) and 0.0 <= zn < zf and st > 0.0):
+        raise ValueError(f"tsdf_raycast: finite 0 <= z_near < z_far and step > 0 are required in fp32, got z_near={z_near} z_far={z_far} step={step}")
+    q = (zf - zn) / st
+    return math.ceil(q) if q < 1e18 else 10 ** 18
+
+
+def tsdf_raycast(volume: torch.Tensor, poses: torch.Tensor, *, Ht: int, Wt: int, fx: float, fy: float, cx: float, cy: float,
+                 origin: Sequence[float], voxel_size: float, min_weight: int = 1, z_near: float = 0.0, z_far: float, step: float,
+                 depth: Optional[torch.Tensor] = None, gradients: Optional[torch.Tensor] = None, image: Optional[torch.Tensor] = None,
+                 count: Optional[torch.Tensor] = None) -> None:
+    """s2m2_tsdf_raycast (K26): ``volume`` (Nz,Ny,Nx,4) int32 seen from the B cameras of the DEVICE pose buffer ``poses`` (B,12) fp32 ([R | t]
+    row-major, world -> camera) with the intrinsics fx, fy, cx, cy and Ht x Wt pixels -> the outputs the caller allocated, each optional, at
+    least one: ``depth`` (B,1,Ht,Wt) fp32 (0: hole), ``gradients`` (B,3,Ht,Wt) fp32 (world frame, unnormalised), ``image`` (B,3,Ht,Wt) uint8,
+    ``count`` (B) int32 covered pixels.  The rays are sampled at z_near + k * step below z_far.  Thin: no allocation, no synchronisation."""
+    _h._resident("tsdf_raycast", volume, poses, depth, gradients, image, count)
+    _h._contig("tsdf_raycast", volume, poses, depth, gradients, image, count)
+    d = _h.TsdfRaycastDesc()
+    d.Nx, d.Ny, d.Nz = _volume("tsdf_raycast", volume)
+    if poses is None or poses.dim() != 2 or poses.shape[0] < 1:
+        raise ValueError("tsdf_raycast: poses must be a (B, 12) fp32 tensor with B >= 1")
+    B = poses.shape[0]
+    _h._mat(poses, (B, 12), torch.float32, "tsdf_raycast: poses")
+    if int(Ht) != Ht or int(Wt) != Wt or Ht < 1 or Wt < 1 or B * int(Ht) * int(Wt) >= 1 << 31:
+        raise ValueError(f"tsdf_raycast: bad extents B={B} Ht={Ht} Wt={Wt} (positive, B*Ht*Wt < 2^31)")
+    Ht, Wt = int(Ht), int(Wt)
+    if depth is None and gradients is None and image is None and count is None:
+        raise ValueError("tsdf_raycast: no output requested")
+    if depth is not None:
+        _h._mat(depth, (B, 1, Ht, Wt), torch.float32, "tsdf_raycast: depth")
+    if gradients is not None:
+        _h._mat(gradients, (B, 3, Ht, Wt), torch.float32, "tsdf_raycast: gradients")
+    if image is not None:
+        _h._mat(image, (B, 3, Ht, Wt), torch.uint8, "tsdf_raycast: image")
+    if count is not None:
+        _h._vec(count, B, "tsdf_raycast: count", dtype=torch.int32)
+    for name, x in (("fx", fx), ("fy", fy)):
+        if not math.isfinite(float(x)) or abs(float(x)) > 3.4e38 or _f32(x) == 0.0:
+            raise ValueError(f"tsdf_raycast: {name} must be finite and non-zero in fp32, got {x}")
+    if not (math.isfinite(float(cx)) and math.isfinite(float(cy))):
+        raise ValueError(f"tsdf_raycast: cx and cy must be finite, got {cx} and {cy}")
+    d.origin, d.voxel_size = _placement("tsdf_raycast", origin, voxel_size)
+    if int(min_weight) != min_weight or min_weight < 1:
+        raise ValueError(f"tsdf_raycast: min_weight must be an integer >= 1, got {min_weight}")
+    n_steps = tsdf_raycast_steps(z_near, z_far, step)
+    if n_steps > RAYCAST_MAX_STEPS:
+        raise ValueError(f"tsdf_raycast: {n_steps} steps from z_near={z_near} to z_far={z_far} (at most {RAYCAST_MAX_STEPS})")
+    d.volume, d.poses = volume.data_ptr(), poses.data_ptr()
+    d.depth, d.gradients, d.image, d.count = _h._ptr(depth), _h._ptr(gradients), _h._ptr(image), _h._ptr(count)
+    d.B, d.Ht, d.Wt, d.min_weight = B, Ht, Wt, int(min_weight)
+    d.fx, d.fy, d.cx, d.cy = float(fx), float(fy), float(cx), float(cy)
+    d.z_near, d.z_far, d.step = float(z_near), float(z_far), float(step)
+    with torch.cuda.device(volume.device):
+        _h._check(_h.load().s2m2_tsdf_raycast(ctypes.byref(d), _h._stream()), "s2m2_tsdf_raycast")
 
 
 def tsdf_workspace_bytes(Nx: int, Ny: int, Nz: int) -> int:

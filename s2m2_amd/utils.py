@@ -218,6 +218,19 @@ def integrate_tsdf(volume, rgb, disp, calib, R, t, depth_trunc=None):
     return volume
 
 
+def render_tsdf(volume, calib, R, t, size=None):
+    """``get_pointcloud``'s conventions (halved intrinsics, fx for both focal lengths) -> ``volume`` (a ``cloud.TsdfVolume``) seen from the pose
+    ``R`` (3,3), ``t`` (3,), world -> camera as ``integrate_tsdf`` takes it: a ``cloud.TsdfRender`` on the device with the model's depth,
+    normals and colour.  ``size`` = (width, height) of the rendered maps; None: half the calibration's ``width`` and ``height``."""
+    from . import cloud
+    cam0 = calib["cam0"]
+    if size is None:
+        size = (int(calib["width"]) // 2, int(calib["height"]) // 2)
+    camera = cloud.Camera(size[0], size[1], float(cam0[0, 0]) / 2.0, float(cam0[0, 0]) / 2.0, float(cam0[0, 2]) / 2.0, float(cam0[1, 2]) / 2.0)
+    with torch.cuda.device(volume.device):
+        return volume.raycast(camera, R, t)
+
+
 def filter_speckles(disp, calib, depth_trunc=None, max_jump=1.0, min_size=100):
     """``get_pointcloud``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter: ``disp`` (H,W) arrives filtered, -1
     where invalid) -> the (H,W) fp32 disparity on the device with -1 also wherever the pixel's 4-connected component of similar disparity

@@ -338,6 +338,47 @@ int main(int argc, char** argv) {
             if (meshed[i] == "--tsdf-dims") meshed[i + 1] = "1024,1024,410";
         CHECK(tsdf(meshed, o7).find("--tsdf-mesh: NX*NY*NZ <= 429496729") == 0);
         CHECK(with("--tsdf-dims", "1024,1024,410") == "engine");
+        // --tsdf-render (K26): the pose, one of the two maps at least, the step and the weight with their defaults
+        const char* pose = "1,0,0,0.5,0,1,0,-0.25,0,0,1,2";
+        const auto rendered = [&](std::vector<std::string> extra, Options& x) {
+            std::vector<std::string> a = full;
+            a.insert(a.end(), {"--tsdf-trunc", "0.25", "--tsdf-min-weight", "3"});
+            a.insert(a.end(), extra.begin(), extra.end());
+            return tsdf(a, x);
+        };
+        Options r0, r1, r2, r3;
+        CHECK(rendered({"--tsdf-render", pose, "--tsdf-render-depth", "d.f32"}, r0) == "engine");
+        CHECK(r0.tsdf_render_pose[0] == 1.f && r0.tsdf_render_pose[3] == 0.5f && r0.tsdf_render_pose[7] == -0.25f && r0.tsdf_render_pose[11] == 2.f);
+        CHECK(r0.tsdf_render_step == 0.125 && r0.tsdf_render_min_weight == 3 && r0.tsdf_render_image_path == nullptr);
+        CHECK(rendered({"--tsdf-render", pose, "--tsdf-render-image", "i.u8", "--tsdf-render-step", "0.05", "--tsdf-render-min-weight", "1"}, r1) == "engine");
+        CHECK(r1.tsdf_render_step == 0.05 && r1.tsdf_render_min_weight == 1 && r1.tsdf_render_image_path != nullptr && r1.tsdf_render_depth_path == nullptr);
+        CHECK(rendered({"--tsdf-render", pose}, r2) == "--tsdf-render needs --tsdf-render-depth or --tsdf-render-image");
+        for (const char* flag : {"--tsdf-render-depth", "--tsdf-render-image", "--tsdf-render-step", "--tsdf-render-min-weight"}) {
+            Options x;
+            CHECK(rendered({flag, "1"}, x) == "the --tsdf-render-* options need --tsdf-render");
+        }
+        CHECK(tsdf({"--tsdf-render", pose, "--tsdf-render-depth", "d.f32"}, r3).find("need --tsdf-frames") != std::string::npos);
+        for (const char* bad : {"1,0,0,0,0,1,0,0,0,0,1", "1,0,0,0,0,1,0,0,0,0,1,0,0", "1,0,0,0,0,1,0,0,0,0,1,nan", "1,0,0,0,0,1,0,0,0,0,1,inf", "", "1 0 0 0 0 1 0 0 0 0 1 0",
+                                "1,0,0,0,0,1,0,0,0,0,1,1e39", "1,0,0,0,0,1,0,0,0,0,1,0x"}) {
+            Options x;
+            CHECK(rendered({"--tsdf-render", bad, "--tsdf-render-depth", "d.f32"}, x).find("--tsdf-render: twelve finite numbers") == 0);
+        }
+        for (const char* bad : {"0", "-1", "nan", "inf", "", "1mm"}) {
+            Options x;
+            CHECK(rendered({"--tsdf-render", pose, "--tsdf-render-depth", "d.f32", "--tsdf-render-step", bad}, x) == "--tsdf-render-step: a number > 0");
+        }
+        for (const char* bad : {"0", "-1", "32768", "two", "1.5", ""}) {
+            Options x;
+            CHECK(rendered({"--tsdf-render", pose, "--tsdf-render-depth", "d.f32", "--tsdf-render-min-weight", bad}, x) == "--tsdf-render-min-weight: an integer in 1..32767");
+        }
+        {
+            const float at[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};                       // the camera in the world's origin
+            const float back[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1};                     // p_cam = p + (0,0,1): the centre is (0,0,-1)
+            const int dims[3] = {3, 5, 9};
+            const double origin[3] = {-1.0, -2.0, 1.0};
+            CHECK(tsdf_far_corner(at, dims, origin, 0.5) == sqrt(1.0 + 4.0 + 25.0));         // corners x -1 | 0, y -2 | 0, z 1 | 5
+            CHECK(tsdf_far_corner(back, dims, origin, 0.5) == sqrt(1.0 + 4.0 + 36.0));
+        }
 
         std::vector<TsdfFrame> fr;
         put("frames.txt", "# head\n\nl0.f32 r0.f32 i0.u8 1 0 0 0.5 0 1 0 -0.25 0 0 1 2\n   l1.f32 r1.f32 i1.u8 1 0 0 0 0 1 0 0 0 0 1 0   \n");

@@ -23,7 +23,7 @@ leaves out, so a low share with carve 0 says that the launch is bound by the vox
 Extract: the surface points of the volumes above after the B = 4 call, against nonzero + gathers in torch (which synchronises to size its
 result); the counts are compared.
 
-    python tools/tsdfbench.py [--steps 20] [--torch-steps 3] [--repeats 5] [--forward] [--dims 256,512] [--out profiles/tsdf/tsdfbench.txt]
+    python tools/tsdfbench.py [--steps 20] [--torch-steps 3] [--repeats 5] [--forward] [--dims 256,512] [--mesh | --raycast] [--out FILE]
 
 --mesh (K25, s2m2_tsdf_mesh; default --out profiles/tsdf/tsdfmesh.txt) measures the triangle mesh instead, on the same volumes (the B = 4, carve 1
 call of each scene, fused once): K25, s2m2_tsdf_extract alone on the same volume (what the triangles cost on top of the vertices), and the same
@@ -32,6 +32,17 @@ rank map by a `cumsum` over the emit flags -- which is what a user can do today 
 once per volume, at the timed size.  MANDATORY BYTES of K25: the volume read once (16 B per voxel) plus the outputs written (16 + 12 B per vertex,
 12 B per face); over the time they are printed as a share of the same 6.29 TB/s copy rate.  K25 reads the volume in each of its three launches and
 writes and reads a rank map of 4 B per voxel, which the figure leaves out on purpose: it is the traffic a perfect kernel would need.
+
+--raycast (K26, s2m2_tsdf_raycast; default --out profiles/tsdf/tsdfraycast.txt) measures the ray caster on the same volumes: depth, gradients,
+image and count at 640x480 and 1216x1024 from two poses (the first frame's, and one turned by 0.2 rad about y), with the API's defaults (z_near
+0, z_far the farthest corner of the grid, step trunc / 2).  Against it: the same maps composed from torch ops -- a march of `grid_sample` over
+the tsdf and the observed flag with the same step, which keeps K26's state (have_prev, t_prev, z_prev) as whole-image tensors, takes every one
+of the n_steps samples for every pixel (leaving early would need a synchronisation per step) and samples the hit again for depth and gradient;
+compared with K26 on the pixels both cover (torch's arithmetic is not the rule's bit for bit: a sample on a cell face or beside an unobserved
+voxel may take another cell or another step, which shows as a few pixels covered by one side only and as a whole-cell change of a gradient) -- and s2m2_tsdf_extract on the same volume, which is what a user pays today before a rasteriser
+on the host.  GATHERED BYTES: a sample inside the grid reads 8 voxels x 8 B = 64 B; the samples a ray takes inside the grid up to its hit are
+counted by the torch march (K26's own clip may take a few more at the box's faces), and samples x 64 B over K26's time is printed as a share of
+the 6.29 TB/s copy rate.  Neighbouring rays share most of those bytes in the caches, so the figure is the gather rate, not HBM traffic.
 """
 import argparse
 import os
@@ -217,6 +228,127 @@ def mesh_main(a, torch, hip, say) -> None:
             del gm, gx, vol
 
 
+def torch_raycast(torch, tsdf, obs, pose, Ht, Wt, fx, fy, cx, cy, origin, vs, z_near, step, n_steps):
+    """K26's rule from torch ops: tsdf, obs (1,1,Nz,Ny,Nx) fp32 (obs: 1.0 where weight >= min_weight) -> depth (Ht,Wt), gradient (3,Ht,Wt) and
+    the number of samples taken inside the grid while a ray was still marching (a device scalar)"""
+    Nz, Ny, Nx = tsdf.shape[2:]
+    dev = tsdf.device
+    q = pose.tolist()
+    v, u = torch.meshgrid(torch.arange(Ht, device=dev, dtype=torch.float32), torch.arange(Wt, device=dev, dtype=torch.float32), indexing="ij")
+    dx, dy = (u - cx) / fx, (v - cy) / fy
+    a = [(-(q[c] * q[3] + q[4 + c] * q[7] + q[8 + c] * q[11]) - origin[c]) / vs for c in range(3)]
+    b = [(q[c] * dx + q[4 + c] * dy + q[8 + c]) / vs for c in range(3)]
+    top = (Nx - 1, Ny - 1, Nz - 1)
+
+    def sample(z):
+        g = [a[c] + z * b[c] for c in range(3)]
+        inside = (g[0] >= 0) & (g[0] < top[0]) & (g[1] >= 0) & (g[1] < top[1]) & (g[2] >= 0) & (g[2] < top[2])
+        grid = torch.stack([2.0 * g[c] / top[c] - 1.0 for c in range(3)], -1)[None, None]           # (1,1,Ht,Wt,3): x, y, z
+        t = torch.nn.functional.grid_sample(tsdf, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0, 0, 0]
+        o = torch.nn.functional.grid_sample(obs, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0, 0, 0]
+        return inside, inside & (o > 0.999999), t, g
+
+    have = torch.zeros((Ht, Wt), device=dev, dtype=torch.bool)
+    done = torch.zeros_like(have)
+    t_prev, z_prev, t_hit, z_at = (torch.zeros((Ht, Wt), device=dev) for _ in range(4))
+    samples = torch.zeros((), device=dev, dtype=torch.int64)
+    for k in range(n_steps):
+        z = z_near + k * step
+        inside, ok, t, _ = sample(z)
+        live = ~done
+        samples += (live & inside).sum()
+        cross = live & ok & have & ~(t_prev < 0) & (t < 0)
+        t_hit = torch.where(cross, t, t_hit)
+        z_at = torch.where(cross, z, z_at)
+        done |= cross
+        go = live & ok & ~cross
+        have = torch.where(live, ok & ~cross, have)
+        t_prev = torch.where(go, t, t_prev)
+        z_prev = torch.where(go, z, z_prev)
+    z_hit = z_prev + (t_prev / (t_prev - t_hit)) * (z_at - z_prev)
+    z_hit = torch.where(done, z_hit, 0.0)
+    _, ok, _, g = sample(z_hit)
+    covered = done & ok
+    grad = []
+    for c in range(3):                                      # the interpolant is linear along each axis inside a cell: its slope from the cell's two faces
+        lo, hi = list(g), list(g)
+        lo[c] = torch.floor(g[c])
+        hi[c] = lo[c] + 1.0
+        gl = torch.stack([2.0 * lo[d] / top[d] - 1.0 for d in range(3)], -1)[None, None]
+        gh = torch.stack([2.0 * hi[d] / top[d] - 1.0 for d in range(3)], -1)[None, None]
+        tl = torch.nn.functional.grid_sample(tsdf, gl, mode="bilinear", padding_mode="border", align_corners=True)[0, 0, 0]
+        th = torch.nn.functional.grid_sample(tsdf, gh, mode="bilinear", padding_mode="border", align_corners=True)[0, 0, 0]
+        grad.append(torch.where(covered, th - tl, 0.0))
+    return torch.where(covered, z_hit, 0.0), torch.stack(grad), samples
+
+
+def raycast_main(a, torch, hip, say) -> None:
+    import math
+    from tools.kbench import captured, spread, timed
+    g = torch.Generator(device="cuda").manual_seed(7)
+    vv, uu = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32), torch.arange(W, device="cuda", dtype=torch.float32), indexing="ij")
+    depth = dict(plane=torch.full((H, W), 2.0, device="cuda"), two=torch.where(uu < W // 2, 1.5, 2.5))
+    one = torch.ones((4, 1, H, W), device="cuda")
+    img = torch.randint(0, 256, (4, 3, H, W), device="cuda", dtype=torch.uint8, generator=g)
+    poses = torch.tensor([[1, 0, 0, 0.01 * b, 0, 1, 0, -0.005 * b, 0, 0, 1, 0.02 * b] for b in range(4)], device="cuda", dtype=torch.float32)
+    c2, s2 = math.cos(0.2), math.sin(0.2)
+    views = dict(front=[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], turned=[c2, 0, s2, -2 * s2, 0, 1, 0, 0, -s2, 0, c2, 2 - 2 * c2])     # turned about (0, 0, 2)
+    for N in (int(x) for x in a.dims.split(",")):
+        vs = 2.048 / N
+        origin, trunc = (-1.024 + vs / 2, -1.024 + vs / 2, 1.0), 4 * vs
+        place = dict(origin=origin, voxel_size=vs)
+        ws = torch.empty(hip.tsdf_workspace_bytes(N, N, N), device="cuda", dtype=torch.uint8)
+        cap = N * N * N // 4
+        rec = torch.empty((cap, 4), device="cuda", dtype=torch.int32)
+        grd = torch.empty((cap, 3), device="cuda", dtype=torch.float32)
+        cnt = torch.zeros((1,), device="cuda", dtype=torch.int32)
+        for scene, z in depth.items():
+            disp = (100.0 / z)[None, None].repeat(4, 1, 1, 1).contiguous()
+            vol = torch.zeros((N, N, N, 4), device="cuda", dtype=torch.int32)
+            hip.tsdf_integrate(vol, disp, one, one, img, poses, **CAM, **place, trunc=trunc, max_weight=64, carve=True)
+            tsdf = vol[..., 0].view(torch.float32)[None, None].contiguous()
+            obs = (vol[..., 1] >= 1).float()[None, None].contiguous()
+            extract = lambda: hip.tsdf_extract(vol, **place, min_weight=1, workspace=ws, records=rec, gradients=grd, count=cnt)      # noqa: E731
+            extract()
+            gx = captured(extract)
+            tx = [timed(gx.replay, a.steps) for _ in range(a.repeats)]
+            say(f"raycast   {N}^3 {scene:5s}: voxel {vs * 1000:.0f} mm, step {trunc / 2 * 1000:.0f} mm; K24 extract of the volume ({int(cnt[0])} points) {spread(tx)}")
+            for (Wt, Ht) in ((640, 480), (W, H)):
+                k = Wt / W
+                cam = dict(fx=CAM["fx"] * k, fy=CAM["fy"] * k, cx=CAM["cx"] * k, cy=CAM["cy"] * Ht / H)
+                for view, pose in views.items():
+                    pb = torch.tensor([pose], device="cuda", dtype=torch.float32)
+                    qd = [float(x) for x in pose]
+                    centre = [-(qd[c] * qd[3] + qd[4 + c] * qd[7] + qd[8 + c] * qd[11]) for c in range(3)]
+                    z_far = max(math.dist(centre, [origin[c] + (N - 1) * vs * ((corner >> c) & 1) for c in range(3)]) for corner in range(8))
+                    n_steps = hip.tsdf_raycast_steps(0.0, z_far, trunc / 2)
+                    out = dict(depth=torch.empty((1, 1, Ht, Wt), device="cuda"), gradients=torch.empty((1, 3, Ht, Wt), device="cuda"),
+                               image=torch.empty((1, 3, Ht, Wt), device="cuda", dtype=torch.uint8), count=torch.zeros((1,), device="cuda", dtype=torch.int32))
+                    cast = lambda: hip.tsdf_raycast(vol, pb, Ht=Ht, Wt=Wt, **cam, **place, min_weight=1, z_near=0.0, z_far=z_far, step=trunc / 2, **out)      # noqa: E731
+                    compose = lambda: torch_raycast(torch, tsdf, obs, pb[0], Ht, Wt, cam["fx"], cam["fy"], cam["cx"], cam["cy"], origin, vs, 0.0, trunc / 2, n_steps)      # noqa: E731
+                    cast()
+                    td, tg, samples = compose()
+                    kd, covered = out["depth"][0, 0], int(out["count"][0])
+                    both = (kd != 0) & (td != 0)
+                    err = float((kd - td)[both].abs().max()) if bool(both.any()) else float("nan")
+                    gerr = float((out["gradients"][0] - tg)[:, both].abs().max()) if bool(both.any()) else float("nan")
+                    samples = int(samples)
+                    gk = captured(cast)
+                    tk, tt = [], []
+                    for _ in range(a.repeats):
+                        tk.append(timed(gk.replay, a.steps))
+                        tt.append(timed(compose, a.torch_steps))
+                    uk, ut, ux = statistics.median(tk), statistics.median(tt), statistics.median(tx)
+                    say(f"  {Wt}x{Ht} {view:6s}: {n_steps} steps, {covered} of {Ht * Wt} pixels covered (torch: {int((td != 0).sum())}; both {int(both.sum())}, "
+                        f"max |depth difference| {err:.2e}, max |gradient difference| {gerr:.2e})")
+                    say(f"    K26                {spread(tk)}   {samples / (Ht * Wt):6.1f} samples per ray inside the grid x 64 B = {samples * 64 / 1e6:8.1f} MB gathered = "
+                        f"{samples * 64 / uk / 1e6:6.3f} TB/s = {samples * 64 / uk / 1e6 / HBM_COPY_TBS * 100:5.1f} % of the {HBM_COPY_TBS} TB/s copy rate")
+                    say(f"    torch composition  {spread(tt)}   {ut / uk:6.1f}x K26")
+                    say(f"    K24 extract        {ux:8.1f} us            {ux / uk:6.2f}x K26" + ("   (extract is faster)" if ux < uk else ""))
+                    del gk
+            del gx, vol, tsdf, obs
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -225,10 +357,11 @@ def main() -> None:
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--dims", default="256,512")
     ap.add_argument("--mesh", action="store_true", help="measure K25 (the triangle mesh) instead; default --out profiles/tsdf/tsdfmesh.txt")
+    ap.add_argument("--raycast", action="store_true", help="measure K26 (the ray caster) instead; default --out profiles/tsdf/tsdfraycast.txt")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "tsdf", "tsdfmesh.txt" if a.mesh else "tsdfbench.txt")
+        a.out = os.path.join(ROOT, "profiles", "tsdf", "tsdfraycast.txt" if a.raycast else "tsdfmesh.txt" if a.mesh else "tsdfbench.txt")
     import torch
     from s2m2_amd import hip
     from tools.kbench import captured, spread, timed
@@ -238,8 +371,8 @@ def main() -> None:
         print(s, flush=True)
         lines.append(s)
 
-    if a.mesh:
-        mesh_main(a, torch, hip, say)
+    if a.mesh or a.raycast:
+        (raycast_main if a.raycast else mesh_main)(a, torch, hip, say)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
