@@ -1358,6 +1358,80 @@ typedef struct s2m2_tsdf_raycast_desc {
 } s2m2_tsdf_raycast_desc;
 int s2m2_tsdf_raycast(const s2m2_tsdf_raycast_desc* desc, void* stream);
 
+/*
+ * K27 -- the camera tracked against K24's volume: frame-to-model point-to-plane ICP with projective data association (KinectFusion's tracking
+ *   step).  The live frame is K15's maps; the model is what K26 rendered from `model_poses`: depth and the world-frame tsdf gradients.  The
+ *   refined pose is written into the DEVICE pose buffer that s2m2_tsdf_integrate / s2m2_tsdf_raycast read next, so that raycast -> track ->
+ *   integrate is one capturable chain without a host step.  No counterpart in the reference: the semantics are defined here and pinned by the
+ *   numpy oracle of tests/tsdf_track_oracle.py.  Still S2M2_ABI_VERSION 800: the entry points are added, nothing changes in place.
+ *   `cloud` holds the INPUT fields of s2m2_cloud with the meaning they have in s2m2_tsdf_desc: the B padded maps, H, W, Hp, Wp (fused crop),
+ *   camera and filter parameters, unfiltered.  Its outputs are IGNORED and the image is not needed.  mfx, mfy, mcx, mcy (the model camera, which
+ *   may differ from the live one) and max_dist are converted to fp32 once on the host; max_dist2 = max_dist * max_dist is formed once on the
+ *   host as fp32.
+ *   Per iteration it = 0 .. n_iters-1, per pair b with [R | t] = poses[b] (as the previous iteration left it) and [Rm | tm] = model_poses[b],
+ *   per pixel (v, u) of the UNPADDED live image, all in fp32, every operation ONE IEEE rounding, nothing fused into a multiply-add:
+ *     live     z, keep = K15's (the same device functions); skip unless keep (z > 0);   x = ((float)u - cx) * z / fx;   y = ((float)v - cy) * z / fy
+ *     world    c = (x - tx, y - ty, z - tz);   p_a = (r0a*c0 + r1a*c1) + r2a*c2   for a = x, y, z  (R^T applied: K26's form)
+ *     model    X = ((m00*px + m01*py) + m02*pz) + tmx;   Y, Z likewise with the rows 1 and 2 of Rm                              (K24's form)
+ *              skip unless Z > 0 and Z is finite
+ *              up = (mfx * X) / Z + mcx;   vp = (mfy * Y) / Z + mcy;   fu = rintf(up);   fv = rintf(vp)                           (half to even)
+ *              skip unless fu >= 0 && fu < Wt && fv >= 0 && fv < Ht   (float comparisons, before any conversion to int: a NaN skips)
+ *     surface  dm = model_depth[b, fv, fu];   skip unless dm > 0
+ *              g = model_gradients[b, 0..2, fv, fu];   s = (gx*gx + gy*gy) + gz*gz;   skip unless s > 0 and s is finite
+ *              q = sqrtf(s);   n = (gx / q, gy / q, gz / q)
+ *              mx = (fu - mcx) * dm / mfx;   my = (fv - mcy) * dm / mfy;   e = (mx - tmx, my - tmy, dm - tmz)
+ *              w_a = (m0a*e0 + m1a*e1) + m2a*e2                                                                                  (Rm^T applied)
+ *     gate     d = w - p;   skip unless (dx*dx + dy*dy) + dz*dz <= max_dist2   (a NaN skips)
+ *     row      r = (nx*dx + ny*dy) + nz*dz
+ *              J = (py*nz - pz*ny,  pz*nx - px*nz,  px*ny - py*nx,  nx,  ny,  nz)
+ *   Sums.  J0..J5 and r are widened to double; the 21 products Ji*Jj (i <= j), the 6 products Ji*r and r*r are exact in double, and they are
+ *     accumulated in double, with an integer count, over the pixels of the pair that were not skipped.  No floating-point atomics: a thread sums
+ *     its pixels, a wave its threads, a block its waves, and a fixed pass sums the per-tile partials, so the order of the additions depends on
+ *     the shapes alone and the result is bit-reproducible.  Any order is within (count-1) roundings of the exact sum.
+ *   Solve and update, per pair, in double:
+ *     status 1 if count < min_count; else status 2 if any of the 28 sums is not finite; else Cholesky of the 6 x 6 A = sum J J^T without
+ *     pivoting, status 2 at a pivot that is not > 0 (or not finite); xi = (omega, v) = A^-1 sum J r; status 2 if an entry of xi is not finite;
+ *     status 3 if |omega| > max_rot or |v| > max_trans.
+ *     E = I + a K + b K^2 with K = [omega]x, th = |omega|, a = sin(th) / th, b = (1 - cos(th)) / th^2 (th < 1e-4: a = 1 - th^2/6, b = 1/2 -
+ *     th^2/24);   R' = R E^T, its rows re-orthonormalised (row 0 normalised, row 1 minus its part along row 0 and normalised, row 2 = row 0 x
+ *     row 1);   t' = t - R' v.  Every entry is rounded to fp32 once; status 2 if one of them is not finite.  With status 0 the twelve numbers
+ *     replace poses[b]; with any other status poses[b] is left as it was, byte for byte, and the remaining iterations still run (they repeat the
+ *     verdict).  This moves the live points by p <- E p + v in the world.
+ *   systems  optional (B, n_iters, 32) float64, 8-byte aligned; the row of (b, it): [0..20] A's upper triangle, row-major; [21..26] sum J r;
+ *            [27] sum r*r; [28] count; [29] status; [30] |omega|; [31] |v| -- the norms with status 0 and 3, 0 with status 1 and 2.
+ *   residual optional (B,1,H,W) fp32: r of the LAST iteration's association (computed from the pose that iteration started from); the bit
+ *            pattern 0x7fc00000 at every pixel that was not kept or was skipped.  Every pixel is written.
+ *   workspace: >= s2m2_tsdf_track_workspace_bytes(B, H, W) bytes, 8-byte aligned: 32 doubles per tile of K15's raster walk (whole rows, as
+ *   many as fit 4096 pixels).
+ *   Two launches per iteration, no host step: the blocks walk K15's tiles and write one partial each; one block per pair sums the partials,
+ *   solves and updates.
+ *   Errors (before any device call): null descriptor; everything s2m2_tsdf_integrate checks of its maps and camera; null or misaligned (4 bytes)
+ *   poses, model_poses, model_depth, model_gradients; a null or misaligned (8 bytes) workspace; Ht or Wt <= 0 or B*Ht*Wt >= 2^31; mfx or mfy
+ *   zero or not finite as fp32; non-finite mcx or mcy; max_dist, max_rot or max_trans not finite or <= 0 as fp32; min_count < 6; n_iters outside
+ *   1 .. 64; systems not 8-byte aligned; residual not 4-byte aligned.
+ *   Non-finite poses or maps never form an address: they end in status 1 or 2.
+ *   Launch plans: s2m2_tsdf_track is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing.
+ *   Safe under stream capture (hipGraph).
+ */
+typedef struct s2m2_tsdf_track_desc {
+    s2m2_cloud_desc cloud;           /* the live maps: K24's meaning; outputs ignored, image not needed */
+    float*       poses;              /* DEVICE (B, 12) fp32 [R | t] row-major, world -> camera: the initial guess in, the refined pose out */
+    const float* model_poses;        /* DEVICE (B, 12): the poses K26 rendered the model maps from */
+    const float* model_depth;        /* (B,1,Ht,Wt) fp32: K26's depth */
+    const float* model_gradients;    /* (B,3,Ht,Wt) fp32: K26's gradients */
+    double*      systems;            /* (B, n_iters, 32) float64; optional */
+    float*       residual;           /* (B,1,H,W) fp32; optional */
+    void*        workspace;          /* >= s2m2_tsdf_track_workspace_bytes(B, H, W), 8-byte aligned */
+    int          Ht, Wt;             /* the model camera */
+    int          min_count;          /* >= 6 */
+    int          n_iters;            /* 1 .. 64 */
+    double       mfx, mfy, mcx, mcy;
+    double       max_dist;           /* correspondence gate, in the unit of z */
+    double       max_rot, max_trans; /* per-iteration step gate: radians, unit of z */
+} s2m2_tsdf_track_desc;
+size_t s2m2_tsdf_track_workspace_bytes(int B, int H, int W);   /* 0: bad extents */
+int s2m2_tsdf_track(const s2m2_tsdf_track_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

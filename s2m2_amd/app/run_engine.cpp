@@ -59,7 +59,7 @@
 //   s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T]
 //                   [--tsdf-min-weight N] [--tsdf-carve] --calib calib.txt --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply]
 //                   [--tsdf-render POSE [--tsdf-render-depth OUT.f32] [--tsdf-render-image OUT.u8] [--tsdf-render-step X]
-//                   [--tsdf-render-min-weight N]]
+//                   [--tsdf-render-min-weight N]] [--tsdf-track [--tsdf-track-iters N] [--tsdf-track-dist D] [--tsdf-poses-out FILE]]
 // Every line of LIST names LEFT.f32 RIGHT.f32 IMAGE.u8 (as above; raw uint8 (1,3,H,W) for the colours) and the twelve numbers of the pose
 //   [R | t], row-major, world -> camera, t in the unit of z; empty lines and lines that start with # are skipped.  The engine (one pair per run)
 //   runs per line and the maps are fused behind it; one extraction follows the last line.  --tsdf-dims: the voxels; --tsdf-voxel: their
@@ -73,6 +73,11 @@
 //   --tsdf-render-image, raw uint8 (1,3,H,W); the rays are sampled every --tsdf-render-step (default T / 2) from 0 to the farthest corner of the
 //   grid; --tsdf-render-min-weight: the frames a voxel needs (default --tsdf-min-weight's).  "tsdf_render_pixels" (the covered pixels) joins the
 //   printed line.
+//   --tsdf-track (K27, s2m2_tsdf_track): only the first line's pose is used as given.  For every later line the volume is rendered (K26) from
+//   the previous pose through the calib's left camera at H x W, the frame is tracked against that render from the same pose with
+//   --tsdf-track-iters iterations (default 10) and the gate --tsdf-track-dist (default T), and fused with the tracked pose; the twelve numbers
+//   of those lines are optional and ignored.  A frame whose last iteration was not accepted is not fused and the previous pose stays.
+//   "tsdf_tracked" and "tsdf_lost" join the printed line; --tsdf-poses-out: per frame one line of the twelve numbers and the status.
 //   LIST is parsed before the engine is loaded.  Prints {"tsdf_frames", "tsdf_points"} on a line of its own.
 #include <hip/hip_runtime.h>
 
@@ -452,6 +457,60 @@ static int render_tsdf(const Options& o, const s2m2_engine_info& m, const Calib&
     return 0;
 }
 
+// --tsdf-track (K27): what a tracked frame needs beside the fusion's buffers, and the step itself
+struct Tracker {
+    DeviceBuffer model_pose, depth, gradients, systems, workspace;
+    s2m2_tsdf_raycast_desc rd;
+    s2m2_tsdf_track_desc kd;
+    int n_iters = 0;
+
+    int make(const Options& o, const s2m2_engine_info& m, const Calib& cal, const s2m2_tsdf_desc& td) {
+        const size_t plane = (size_t)m.H * m.W, ws = s2m2_tsdf_track_workspace_bytes(1, m.H, m.W);
+        n_iters = o.tsdf_track_iters;
+        if (ws == 0) return fail("--tsdf-track: the image is too large");
+        if (DeviceBuffer::make(model_pose, 12 * sizeof(float)) || DeviceBuffer::make(depth, plane * sizeof(float)) ||
+            DeviceBuffer::make(gradients, 3 * plane * sizeof(float)) || DeviceBuffer::make(systems, (size_t)n_iters * 32 * sizeof(double)) ||
+            DeviceBuffer::make(workspace, ws))
+            return 1;
+        memset(&rd, 0, sizeof rd);
+        rd.volume = td.volume; rd.poses = model_pose.as<float>();
+        rd.depth = depth.as<float>(); rd.gradients = gradients.as<float>();
+        rd.B = 1; rd.Ht = m.H; rd.Wt = m.W;
+        rd.Nx = td.Nx; rd.Ny = td.Ny; rd.Nz = td.Nz;
+        rd.min_weight = o.tsdf_min_weight;
+        rd.fx = cal.fx; rd.fy = cal.fy; rd.cx = cal.cx; rd.cy = cal.cy;
+        memcpy(rd.origin, td.origin, sizeof rd.origin);
+        rd.voxel_size = td.voxel_size;
+        rd.z_near = 0.0; rd.step = 0.5 * td.trunc;
+        memset(&kd, 0, sizeof kd);
+        kd.cloud = td.cloud;
+        kd.poses = const_cast<float*>(td.poses); kd.model_poses = model_pose.as<float>();
+        kd.model_depth = depth.as<float>(); kd.model_gradients = gradients.as<float>();
+        kd.systems = systems.as<double>(); kd.workspace = workspace.h;
+        kd.Ht = m.H; kd.Wt = m.W;
+        kd.min_count = 100; kd.n_iters = n_iters;
+        kd.mfx = cal.fx; kd.mfy = cal.fy; kd.mcx = cal.cx; kd.mcy = cal.cy;
+        kd.max_dist = o.tsdf_track_dist; kd.max_rot = 0.2; kd.max_trans = 4.0 * td.trunc;
+        return 0;
+    }
+
+    // the frame whose maps the engine just wrote, from `pose` (the previous frame's): the refined pose stays in the fusion's pose buffer and
+    // comes back in `pose` where the last iteration was accepted -> its status in `status`
+    int step(const Options& o, float* pose, hipStream_t s, int& status) {
+        HIP_OK(hipMemcpy(model_pose.h, pose, 12 * sizeof(float), hipMemcpyHostToDevice), "upload");
+        HIP_OK(hipMemcpy(kd.poses, pose, 12 * sizeof(float), hipMemcpyHostToDevice), "upload");
+        rd.z_far = tsdf_far_corner(pose, o.tsdf_dims, o.tsdf_origin, o.tsdf_voxel);
+        if (s2m2_tsdf_raycast(&rd, s) != 0) return fail_lib("s2m2_tsdf_raycast failed");
+        if (s2m2_tsdf_track(&kd, s) != 0) return fail_lib("s2m2_tsdf_track failed");
+        HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_track");
+        double row[32];
+        HIP_OK(hipMemcpy(row, systems.as<double>() + (size_t)(n_iters - 1) * 32, sizeof row, hipMemcpyDeviceToHost), "download");
+        status = (int)row[29];
+        if (status == 0) HIP_OK(hipMemcpy(pose, kd.poses, 12 * sizeof(float), hipMemcpyDeviceToHost), "download");
+        return 0;
+    }
+};
+
 // --tsdf-frames (K24): the engine per line of LIST, the maps fused into the volume behind it, one extraction at the end
 static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& m, const std::vector<TsdfFrame>& frames, hipStream_t s) {
     if (m.B != 1) return fail("--tsdf-frames needs an engine of one pair per run");
@@ -478,9 +537,15 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
     td.max_weight = 32767; td.carve = o.tsdf_carve;
     memcpy(td.origin, o.tsdf_origin, sizeof td.origin);
     td.voxel_size = o.tsdf_voxel; td.trunc = o.tsdf_trunc;
+    Tracker tracker;
+    if (o.tsdf_track && tracker.make(o, m, cal, td)) return 1;
+    float pose[12];                                                          // --tsdf-track: the pose of the last frame that was fused
+    int tracked = 0, lost = 0;
+    std::string poses_out;
     std::vector<float> hl(img), hr(img);
     std::vector<unsigned char> hi(img);
     for (const TsdfFrame& fr : frames) {
+        const bool first = &fr == &frames[0];
         if (!read_raw(fr.left.c_str(), hl) || !read_raw(fr.right.c_str(), hr) || !read_raw_u8(fr.image.c_str(), hi)) {
             fprintf(stderr, "s2m2_run_engine: --tsdf-frames: %s and %s must be raw float32 and %s raw uint8 (1,3,%d,%d) files\n", fr.left.c_str(),
                     fr.right.c_str(), fr.image.c_str(), m.H, m.W);
@@ -489,11 +554,27 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
         HIP_OK(hipMemcpy(dl.h, hl.data(), img * sizeof(float), hipMemcpyHostToDevice), "upload");
         HIP_OK(hipMemcpy(dr.h, hr.data(), img * sizeof(float), hipMemcpyHostToDevice), "upload");
         HIP_OK(hipMemcpy(dimage.h, hi.data(), img, hipMemcpyHostToDevice), "upload");
-        HIP_OK(hipMemcpy(dpose.h, fr.pose, sizeof fr.pose, hipMemcpyHostToDevice), "upload");
+        if (!o.tsdf_track || first) HIP_OK(hipMemcpy(dpose.h, fr.pose, sizeof fr.pose, hipMemcpyHostToDevice), "upload");
         if (s2m2_engine_run(eng, dl.h, dr.h, dout[0].as<float>(), dout[1].as<float>(), dout[2].as<float>(), s) != 0) return fail_lib("engine run failed");
-        if (s2m2_tsdf_integrate(&td, s) != 0) return fail_lib("s2m2_tsdf_integrate failed");
+        int status = 0;
+        if (o.tsdf_track && first) memcpy(pose, fr.pose, sizeof pose);
+        if (o.tsdf_track && !first) {
+            if (int rc = tracker.step(o, pose, s, status)) return rc;
+            ++(status == 0 ? tracked : lost);
+        }
+        if (o.tsdf_track) {
+            char num[32];
+            for (int i = 0; i < 12; ++i) {
+                snprintf(num, sizeof num, "%.9g ", (double)pose[i]);
+                poses_out += num;
+            }
+            poses_out += std::to_string(status) + "\n";
+        }
+        if (status == 0 && s2m2_tsdf_integrate(&td, s) != 0) return fail_lib("s2m2_tsdf_integrate failed");
         HIP_OK(hipStreamSynchronize(s), "s2m2_tsdf_integrate");       // the next line overwrites the inputs
     }
+    if (o.tsdf_poses_out_path && !write_bytes(o.tsdf_poses_out_path, "", poses_out.data(), poses_out.size()))
+        return fail("cannot write the --tsdf-poses-out file");
     s2m2_tsdf_extract_desc ed;
     memset(&ed, 0, sizeof ed);
     ed.volume = dvol.h; ed.count = dcount.as<int32_t>(); ed.workspace = dws.h;
@@ -519,6 +600,7 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
         if (int rc = render_tsdf(o, m, cal, dvol.h, s, pixels)) return rc;
         render = ", \"tsdf_render_pixels\": " + std::to_string(pixels);
     }
+    if (o.tsdf_track) render += ", \"tsdf_tracked\": " + std::to_string(tracked) + ", \"tsdf_lost\": " + std::to_string(lost);
     if (!o.tsdf_mesh_path) {
         printf("{\"tsdf_frames\": %zu, \"tsdf_points\": %d%s}\n", frames.size(), n, render.c_str());
         return 0;
@@ -555,7 +637,7 @@ int main(int argc, char** argv) {
     if (const char* msg = check_options(o)) return fail(msg);
     std::vector<TsdfFrame> tsdf_frames;                   // LIST is parsed here, before the engine is loaded
     if (o.tsdf_frames_path) {
-        const std::string msg = read_tsdf_frames(o.tsdf_frames_path, tsdf_frames);
+        const std::string msg = read_tsdf_frames(o.tsdf_frames_path, tsdf_frames, o.tsdf_track != 0);
         if (!msg.empty()) return fail(msg.c_str());
     }
     // the ground truth is parsed and validated here, before the engine is loaded and anything touches the device

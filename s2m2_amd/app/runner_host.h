@@ -21,7 +21,8 @@ inline const char* const USAGE =
     "[--thresholds a,b,c] --metrics OUT.json]"
     " | s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T] "
     "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply] [--tsdf-render POSE [--tsdf-render-depth OUT.f32] "
-    "[--tsdf-render-image OUT.u8] [--tsdf-render-step X] [--tsdf-render-min-weight N]] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
+    "[--tsdf-render-image OUT.u8] [--tsdf-render-step X] [--tsdf-render-min-weight N]] [--tsdf-track [--tsdf-track-iters N] [--tsdf-track-dist D] "
+    "[--tsdf-poses-out FILE]] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
     "[--unfiltered]";
 
 // ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
@@ -41,12 +42,15 @@ struct Options {
     const char* tsdf_mesh_path = nullptr;
     const char *tsdf_render_arg = nullptr, *tsdf_render_depth_path = nullptr, *tsdf_render_image_path = nullptr;
     const char *tsdf_render_step_arg = nullptr, *tsdf_render_min_weight_arg = nullptr;
+    const char *tsdf_track_arg = nullptr, *tsdf_track_iters_arg = nullptr, *tsdf_track_dist_arg = nullptr, *tsdf_poses_out_path = nullptr;
 
     int tsdf_dims[3] = {0, 0, 0}, tsdf_min_weight = 1, tsdf_carve = 0;
     double tsdf_voxel = 0.0, tsdf_trunc = 0.0, tsdf_origin[3] = {0, 0, 0};      // tsdf_trunc: 4 * tsdf_voxel unless --tsdf-trunc
     float tsdf_render_pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};          // --tsdf-render: [R | t] row-major, world -> camera
     double tsdf_render_step = 0.0;                       // tsdf_trunc / 2 unless --tsdf-render-step
     int tsdf_render_min_weight = 1;                      // tsdf_min_weight unless --tsdf-render-min-weight
+    int tsdf_track = 0, tsdf_track_iters = 10;           // --tsdf-track (K27): the poses of the lines behind the first are tracked
+    double tsdf_track_dist = 0.0;                        // tsdf_trunc unless --tsdf-track-dist
     int repeat = 0, splat = 2, unfiltered = 0;
     long long min_size = 1, voxel_max = 0;               // voxel_max 0: a quarter of the image's pixels
     double max_jump = 1.0, voxel_size = 0.0;
@@ -104,6 +108,10 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--tsdf-render-image", true, &Options::tsdf_render_image_path},
     {"--tsdf-render-step", true, &Options::tsdf_render_step_arg},
     {"--tsdf-render-min-weight", true, &Options::tsdf_render_min_weight_arg},
+    {"--tsdf-track", false, &Options::tsdf_track_arg},
+    {"--tsdf-track-iters", true, &Options::tsdf_track_iters_arg},
+    {"--tsdf-track-dist", true, &Options::tsdf_track_dist_arg},
+    {"--tsdf-poses-out", true, &Options::tsdf_poses_out_path},
 };
 
 // "a,b,c": exactly three numbers, nothing behind them
@@ -181,6 +189,18 @@ inline const char* check_tsdf_options(Options& o) {
             o.tsdf_render_min_weight = (int)n;
         }
     }
+    // --tsdf-track (K27): the iterations per frame and the correspondence gate
+    if (!o.tsdf_track_arg && (o.tsdf_track_iters_arg || o.tsdf_track_dist_arg || o.tsdf_poses_out_path))
+        return "--tsdf-track-iters, --tsdf-track-dist and --tsdf-poses-out need --tsdf-track";
+    o.tsdf_track = o.tsdf_track_arg != nullptr;
+    o.tsdf_track_dist = o.tsdf_trunc;
+    if (o.tsdf_track_iters_arg) {
+        char* end = nullptr;
+        const long long n = strtoll(o.tsdf_track_iters_arg, &end, 10);
+        if (end == o.tsdf_track_iters_arg || *end || n < 1 || n > 64) return "--tsdf-track-iters: an integer in 1..64";
+        o.tsdf_track_iters = (int)n;
+    }
+    if (o.tsdf_track_dist_arg && !parse_positive(o.tsdf_track_dist_arg, o.tsdf_track_dist)) return "--tsdf-track-dist: a number > 0";
     return nullptr;
 }
 
@@ -209,7 +229,7 @@ inline const char* check_options(Options& o) {
     o.unfiltered = o.unfiltered_arg != nullptr;
     if (o.tsdf_frames_path || o.tsdf_dims_arg || o.tsdf_voxel_arg || o.tsdf_origin_arg || o.tsdf_trunc_arg || o.tsdf_min_weight_arg || o.tsdf_carve_arg ||
         o.tsdf_ply_path || o.tsdf_mesh_path || o.tsdf_render_arg || o.tsdf_render_depth_path || o.tsdf_render_image_path || o.tsdf_render_step_arg ||
-        o.tsdf_render_min_weight_arg)
+        o.tsdf_render_min_weight_arg || o.tsdf_track_arg || o.tsdf_track_iters_arg || o.tsdf_track_dist_arg || o.tsdf_poses_out_path)
         return check_tsdf_options(o);
     if (o.npos != 3 || o.repeat < 0) return USAGE;
     if (o.mesh_path && !o.calib_path) return "--calib and --mesh come together";
@@ -326,14 +346,15 @@ inline bool read_camera(const char* path, TargetCamera& c) {
 }
 
 // --tsdf-frames LIST: one frame per line -- LEFT.f32 RIGHT.f32 IMAGE.u8 and the twelve numbers of [R | t] row-major (world -> camera, t in the
-// unit of z); empty lines and lines that start with # are skipped.  The file names are used as they stand and hold no blanks
+// unit of z); empty lines and lines that start with # are skipped.  The file names are used as they stand and hold no blanks.  With `track`
+// (--tsdf-track) the twelve numbers are optional behind the first frame -- they are ignored there --, all twelve or none
 struct TsdfFrame {
     std::string left, right, image;
     float pose[12];
 };
 
 // "": fine, else the message (with the line's number)
-inline std::string read_tsdf_frames(const char* path, std::vector<TsdfFrame>& frames) {
+inline std::string read_tsdf_frames(const char* path, std::vector<TsdfFrame>& frames, bool track = false) {
     FILE* f = fopen(path, "r");
     if (!f) return std::string("--tsdf-frames ") + path + ": cannot open the file";
     char line[4096];
@@ -346,7 +367,9 @@ inline std::string read_tsdf_frames(const char* path, std::vector<TsdfFrame>& fr
         TsdfFrame fr;
         bool ok = sscanf(c, "%1023s %1023s %1023s%n", name[0], name[1], name[2], &used) == 3;
         c += used;
-        for (int i = 0; ok && i < 12; ++i) {
+        const bool bare = ok && track && !frames.empty() && !c[strspn(c, " \t\r\n")];      // a tracked frame without a pose
+        for (int i = 0; i < 12; ++i) fr.pose[i] = 0.f;
+        for (int i = 0; ok && !bare && i < 12; ++i) {
             char* end = nullptr;
             fr.pose[i] = strtof(c, &end);
             ok = end != c && isfinite(fr.pose[i]);

@@ -510,11 +510,13 @@ class TsdfRender:
     """What ``TsdfVolume.raycast`` returns, all on the device and in the target camera unless noted: ``depth`` (B,1,Ht,Wt) fp32 z of the first
     surface along the ray (0: hole), ``gradients_buf`` (B,3,Ht,Wt) fp32 or None: the unnormalised tsdf gradient at the hit in the WORLD frame,
     from the surface to free space (0 at holes), ``image`` (B,3,Ht,Wt) uint8 or None, ``count`` (B) int32 covered pixels or None; ``R``
-    (B,3,3) fp32: the rotations the maps were rendered with."""
+    (B,3,3) fp32: the rotations the maps were rendered with.  ``raycast`` also sets ``poses`` (B,12) fp32, the device pose buffer of the render,
+    and ``camera``, its ``Camera``: what ``TsdfVolume.track`` needs of the model side (None in a render built by hand without them)."""
 
     def __init__(self, depth: torch.Tensor, gradients_buf: Optional[torch.Tensor], image: Optional[torch.Tensor], count: Optional[torch.Tensor],
-                 R: torch.Tensor):
+                 R: torch.Tensor, poses: Optional[torch.Tensor] = None, camera: Optional[Camera] = None):
         self.depth, self.gradients_buf, self.image, self.count, self.R = depth, gradients_buf, image, count, R
+        self.poses, self.camera = poses, camera
 
     def normals(self) -> torch.Tensor:
         """(B,3,Ht,Wt) fp32 in the CAMERA frame: ``R @ G`` normalised in torch (a zero gradient stays zero); not part of the exact contract"""
@@ -528,6 +530,40 @@ class TsdfRender:
         if self.count is None:
             raise ValueError("TsdfRender.holes: raycast was called with want_count=False")
         return self.depth.shape[-2] * self.depth.shape[-1] - int(self.count[b].item())
+
+
+class TsdfTrack:
+    """What ``TsdfVolume.track`` returns, all on the device: ``poses`` (B,12) fp32, the refined [R | t] per pair (world -> camera; the buffer
+    that was passed in, where one was); ``R`` (B,3,3) and ``t`` (B,3): strided views of it; ``systems`` (B, n_iters, 32) float64 or None: per
+    iteration the normal equations (A's upper triangle, sum J r, sum r^2), the count of correspondences, the status (0 accepted, 1 too few
+    correspondences, 2 singular or non-finite, 3 step too long) and the norms of the step; ``residual`` (B,1,H,W) fp32 or None: the
+    point-to-plane distance of the last iteration's correspondences, NaN elsewhere."""
+
+    def __init__(self, poses: torch.Tensor, systems: Optional[torch.Tensor], residual: Optional[torch.Tensor]):
+        self.poses, self.systems, self.residual = poses, systems, residual
+        P = poses.view(poses.shape[0], 3, 4)
+        self.R, self.t = P[:, :, :3], P[:, :, 3]
+
+    def _last(self, b: int) -> torch.Tensor:
+        if self.systems is None:
+            raise ValueError("TsdfTrack: track was called with want_systems=False")
+        return self.systems[b, -1].cpu()
+
+    def status(self, b: int = 0) -> int:
+        """the status of pair b's last iteration -- reads ``systems`` on the host (synchronises), like the three below"""
+        return int(self._last(b)[29])
+
+    def count(self, b: int = 0) -> int:
+        """correspondences of the last iteration"""
+        return int(self._last(b)[28])
+
+    def rmse(self, b: int = 0) -> float:
+        """sqrt(sum r^2 / count) of the last iteration (NaN without a correspondence)"""
+        row = self._last(b)
+        return float((row[27] / row[28]).sqrt()) if row[28] > 0 else float("nan")
+
+    def ok(self, b: int = 0) -> bool:
+        return self.status(b) == 0
 
 
 class TsdfVolume:
@@ -555,6 +591,7 @@ class TsdfVolume:
         self.buffer = torch.zeros((Nz, Ny, Nx, 4), device=self.device, dtype=torch.int32)
         self._workspace = None
         self._mesh_workspace = None
+        self._track_workspace = None
 
     def reset(self) -> None:
         self.buffer.zero_()
@@ -581,14 +618,19 @@ class TsdfVolume:
         t = t.expand(B, 3) if t.dim() == 1 else t
         return torch.cat([R, t[:, :, None]], dim=2).reshape(B, 12).contiguous()
 
-    def integrate(self, disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, left_u8: torch.Tensor, *, R, t, fx: float, cx: float,
-                  cy: float, baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
+    def integrate(self, disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, left_u8: torch.Tensor, *, R=None, t=None, fx: float,
+                  cx: float, cy: float, baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
                   depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True,
-                  carve: bool = False) -> "TsdfVolume":
+                  carve: bool = False, poses: Optional[torch.Tensor] = None) -> "TsdfVolume":
         """``reproject``'s operands and conventions plus the pose of every pair (``p_cam = R @ p_world + t``, ``t`` in the unit of z): the B
         depth maps are fused into the volume in the order of the batch.  ``carve``: also the voxels between the camera and the band take the
-        free-space value 1.  One launch, no synchronisation, capturable; composes with ``segment(...).disp`` via ``filtered=False``."""
-        poses = self._poses(R, t, disp.shape[0])
+        free-space value 1.  Instead of ``R`` and ``t``, ``poses`` takes a device (B,12) fp32 buffer as it is (``TsdfTrack.poses``: a tracked
+        pose feeds the fusion without a copy).  One launch, no synchronisation, capturable; composes with ``segment(...).disp`` via
+        ``filtered=False``."""
+        if (poses is None) == (R is None or t is None):
+            raise ValueError("TsdfVolume.integrate: pass the poses either as R and t or as poses")
+        if poses is None:
+            poses = self._poses(R, t, disp.shape[0])
         hip.tsdf_integrate(self.buffer, disp, occ, conf, left_u8, poses,
                            **_binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered),
                            origin=self.origin, voxel_size=self.voxel_size, trunc=self.trunc, max_weight=self.max_weight, carve=carve)
@@ -669,4 +711,40 @@ class TsdfVolume:
         hip.tsdf_raycast(self.buffer, poses, Ht=Ht, Wt=Wt, fx=camera.fx, fy=camera.fy, cx=camera.cx, cy=camera.cy, origin=self.origin,
                          voxel_size=self.voxel_size, min_weight=min_weight, z_near=z_near, z_far=z_far, step=step, depth=depth,
                          gradients=gradients, image=image, count=count)
-        return TsdfRender(depth, gradients, image, count, poses.view(B, 3, 4)[:, :, :3])
+        return TsdfRender(depth, gradients, image, count, poses.view(B, 3, 4)[:, :, :3], poses, camera)
+
+    def track(self, disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, render: TsdfRender, *, R=None, t=None, poses=None, fx: float,
+              cx: float, cy: float, baseline: float, H: Optional[int] = None, W: Optional[int] = None, doffs: float = 0.0,
+              fy: Optional[float] = None, depth_scale: float = 1000.0, depth_trunc: Optional[float] = None, conf_min: float = 0.1,
+              occ_min: float = 0.5, filtered: bool = True, max_dist: Optional[float] = None, n_iters: int = 10, min_count: int = 100,
+              max_rot: float = 0.2, max_trans: Optional[float] = None, want_systems: bool = True, want_residual: bool = False) -> TsdfTrack:
+        """The pose of a new frame against the volume (K27, ``s2m2_tsdf_track``; the rule: include/s2m2_hip.h, K27): the live maps in
+        ``reproject``'s conventions (``H``, ``W``: the fused crop, default the maps' own size) are registered by ``n_iters`` iterations of
+        point-to-plane ICP with projective association to ``render``, a ``raycast`` of this volume WITH gradients from a nearby pose.  The
+        initial guess is ``R``, ``t`` in ``integrate``'s shapes, or ``poses``: a device (B,12) fp32 buffer that is refined IN PLACE (the one
+        ``integrate(poses=...)`` and the next ``raycast`` may read).  Defaults: ``max_dist`` = trunc (the correspondence gate), ``min_count``
+        = 100 correspondences, ``max_rot`` = 0.2 rad and ``max_trans`` = 4 * trunc per iteration; an iteration that fails one of them leaves
+        the pose as it was (``TsdfTrack.status``).  2 * n_iters launches, no synchronisation, capturable together with ``raycast`` and
+        ``integrate``."""
+        if render.gradients_buf is None or render.poses is None or render.camera is None:
+            raise ValueError("TsdfVolume.track: the render must come from raycast(..., want_gradients=True)")
+        B = disp.shape[0]
+        if (poses is None) == (R is None or t is None):
+            raise ValueError("TsdfVolume.track: pass the initial guess either as R and t or as poses")
+        if poses is None:
+            poses = self._poses(R, t, B, "track")
+        Hl = disp.shape[2] if H is None else int(H)
+        Wl = disp.shape[3] if W is None else int(W)
+        need = hip.tsdf_track_workspace_bytes(B, Hl, Wl)
+        if self._track_workspace is None or self._track_workspace.nbytes < need:
+            self._track_workspace = torch.empty((need // 8,), device=self.device, dtype=torch.float64)
+        n_iters = int(n_iters)
+        systems = torch.empty((B, n_iters, 32), device=self.device, dtype=torch.float64) if want_systems else None
+        residual = torch.empty((B, 1, Hl, Wl), device=self.device, dtype=torch.float32) if want_residual else None
+        kw = _binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered)
+        cam = render.camera
+        hip.tsdf_track(disp, occ, conf, poses, render.poses, render.depth, render.gradients_buf, H=Hl, W=Wl, **kw, mfx=cam.fx, mfy=cam.fy,
+                       mcx=cam.cx, mcy=cam.cy, max_dist=self.trunc if max_dist is None else max_dist, min_count=min_count, max_rot=max_rot,
+                       max_trans=4.0 * self.trunc if max_trans is None else max_trans, n_iters=n_iters, workspace=self._track_workspace,
+                       systems=systems, residual=residual)
+        return TsdfTrack(poses, systems, residual)

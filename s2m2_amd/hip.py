@@ -173,6 +173,14 @@ class TsdfRaycastDesc(ctypes.Structure):
                 ("z_near", ctypes.c_double), ("z_far", ctypes.c_double), ("step", ctypes.c_double)]
 
 
+class TsdfTrackDesc(ctypes.Structure):
+    """mirror of s2m2_tsdf_track_desc (include/s2m2_hip.h): K27, the camera tracked against a TSDF volume's rendered model maps"""
+    _fields_ = [("cloud", CloudDesc), ("poses", _vp), ("model_poses", _vp), ("model_depth", _vp), ("model_gradients", _vp), ("systems", _vp),
+                ("residual", _vp), ("workspace", _vp), ("Ht", _i), ("Wt", _i), ("min_count", _i), ("n_iters", _i), ("mfx", ctypes.c_double),
+                ("mfy", ctypes.c_double), ("mcx", ctypes.c_double), ("mcy", ctypes.c_double), ("max_dist", ctypes.c_double),
+                ("max_rot", ctypes.c_double), ("max_trans", ctypes.c_double)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -301,6 +309,8 @@ SIGNATURES = {
     "s2m2_tsdf_mesh_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_tsdf_mesh": (_i, [ctypes.POINTER(TsdfMeshDesc), _vp]),
     "s2m2_tsdf_raycast": (_i, [ctypes.POINTER(TsdfRaycastDesc), _vp]),
+    "s2m2_tsdf_track_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "s2m2_tsdf_track": (_i, [ctypes.POINTER(TsdfTrackDesc), _vp]),
 }
 
 
@@ -1408,6 +1418,7 @@ from .hip_register import register, register_workspace_bytes  # noqa: E402,F401
 from .hip_segment import segment, segment_tile, segment_workspace_bytes  # noqa: E402,F401
 # K23 (s2m2_voxel): likewise, from hip_voxel.py
 from .hip_voxel import voxel, voxel_home_slot, voxel_slots, voxel_tile_rows, voxel_workspace_bytes  # noqa: E402,F401
-# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract), K25 (s2m2_tsdf_mesh) and K26 (s2m2_tsdf_raycast): likewise, from hip_tsdf.py
-from .hip_tsdf import (RAYCAST_MAX_STEPS, tsdf_extract, tsdf_integrate, tsdf_mesh, tsdf_mesh_workspace_bytes, tsdf_raycast, tsdf_raycast_steps,  # noqa: E402,F401
-                       tsdf_tile_voxels, tsdf_workspace_bytes)
+# K24 (s2m2_tsdf_integrate, s2m2_tsdf_extract), K25 (s2m2_tsdf_mesh), K26 (s2m2_tsdf_raycast) and K27 (s2m2_tsdf_track): likewise, from
+# hip_tsdf.py
+from .hip_tsdf import (RAYCAST_MAX_STEPS, TRACK_MAX_ITERS, tsdf_extract, tsdf_integrate, tsdf_mesh, tsdf_mesh_workspace_bytes, tsdf_raycast,  # noqa: E402,F401
+                       tsdf_raycast_steps, tsdf_tile_voxels, tsdf_track, tsdf_track_workspace_bytes, tsdf_workspace_bytes)

@@ -1,9 +1,11 @@
 """K24 (``s2m2_tsdf_integrate`` / ``s2m2_tsdf_extract``, csrc/tsdf.hip): depth maps fused into a TSDF volume, and the volume's surface points;
 K25 (``s2m2_tsdf_mesh``, csrc/tsdf_mesh.hip): that surface as a triangle mesh; K26 (``s2m2_tsdf_raycast``, csrc/tsdf_raycast.hip): the volume
-ray-cast into the depth, gradient and colour maps of a camera.
+ray-cast into the depth, gradient and colour maps of a camera; K27 (``s2m2_tsdf_track``, csrc/tsdf_track.hip): the camera tracked against those
+maps.
 The descriptor mirrors and the signatures are in hip.py with all the others (``hip.load()`` binds every symbol there); this module holds the
 wrappers, which hip.py re-exports as ``hip.tsdf_integrate``, ``hip.tsdf_extract``, ``hip.tsdf_mesh``, ``hip.tsdf_raycast``,
-``hip.tsdf_raycast_steps``, ``hip.tsdf_workspace_bytes``, ``hip.tsdf_mesh_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
+``hip.tsdf_raycast_steps``, ``hip.tsdf_track``, ``hip.tsdf_track_workspace_bytes``, ``hip.tsdf_workspace_bytes``,
+``hip.tsdf_mesh_workspace_bytes`` and ``hip.tsdf_tile_voxels``."""
 import ctypes
 import math
 from typing import Optional, Sequence, Tuple
@@ -198,6 +200,84 @@ def tsdf_raycast(volume: torch.Tensor, poses: torch.Tensor, *, Ht: int, Wt: int,
     d.z_near, d.z_far, d.step = float(z_near), float(z_far), float(step)
     with torch.cuda.device(volume.device):
         _h._check(_h.load().s2m2_tsdf_raycast(ctypes.byref(d), _h._stream()), "s2m2_tsdf_raycast")
+
+
+TRACK_MAX_ITERS = 64
+
+
+def _positive_f32(what: str, name: str, x: float) -> float:
+    if not (math.isfinite(float(x)) and abs(float(x)) <= 3.4e38 and _f32(x) > 0.0):
+        raise ValueError(f"{what}: {name} must be finite and > 0 in fp32, got {x}")
+    return float(x)
+
+
+def tsdf_track(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, poses: torch.Tensor, model_poses: torch.Tensor,
+               model_depth: torch.Tensor, model_gradients: torch.Tensor, *, H: int, W: int, fx: float, fy: float, cx: float, cy: float,
+               baseline: float, doffs: float = 0.0, depth_scale: float = 1000.0, depth_trunc: float = 0.0, conf_min: float = 0.1,
+               occ_min: float = 0.5, unfiltered: bool = False, mfx: float, mfy: float, mcx: float, mcy: float, max_dist: float,
+               min_count: int = 6, max_rot: float, max_trans: float, n_iters: int, workspace: torch.Tensor,
+               systems: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> None:
+    """s2m2_tsdf_track (K27): the live frame -- the B padded maps (B,1,Hp,Wp) fp32 with the fused crop H x W and K15's camera and filter
+    numbers -- is registered to the model maps that ``tsdf_raycast`` rendered from ``model_poses`` (B,12) through the camera mfx, mfy, mcx,
+    mcy: ``model_depth`` (B,1,Ht,Wt) and ``model_gradients`` (B,3,Ht,Wt) fp32.  ``poses`` (B,12) fp32 on the device ([R | t] row-major,
+    world -> camera) holds the initial guess and is REFINED IN PLACE by ``n_iters`` point-to-plane iterations.  Optional outputs the caller
+    allocated: ``systems`` (B, n_iters, 32) float64 and ``residual`` (B,1,H,W) fp32; ``workspace``: ``tsdf_track_workspace_bytes`` bytes.
+    Thin: no allocation, no synchronisation."""
+    what = "tsdf_track"
+    _h._resident(what, disp, occ, conf, poses, model_poses, model_depth, model_gradients, workspace, systems, residual)
+    _h._contig(what, disp, occ, conf, poses, model_poses, model_depth, model_gradients, workspace, systems, residual)
+    d = _h.TsdfTrackDesc()
+    if int(H) != H or int(W) != W:
+        raise ValueError(f"{what}: H and W must be integers, got {H} and {W}")
+    B, H, W = _h._cloud_inputs(what, d.cloud, disp, occ, conf, None, int(H), int(W), fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc,
+                               conf_min, occ_min, unfiltered)
+    if not (1 <= H <= disp.shape[2] and 1 <= W <= disp.shape[3]):
+        raise ValueError(f"{what}: the crop H={H} W={W} must be positive and no larger than the maps {tuple(disp.shape[2:])}")
+    for name, t in (("poses", poses), ("model_poses", model_poses)):
+        if t is None:
+            raise ValueError(f"{what}: {name} is required")
+        _h._mat(t, (B, 12), torch.float32, f"{what}: {name}")
+    if model_depth is None or model_depth.dim() != 4:
+        raise ValueError(f"{what}: model_depth must be a (B,1,Ht,Wt) fp32 tensor")
+    Ht, Wt = model_depth.shape[2:]
+    if Ht < 1 or Wt < 1 or B * Ht * Wt >= 1 << 31:
+        raise ValueError(f"{what}: bad model extents B={B} Ht={Ht} Wt={Wt} (positive, B*Ht*Wt < 2^31)")
+    _h._mat(model_depth, (B, 1, Ht, Wt), torch.float32, f"{what}: model_depth")
+    if model_gradients is None:
+        raise ValueError(f"{what}: model_gradients is required")
+    _h._mat(model_gradients, (B, 3, Ht, Wt), torch.float32, f"{what}: model_gradients")
+    for name, x in (("mfx", mfx), ("mfy", mfy)):
+        if not math.isfinite(float(x)) or abs(float(x)) > 3.4e38 or _f32(x) == 0.0:
+            raise ValueError(f"{what}: {name} must be finite and non-zero in fp32, got {x}")
+    if not (math.isfinite(float(mcx)) and math.isfinite(float(mcy))):
+        raise ValueError(f"{what}: mcx and mcy must be finite, got {mcx} and {mcy}")
+    d.max_dist = _positive_f32(what, "max_dist", max_dist)
+    d.max_rot = _positive_f32(what, "max_rot", max_rot)
+    d.max_trans = _positive_f32(what, "max_trans", max_trans)
+    if int(min_count) != min_count or min_count < 6:
+        raise ValueError(f"{what}: min_count must be an integer >= 6, got {min_count}")
+    if int(n_iters) != n_iters or not 1 <= n_iters <= TRACK_MAX_ITERS:
+        raise ValueError(f"{what}: n_iters must be an integer in 1..{TRACK_MAX_ITERS}, got {n_iters}")
+    n_iters = int(n_iters)
+    if systems is not None:
+        _h._mat(systems, (B, n_iters, 32), torch.float64, f"{what}: systems")
+    if residual is not None:
+        _h._mat(residual, (B, 1, H, W), torch.float32, f"{what}: residual")
+    need = tsdf_track_workspace_bytes(B, H, W)
+    if workspace is None or workspace.nbytes < need or workspace.data_ptr() % 8:
+        raise ValueError(f"{what}: an 8-byte aligned workspace of {need} bytes is required")
+    d.poses, d.model_poses = poses.data_ptr(), model_poses.data_ptr()
+    d.model_depth, d.model_gradients = model_depth.data_ptr(), model_gradients.data_ptr()
+    d.systems, d.residual, d.workspace = _h._ptr(systems), _h._ptr(residual), workspace.data_ptr()
+    d.Ht, d.Wt, d.min_count, d.n_iters = Ht, Wt, int(min_count), n_iters
+    d.mfx, d.mfy, d.mcx, d.mcy = float(mfx), float(mfy), float(mcx), float(mcy)
+    with torch.cuda.device(disp.device):
+        _h._check(_h.load().s2m2_tsdf_track(ctypes.byref(d), _h._stream()), "s2m2_tsdf_track")
+
+
+def tsdf_track_workspace_bytes(B: int, H: int, W: int) -> int:
+    """bytes of ``tsdf_track``'s workspace: 32 doubles per tile (whole rows, as many as fit 4096 pixels) of the B live frames"""
+    return _h._extent_query("s2m2_tsdf_track_workspace_bytes", "tsdf_track", B=B, H=H, W=W)
 
 
 def tsdf_workspace_bytes(Nx: int, Ny: int, Nz: int) -> int:

@@ -231,6 +231,23 @@ def render_tsdf(volume, calib, R, t, size=None):
         return volume.raycast(camera, R, t)
 
 
+def track_tsdf(volume, disp, calib, R, t, depth_trunc=None, n_iters=10, **gates):
+    """``integrate_tsdf``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter) for the pose of a new frame:
+    ``volume`` (a ``cloud.TsdfVolume``) is rendered from the guess ``R`` (3,3), ``t`` (3,) at the size of ``disp`` (H,W), and the frame is
+    tracked against that render from the same guess (``cloud.TsdfVolume.track``; ``gates``: its max_dist, min_count, max_rot, max_trans).
+    Returns ``(R, t, ok)``: (3,3) and (3,) fp32 tensors on the device, as the accepted iterations left them, and whether the last
+    iteration was accepted (read on the host: synchronises)."""
+    disp_t = torch.as_tensor(disp).to(device=volume.device, dtype=torch.float32).contiguous()[None, None]
+    H, W = disp_t.shape[-2:]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(volume.device):
+        render = render_tsdf(volume, calib, R, t, size=(W, H))
+        tr = volume.track(disp_t, disp_t, disp_t, render, R=R, t=t, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0,
+                          cy=float(cam0[1, 2]) / 2.0, baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc,
+                          filtered=False, n_iters=n_iters, **gates)
+    return tr.R[0], tr.t[0], tr.ok(0)
+
+
 def filter_speckles(disp, calib, depth_trunc=None, max_jump=1.0, min_size=100):
     """``get_pointcloud``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter: ``disp`` (H,W) arrives filtered, -1
     where invalid) -> the (H,W) fp32 disparity on the device with -1 also wherever the pixel's 4-connected component of similar disparity

@@ -371,6 +371,24 @@ int main(int argc, char** argv) {
             Options x;
             CHECK(rendered({"--tsdf-render", pose, "--tsdf-render-depth", "d.f32", "--tsdf-render-min-weight", bad}, x) == "--tsdf-render-min-weight: an integer in 1..32767");
         }
+        // --tsdf-track (K27): the flag, the iterations and the gate with their defaults
+        Options k0, k1, k2;
+        CHECK(rendered({"--tsdf-track"}, k0) == "engine" && k0.tsdf_track == 1 && k0.tsdf_track_iters == 10 && k0.tsdf_track_dist == 0.25 && !k0.tsdf_poses_out_path);
+        CHECK(rendered({"--tsdf-track", "--tsdf-track-iters", "64", "--tsdf-track-dist", "0.5", "--tsdf-poses-out", "p.txt"}, k1) == "engine");
+        CHECK(k1.tsdf_track_iters == 64 && k1.tsdf_track_dist == 0.5 && k1.tsdf_poses_out_path != nullptr && r0.tsdf_track == 0);
+        CHECK(tsdf({"--tsdf-track"}, k2).find("need --tsdf-frames") != std::string::npos);
+        for (const char* flag : {"--tsdf-track-iters", "--tsdf-track-dist", "--tsdf-poses-out"}) {
+            Options x;
+            CHECK(rendered({flag, "1"}, x) == "--tsdf-track-iters, --tsdf-track-dist and --tsdf-poses-out need --tsdf-track");
+        }
+        for (const char* bad : {"0", "-1", "65", "ten", "2.5", ""}) {
+            Options x;
+            CHECK(rendered({"--tsdf-track", "--tsdf-track-iters", bad}, x) == "--tsdf-track-iters: an integer in 1..64");
+        }
+        for (const char* bad : {"0", "-1", "nan", "inf", "", "2cm"}) {
+            Options x;
+            CHECK(rendered({"--tsdf-track", "--tsdf-track-dist", bad}, x) == "--tsdf-track-dist: a number > 0");
+        }
         {
             const float at[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};                       // the camera in the world's origin
             const float back[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1};                     // p_cam = p + (0,0,1): the centre is (0,0,-1)

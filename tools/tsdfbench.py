@@ -23,7 +23,7 @@ leaves out, so a low share with carve 0 says that the launch is bound by the vox
 Extract: the surface points of the volumes above after the B = 4 call, against nonzero + gathers in torch (which synchronises to size its
 result); the counts are compared.
 
-    python tools/tsdfbench.py [--steps 20] [--torch-steps 3] [--repeats 5] [--forward] [--dims 256,512] [--mesh | --raycast] [--out FILE]
+    python tools/tsdfbench.py [--steps 20] [--torch-steps 3] [--repeats 5] [--forward] [--dims 256,512] [--mesh | --raycast | --track] [--out FILE]
 
 --mesh (K25, s2m2_tsdf_mesh; default --out profiles/tsdf/tsdfmesh.txt) measures the triangle mesh instead, on the same volumes (the B = 4, carve 1
 call of each scene, fused once): K25, s2m2_tsdf_extract alone on the same volume (what the triangles cost on top of the vertices), and the same
@@ -43,6 +43,17 @@ voxel may take another cell or another step, which shows as a few pixels covered
 on the host.  GATHERED BYTES: a sample inside the grid reads 8 voxels x 8 B = 64 B; the samples a ray takes inside the grid up to its hit are
 counted by the torch march (K26's own clip may take a few more at the box's faces), and samples x 64 B over K26's time is printed as a share of
 the 6.29 TB/s copy rate.  Neighbouring rays share most of those bytes in the caches, so the figure is the gather rate, not HBM traffic.
+
+--track (K27, s2m2_tsdf_track; default --out profiles/tsdf/tsdftrack.txt) measures the tracker: a curved surface around 2 m fused once at the
+identity into the 256^3 and 512^3 volumes, K26's depth and gradient maps of it at 640x480 and 1216x1024 from the identity, and live frames of
+1216x1024 and 640x480 of the same surface, tracked from a pose 0.01 rad and 1 cm off.  Timed as hipGraph replays: the call of 10 iterations (per
+iteration: a tenth; per launch: a twentieth -- the MEAN of the sums launch and the solve launch, which this tool cannot tell apart; the kernel
+trace of a profiler run can), and the chain raycast + track + integrate of one frame; both also as a share of an S forward at 1216x1024 (7.97
+ms).  The replays go on from the pose the call before left, i.e. at the converged pose, where the work is the same.  MANDATORY BYTES per
+iteration: the three live maps read once (12 B per live pixel) plus 16 B (depth and three gradient planes) per live pixel that lands inside
+the model image; over the time of an iteration they are printed as a share of the 6.29 TB/s copy rate.  Beside it: the same 28 sums and the
+count composed from torch ops -- the per-pixel rule as whole-image fp32 tensors, four gathers, and J^T J as one float64 matmul -- compared
+with K27's first row of `systems` (torch's arithmetic is not the rule's bit for bit; a pixel on the gate's edge may fall on the other side).
 """
 import argparse
 import os
@@ -349,6 +360,130 @@ def raycast_main(a, torch, hip, say) -> None:
             del gx, vol, tsdf, obs
 
 
+FORWARD_MS = 7.97                                        # an S forward at 1216x1024 fp16 (profiles/: the flagship measurement)
+
+
+def torch_track_sums(torch, disp, pose, mpose, md, mg, cam, mcam, max_dist):
+    """one iteration's sums of K27 from torch ops: disp (H,W), md (Ht,Wt), mg (3,Ht,Wt) -> (sums (28) float64, count, live pixels inside the
+    model image)"""
+    Hl, Wl = disp.shape
+    Ht, Wt = md.shape
+    dev = disp.device
+    q, m = pose.tolist(), mpose.tolist()
+    v, u = torch.meshgrid(torch.arange(Hl, device=dev, dtype=torch.float32), torch.arange(Wl, device=dev, dtype=torch.float32), indexing="ij")
+    z = torch.where(disp <= 0, 1e9, (cam["baseline"] * cam["fx"]) / (disp + cam["doffs"])) / cam["depth_scale"]
+    keep = (z > 0) & (z < cam["depth_trunc"])
+    x, y = (u - cam["cx"]) * z / cam["fx"], (v - cam["cy"]) * z / cam["fy"]
+    c = (x - q[3], y - q[7], z - q[11])
+    p = [q[a] * c[0] + q[4 + a] * c[1] + q[8 + a] * c[2] for a in range(3)]
+    X, Y, Z = (m[4 * r] * p[0] + m[4 * r + 1] * p[1] + m[4 * r + 2] * p[2] + m[4 * r + 3] for r in range(3))
+    fu, fv = torch.round(mcam["fx"] * X / Z + mcam["cx"]), torch.round(mcam["fy"] * Y / Z + mcam["cy"])
+    inside = keep & (Z > 0) & torch.isfinite(Z) & (fu >= 0) & (fu < Wt) & (fv >= 0) & (fv < Ht)
+    pix = torch.where(inside, fv * Wt + fu, 0.0).long().reshape(-1)
+    dm = md.reshape(-1)[pix].reshape(Z.shape)
+    g = [mg[a].reshape(-1)[pix].reshape(Z.shape) for a in range(3)]
+    s = g[0] * g[0] + g[1] * g[1] + g[2] * g[2]
+    n = [ga / torch.sqrt(s) for ga in g]
+    e = ((fu - mcam["cx"]) * dm / mcam["fx"] - m[3], (fv - mcam["cy"]) * dm / mcam["fy"] - m[7], dm - m[11])
+    w = [m[a] * e[0] + m[4 + a] * e[1] + m[8 + a] * e[2] for a in range(3)]
+    d = [w[a] - p[a] for a in range(3)]
+    used = inside & (dm > 0) & (s > 0) & torch.isfinite(s) & (d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= max_dist * max_dist)
+    r = n[0] * d[0] + n[1] * d[1] + n[2] * d[2]
+    J = torch.stack([p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0], n[0], n[1], n[2], r], -1)
+    J = torch.where(used[..., None], J, 0.0).reshape(-1, 7).double()
+    A = J.T @ J
+    iu = torch.triu_indices(6, 6, device=dev)
+    return torch.cat([A[iu[0], iu[1]], A[:6, 6], A[6:, 6]]), used.sum(), inside.sum()
+
+
+def track_main(a, torch, hip, say) -> None:
+    import math
+    from tools.kbench import captured, spread, timed
+    n_iters = 10
+    c1, s1 = math.cos(0.01), math.sin(0.01)
+    start = [c1, 0, s1, 0.01, 0, 1, 0, -0.005, -s1, 0, c1, 0.005]                     # 0.01 rad about y and about 1 cm off the true pose
+    ident = torch.tensor([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], device="cuda", dtype=torch.float32)
+
+    def frame(Wl, Hl):
+        """the live maps of the curved surface at Wl x Hl and its camera"""
+        k = Wl / W
+        cam = dict(CAM, fx=CAM["fx"] * k, fy=CAM["fy"] * k, cx=CAM["cx"] * k, cy=CAM["cy"] * Hl / H)
+        v, u = torch.meshgrid(torch.arange(Hl, device="cuda", dtype=torch.float32), torch.arange(Wl, device="cuda", dtype=torch.float32), indexing="ij")
+        U, V = CAM["cx"] + (u - cam["cx"]) / k, CAM["cy"] + (v - cam["cy"]) / k        # the pixel of the 1216 x 1024 frame on the same ray
+        z = 2.0 + 0.15 * torch.sin(U / 90.0) + 0.12 * torch.cos(V / 70.0) + 0.1 * torch.sin((U + V) / 110.0)
+        return (cam["baseline"] * cam["fx"] / 1000.0 / z)[None, None].contiguous(), cam
+
+    frames = {size: frame(*size) for size in ((W, H), (640, 480))}
+    one = {size: torch.ones((1, 1, size[1], size[0]), device="cuda") for size in frames}
+    img = {size: torch.zeros((1, 3, size[1], size[0]), device="cuda", dtype=torch.uint8) for size in frames}
+    for N in (int(x) for x in a.dims.split(",")):
+        vs = 2.048 / N
+        origin, trunc = (-1.024 + vs / 2, -1.024 + vs / 2, 1.0), 4 * vs
+        place = dict(origin=origin, voxel_size=vs)
+        vol = torch.zeros((N, N, N, 4), device="cuda", dtype=torch.int32)
+        disp0, cam0 = frames[(W, H)]
+        hip.tsdf_integrate(vol, disp0, one[(W, H)], one[(W, H)], img[(W, H)], ident, **cam0, **place, trunc=trunc, max_weight=64, carve=True)
+        z_far = max(math.dist([0, 0, 0], [origin[c] + (N - 1) * vs * ((corner >> c) & 1) for c in range(3)]) for corner in range(8))
+        say(f"track     {N}^3: voxel {vs * 1000:.0f} mm, max_dist = trunc = {trunc * 1000:.0f} mm, {n_iters} iterations, start 0.01 rad / 12 mm off")
+        for (Wt, Ht) in ((640, 480), (W, H)):
+            mcam = {k: frames[(Wt, Ht)][1][k] for k in ("fx", "fy", "cx", "cy")}
+            md = torch.empty((1, 1, Ht, Wt), device="cuda")
+            mg = torch.empty((1, 3, Ht, Wt), device="cuda")
+            cast = lambda pb: hip.tsdf_raycast(vol, pb, Ht=Ht, Wt=Wt, **mcam, **place, min_weight=1, z_near=0.0, z_far=z_far, step=trunc / 2, depth=md, gradients=mg)      # noqa: E731
+            cast(ident)
+            for (Wl, Hl) in ((W, H), (640, 480)):
+                disp, cam = frames[(Wl, Hl)]
+                maps = (disp, one[(Wl, Hl)], one[(Wl, Hl)])
+                ws = torch.empty(hip.tsdf_track_workspace_bytes(1, Hl, Wl) // 8, device="cuda", dtype=torch.float64)
+                pb = torch.tensor([start], device="cuda", dtype=torch.float32)
+                systems = torch.zeros((1, n_iters, 32), device="cuda", dtype=torch.float64)
+                kw = dict(H=Hl, W=Wl, **cam, mfx=mcam["fx"], mfy=mcam["fy"], mcx=mcam["cx"], mcy=mcam["cy"], max_dist=trunc, min_count=100, max_rot=0.2,
+                          max_trans=4 * trunc, workspace=ws)
+                track = lambda: hip.tsdf_track(*maps, pb, ident, md, mg, n_iters=n_iters, systems=systems, **kw)      # noqa: E731
+                mp = ident.clone()
+
+                def chain():
+                    mp.copy_(pb)
+                    cast(mp)
+                    hip.tsdf_track(*maps, pb, mp, md, mg, n_iters=n_iters, systems=systems, **kw)
+                    hip.tsdf_integrate(vol, *maps, img[(Wl, Hl)], pb, **cam, **place, trunc=trunc, max_weight=64, carve=True)
+
+                compose = lambda: torch_track_sums(torch, disp[0, 0], torch.tensor(start), ident[0].cpu(), md[0, 0], mg[0], cam, mcam, trunc)      # noqa: E731
+                track()
+                first = systems[0, 0].cpu()
+                statuses = systems[0, :, 29].int().tolist()
+                ts, tc, tin = compose()
+                rel = float(((ts.cpu() - first[:28]).abs() / first[:28].abs().clamp_min(1e-30)).max())
+                t_rot, t_tr = float(torch.arccos(((pb[0, 0] + pb[0, 5] + pb[0, 10] - 1) / 2).clamp(-1, 1))), float(pb[0, [3, 7, 11]].norm())
+                gt = captured(track)
+                tk, tt = [], []
+                for _ in range(a.repeats):
+                    tk.append(timed(gt.replay, a.steps))
+                    tt.append(timed(compose, a.torch_steps))
+                del gt
+                cast(ident)
+                pb.copy_(torch.tensor([start], device="cuda"))
+                keep = vol.clone()                                               # the chain fuses a frame per replay: timed on a volume of its own
+                gc = captured(chain)
+                tch = [timed(gc.replay, a.steps) for _ in range(a.repeats)]
+                del gc
+                vol.copy_(keep)
+                del keep
+                cast(ident)
+                uk, ut, uc = statistics.median(tk), statistics.median(tt), statistics.median(tch)
+                mandatory = 12 * Hl * Wl + 16 * int(tin)
+                say(f"  live {Wl}x{Hl} against model {Wt}x{Ht}: {int(first[28])} correspondences of {Hl * Wl} pixels in the first iteration (torch: {int(tc)}, "
+                    f"largest relative difference of a sum {rel:.1e}); statuses {statuses}; left {t_rot:.1e} rad, {t_tr * 1000:.2f} mm from the true pose")
+                say(f"    K27, {n_iters} iterations  {spread(tk)}   {uk / n_iters:7.1f} us per iteration, {uk / n_iters / 2:6.1f} us per launch (mean of two)   "
+                    f"{uk / FORWARD_MS / 10:.2f} % of an S forward ({FORWARD_MS} ms)")
+                say(f"    mandatory bytes per iteration {mandatory} = {mandatory / (uk / n_iters) / 1e6:6.3f} TB/s = "
+                    f"{mandatory / (uk / n_iters) / 1e6 / HBM_COPY_TBS * 100:5.1f} % of the {HBM_COPY_TBS} TB/s copy rate")
+                say(f"    torch composition of one iteration's sums  {spread(tt)}   {ut / (uk / n_iters):6.1f}x an iteration of K27" +
+                    ("   (torch is faster)" if ut < uk / n_iters else ""))
+                say(f"    raycast + track + integrate  {spread(tch)}   {uc / FORWARD_MS / 10:.2f} % of an S forward")
+        del vol
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -358,10 +493,12 @@ def main() -> None:
     ap.add_argument("--dims", default="256,512")
     ap.add_argument("--mesh", action="store_true", help="measure K25 (the triangle mesh) instead; default --out profiles/tsdf/tsdfmesh.txt")
     ap.add_argument("--raycast", action="store_true", help="measure K26 (the ray caster) instead; default --out profiles/tsdf/tsdfraycast.txt")
+    ap.add_argument("--track", action="store_true", help="measure K27 (the tracker) instead; default --out profiles/tsdf/tsdftrack.txt")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "tsdf", "tsdfraycast.txt" if a.raycast else "tsdfmesh.txt" if a.mesh else "tsdfbench.txt")
+        a.out = os.path.join(ROOT, "profiles", "tsdf",
+                             "tsdftrack.txt" if a.track else "tsdfraycast.txt" if a.raycast else "tsdfmesh.txt" if a.mesh else "tsdfbench.txt")
     import torch
     from s2m2_amd import hip
     from tools.kbench import captured, spread, timed
@@ -371,8 +508,8 @@ def main() -> None:
         print(s, flush=True)
         lines.append(s)
 
-    if a.mesh or a.raycast:
-        (raycast_main if a.raycast else mesh_main)(a, torch, hip, say)
+    if a.mesh or a.raycast or a.track:
+        (track_main if a.track else raycast_main if a.raycast else mesh_main)(a, torch, hip, say)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
