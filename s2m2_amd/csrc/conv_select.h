@@ -92,20 +92,27 @@ inline ConvChoice conv_select_frag(const Args& a, int tile, int cb, int slots, i
     const long long b4 = (long long)a.N * ((a.W + 31) / 32) * ((a.H + 3) / 4) * (a.Cout / cb);
     const long long b5 = (long long)a.N * ((a.W + 39) / 40) * ((a.H + 3) / 4) * (a.Cout / cb);
     const long long cost4 = ((b4 + slots - 1) / slots) * 4, cost5 = ((b5 + slots - 1) / slots) * 5;
-    const int PH = tile == 2 || tile == 4 ? tile : (force_ph == 2 || force_ph == 4) ? force_ph : (a.epi != S2M2_EPI_NONE || b4 <= small) ? 2 : 4;
     const bool one_op = a.epi == S2M2_EPI_ADD || a.epi == S2M2_EPI_MUL;
-    bool wide = false;
-    if (one_op && (tile == 40 || (tile == 0 && aux_pw == 40 && force_ph == 0))) wide = tile == 40 || (b4 > small && cost5 < cost4 + 4);
-    else if (PH == 4 && a.epi == S2M2_EPI_NONE) wide = tile == 40 || force_pw == 40 || (tile == 0 && force_pw != 32 && cost5 < cost4);
-    const int ph = wide ? 4 : PH, pw = wide ? 40 : 32;
+    int ph, pw;
+    if (tile == 2 || tile == 4 || tile == 40) {                   // a forced form is taken as it is or refused below, never replaced by another
+        ph = tile == 2 ? 2 : 4;
+        pw = tile == 40 ? 40 : 32;
+    } else {
+        const int PH = (force_ph == 2 || force_ph == 4) ? force_ph : (a.epi != S2M2_EPI_NONE || b4 <= small) ? 2 : 4;
+        bool wide = false;
+        if (one_op && tile == 0 && aux_pw == 40 && force_ph == 0) wide = b4 > small && cost5 < cost4 + 4;
+        else if (PH == 4 && a.epi == S2M2_EPI_NONE) wide = force_pw == 40 || (tile == 0 && force_pw != 32 && cost5 < cost4);
+        ph = wide ? 4 : PH;
+        pw = wide ? 40 : 32;
+    }
     // what the kernel can take
     const bool two = a.epi == S2M2_EPI_GRU || a.epi == S2M2_EPI_GATEMIX;
     const int naux = a.epi == S2M2_EPI_NONE ? 0 : two ? 2 : 1;
     if (a.stride != 1 || a.shuffle2 || a.KH > 3 || a.KW > 3 || a.KH * a.KW < 2 || a.Cout % cb || a.Cin % 8 || a.ln_wsum)
         return refuse("conv2d: K order 2 needs a stride-1 3x3 / 3x1 / 1x3 layer with Cout a multiple of %d (Cout=%d)", cb, a.Cout);
+    if (pw != 32 && naux == 2) return refuse("conv2d: K order 2 with 160-pixel blocks takes one-operand epilogues only (epi=%d has two)", a.epi);
     if (a.epi == S2M2_EPI_DUALMIX || (ph == 4 && two))
         return refuse("conv2d: K order 2 with 128-pixel blocks takes one-operand epilogues only (epi=%d has two)", a.epi);
-    if (pw != 32 && naux == 2) return refuse("conv2d: K order 2 with 160-pixel blocks takes one-operand epilogues only (epi=%d has two)", a.epi);
     return pick(ConvFamily::frag, cb, cb, ph, pw, naux);
 }
 

@@ -34,7 +34,9 @@ Reference        F.conv2d in float64, stride, padding (KH // 2, KW // 2), on the
                    activation        times its Lipschitz constant (1, 1, 1.13 for GELU) plus its own error: 0, 0, and for GELU the absolute
                                      figures of csrc/epilogue.h -- 3.3e-7 (fast_gelu, fp32) / 8.1e-7 (fast_gelu16) -- and for the fp16 GELU
                                      one fp16 ulp of the result (tests/test_gelu16_cpu.py: within one ulp of the correctly rounded value);
-                                     the figures hold on [-8, 8], and build() asserts the pre-activations stay inside
+                                     the figures hold on [-8, 8], and build() asserts the pre-activations stay inside;
+                                     SIGMOID and TANH (the patch-kernel cases of tests/k5_patch_cases.py): Lipschitz constants 1 / 4 and 1,
+                                     own error act_abs(), derived in its docstring from epilogue.h's two formulas (about 4 u and 9 u at most)
                    out_scale         times out_scale
                    staging           half an ulp of the I/O dtype at the value: the kernel stages act(.) * scale in the I/O dtype
                    epilogue          v the staged value with error e, a0 / a1 the operands, the arithmetic in fp32 (3 u per term at most):
@@ -65,13 +67,14 @@ from s2m2_amd import pack
 TDT = {"float32": torch.float32, "float16": torch.float16}
 SHORT = {"float32": "fp32", "float16": "fp16"}
 U24 = 2.0 ** -24
-ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2                                  # s2m2_amd.hip.ACT_*
+ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3, 4     # s2m2_amd.hip.ACT_*
 EPI_NONE, EPI_ADD, EPI_MUL, EPI_GRU, EPI_GATEMIX = 0, 1, 2, 3, 4        # s2m2_amd.hip.EPI_*
-ACT_NAME = {ACT_NONE: "none", ACT_GELU: "gelu", ACT_RELU: "relu"}
+ACT_NAME = {ACT_NONE: "none", ACT_GELU: "gelu", ACT_RELU: "relu", ACT_SIGMOID: "sigmoid", ACT_TANH: "tanh"}
 EPI_NAME = {EPI_NONE: "", EPI_ADD: "add", EPI_MUL: "mul", EPI_GRU: "gru", EPI_GATEMIX: "gatemix"}
-LIPSCHITZ = {ACT_NONE: 1.0, ACT_RELU: 1.0, ACT_GELU: 1.13}
+LIPSCHITZ = {ACT_NONE: 1.0, ACT_RELU: 1.0, ACT_GELU: 1.13, ACT_SIGMOID: 0.25, ACT_TANH: 1.0}
 GELU_ABS = {"float32": 3.3e-7, "float16": 8.1e-7}                       # csrc/epilogue.h
 GELU_RANGE = 8.0
+EXP_RANGE = 8.0                                                         # |pre-activation| of a SIGMOID / TANH case: act_abs() is derived for it
 EXACT_MAX = 2048                                                        # integers up to here are fp16 values
 PAD = 8                                                                 # channels of NaN on either side of a source inside its buffer
 TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 20, 21, 22, 27)   # 0 and every id conv_select.h maps to igemm / igemm2
@@ -96,7 +99,7 @@ LAYERS = {
 SHAPES = ((1, 1, 1), (1, 2, 2), (1, 1, 9), (1, 9, 1), (1, 2, 5), (1, 9, 13), (1, 8, 12), (1, 9, 12), (3, 11, 15), (2, 16, 16), (1, 33, 61))
 T20_ABOVE, T20_BELOW = (2, 256, 304), (2, 256, 296)                    # 3x3s2_32_128: 304 and 296 tiles of 128 x 128 (t20_min = 300)
 
-Spec = collections.namedtuple("Spec", "layer shape regime act scale epi tiles")
+Spec = collections.namedtuple("Spec", "layer shape regime act scale epi tiles epi_cout0", defaults=(0,))
 
 
 def _specs():
@@ -174,8 +177,11 @@ def korder1_ok(case):
 @functools.lru_cache(maxsize=None)
 def build(name, dtype="float16"):
     """built once per process and shared; nothing may write into it"""
-    spec = SPECS[name]
-    L = LAYERS[spec.layer]
+    return build_case(name, SPECS[name], LAYERS[SPECS[name].layer], dtype)
+
+
+def build_case(name, spec, L, dtype):
+    """the operands of one (spec, layer), seeded by the name (tests/k5_patch_cases.py builds its own specs with it)"""
     N, H, W = spec.shape
     Ho, Wo = out_size(H, W, L.stride)
     Cin, K = sum(L.cs), L.KH * L.KW * sum(L.cs)
@@ -196,10 +202,11 @@ def build(name, dtype="float16"):
         xs = [rnd(torch.randn(N, H, W, c, generator=g) + 0.3) for c in L.cs]
         w = rnd(torch.randn(L.Cout, Cin, L.KH, L.KW, generator=g) / math.sqrt(K))
         b = torch.randn(L.Cout, generator=g) * 0.1
+        assert spec.epi_cout0 == 0 or (spec.epi in (EPI_ADD, EPI_MUL) and 0 < spec.epi_cout0 < L.Cout)
         if spec.epi in (EPI_ADD, EPI_GATEMIX):
-            a0 = rnd(torch.randn(N, Ho, Wo, L.Cout, generator=g))
+            a0 = rnd(torch.randn(N, Ho, Wo, L.Cout - spec.epi_cout0, generator=g))
         elif spec.epi in (EPI_MUL, EPI_GRU):
-            a0 = rnd(torch.rand(N, Ho, Wo, L.Cout, generator=g))        # a gate
+            a0 = rnd(torch.rand(N, Ho, Wo, L.Cout - spec.epi_cout0, generator=g))   # a gate
         if spec.epi in (EPI_GRU, EPI_GATEMIX):
             a1 = rnd(torch.randn(N, Ho, Wo, L.Cout, generator=g))
     for t in xs + [w]:
@@ -208,15 +215,34 @@ def build(name, dtype="float16"):
     if spec.regime == "exact":
         S = _conv64([x.abs() for x in xs], w.abs(), L) + b.abs().double()
         assert float(S.max()) <= EXACT_MAX, (name, float(S.max()))
+    elif spec.act in (ACT_SIGMOID, ACT_TANH):                           # the range act_abs() is derived for
+        top = float((_conv64(xs, w, L) + b.double()).abs().max())
+        assert top <= EXP_RANGE, (name, top)
     return c
+
+
+def widen(x, poison=float("nan")):
+    """an (N, H, W, c) tensor as the GPU tests lay it out: (N + 2, H, W, c + 2 PAD) with the values at [1 : 1 + N, :, :, PAD : PAD + c], `poison` elsewhere"""
+    N, H, W, c = x.shape
+    big = torch.full((N + 2, H, W, c + 2 * PAD), poison)
+    big[1:1 + N, :, :, PAD:PAD + c] = x
+    return big
+
+
+def in_nan(t):
+    """a device tensor t (N, H, W, c) as images 1 .. N of an (N + 2)-image buffer and the middle third of a tensor three times as wide, NaN
+    everywhere else -> (buffer, view); the fused kernels' tests (K14, K17, K19) lay their inputs out like this"""
+    N, H, W, c = t.shape
+    big = torch.full((N + 2, H, W, 3 * c), float("nan"), device=t.device, dtype=t.dtype)
+    view = big[1:1 + N, :, :, c:2 * c]
+    view.copy_(t)
+    assert view.stride(2) == 3 * c and not view.is_contiguous() and bool(torch.isnan(big[0]).all()) and bool(torch.isnan(big[-1]).all())
+    return big, view
 
 
 def wide(case, i, poison=float("nan")):
     """source i as the GPU test lays it out: (N + 2, H, W, c + 2 PAD) with the values at [1 : 1 + N, :, :, PAD : PAD + c] and `poison` elsewhere"""
-    x = case.xs[i]
-    big = torch.full((case.N + 2, case.H, case.W, x.shape[-1] + 2 * PAD), poison)
-    big[1:1 + case.N, :, :, PAD:PAD + x.shape[-1]] = x
-    return big
+    return widen(case.xs[i], poison)
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------
@@ -229,16 +255,56 @@ def _conv64(xs, w, L):
 
 
 def activate(pre, act):
+    if act == ACT_SIGMOID:
+        return torch.sigmoid(pre)
+    if act == ACT_TANH:
+        return torch.tanh(pre)
     return F.gelu(pre) if act == ACT_GELU else pre.clamp(min=0) if act == ACT_RELU else pre
+
+
+def act_abs(x, act):
+    """The absolute error of the device's own SIGMOID / TANH at the fp32 pre-activation x (float64 tensor), before any rounding to the I/O
+    dtype, derived from the two formulas of csrc/epilogue.h; first order in u = 2^-24, |x| <= EXP_RANGE (build_case() asserts it).
+
+    What rounds.  A correctly rounded fp32 operation has relative error u.  v_exp_f32 and v_rcp_f32 are within one ulp of the true value
+    (epilogue.h), so each returns the correctly rounded value or one of its two neighbours: at most 1.5 ulp = 3 u relative from the true
+    value (an ulp is at most 2 u relative).  L = fl(log2 e) is within u of log2 e.
+
+    SIGMOID  rcp(1 + exp2(fl(-x L))).  fl(-x L) = -x log2 e (1 + d), |d| <= 2 u (the constant and the product), an absolute error of
+             2 u |x| log2 e in the exponent, which exp2 turns into a relative error 2 u |x| ln 2 log2 e = 2 u |x| of E = e^-x; with exp2's own
+             3 u:  E (1 + (3 + 2 |x|) u).  s = sigmoid(x) = 1 / (1 + E) moves by E / (1 + E)^2 = s (1 - s) per unit of relative error of E:
+             s (1 - s) (3 + 2 |x|) u.  The add 1 + E rounds (u) and rcp adds 3 u, both relative to s:  4 u s.
+               error <= u [ s (1 - s) (3 + 2 |x|) + 4 s ]                        (at most 4.2 u on [-8, 8]; below (4 + |x|) u everywhere)
+    TANH     1 - 2 rcp(1 + exp2(fl(2 x L))), 2 x exact.  E = e^2x (1 + (3 + 4 |x|) u) by the same steps.  q = 2 / (1 + E) = 1 - t, t = tanh(x),
+             moves by 2 E / (1 + E)^2 = (1 - t^2) / 2 per unit of relative error of E; the add and rcp give 4 u q; 2 rcp is exact and the last
+             subtraction rounds the result (u |t|).
+               error <= u [ (1 - t^2) / 2 (3 + 4 |x|) + 4 (1 - t) + |t| ]        (9 u at x = -8, 5.5 u at 0, u at +8; below (8 + 4 |x|) u)
+    The second-order terms are below (20 u)^2 < 2e-5 u on the range; 0.01 u is added for them.  tests/test_k5_patch_cases_cpu.py holds both
+    figures against a float32 restatement in which exp2 and the reciprocal are each moved by -1, 0 and +1 ulp."""
+    ax = x.abs()
+    if act == ACT_SIGMOID:
+        s = torch.sigmoid(x)
+        return U24 * (s * (1 - s) * (3 + 2 * ax) + 4 * s + 0.01)
+    if act == ACT_TANH:
+        t = torch.tanh(x)
+        return U24 * ((1 - t * t) / 2 * (3 + 4 * ax) + 4 * (1 - t) + t.abs() + 0.01)
+    raise KeyError(act)
 
 
 GATE_LO, GATE_HI = float(np.float32(0.01)), float(np.float32(0.99))      # the kernel's clamp constants are fp32
 
 
 def finish(case, pre):
-    """pre-activation (with bias) float64 -> the layer's output: activation, out_scale, epilogue"""
+    """pre-activation (with bias) float64 -> the layer's output: activation, out_scale, epilogue.  spec.epi_cout0 > 0 (two stacked layers in
+    one launch): output channels below it get bias and activation only, those from it on the epilogue, whose operand has Cout - epi_cout0 channels"""
+    c0 = case.spec.epi_cout0
+    if c0:
+        return torch.cat([_finish(case, pre[..., :c0], EPI_NONE), _finish(case, pre[..., c0:], case.spec.epi)], -1)
+    return _finish(case, pre, case.spec.epi)
+
+
+def _finish(case, pre, e):
     v = activate(pre, case.spec.act) * case.spec.scale
-    e = case.spec.epi
     if e == EPI_NONE:
         return v
     a0 = case.a0.double()
@@ -263,7 +329,15 @@ def ulp(v, dtype):
 
 
 def bound(case, pre, S):
-    """the elementwise bound of the docstring; pre, S float64 (N, Ho, Wo, Cout)"""
+    """the elementwise bound of the docstring; pre, S float64 (N, Ho, Wo, Cout).  SIGMOID and TANH: Lipschitz constants 1 / 4 and 1, their own
+    error act_abs() (derived there).  spec.epi_cout0: the channels below it are bounded as a layer without epilogue."""
+    c0 = case.spec.epi_cout0
+    if c0:
+        return torch.cat([_bound(case, pre[..., :c0], S[..., :c0], EPI_NONE), _bound(case, pre[..., c0:], S[..., c0:], case.spec.epi)], -1)
+    return _bound(case, pre, S, case.spec.epi)
+
+
+def _bound(case, pre, S, epi):
     spec, dt = case.spec, case.dtype
     half = lambda value, err: 0.5 * ulp(value.abs() + err, dt)
     act = activate(pre, spec.act)
@@ -272,20 +346,22 @@ def bound(case, pre, S):
         e = e + GELU_ABS[dt]
         if dt == "float16":
             e = e + ulp(act.abs() + e, dt)
+    elif spec.act in (ACT_SIGMOID, ACT_TANH):
+        e = e + act_abs(pre, spec.act)
     e = e * spec.scale
     v = act * spec.scale
     e = e + half(v, e)
-    if spec.epi == EPI_NONE:
+    if epi == EPI_NONE:
         return e
-    o = finish(case, pre)
+    o = _finish(case, pre, epi)
     a0 = case.a0.double().abs()
-    if spec.epi == EPI_ADD:
+    if epi == EPI_ADD:
         e = e + U24 * (o.abs() + e)
-    elif spec.epi == EPI_MUL:
+    elif epi == EPI_MUL:
         e = a0 * e + U24 * (o.abs() + a0 * e)
     else:
         a1 = case.a1.double().abs()
-        if spec.epi == EPI_GRU:
+        if epi == EPI_GRU:
             terms = (1 - case.a0.double()).abs() * a1 + a0 * (v.abs() + e)
             e = a0 * e + 3 * U24 * terms
         else:
@@ -300,7 +376,11 @@ Ref = collections.namedtuple("Ref", "out bound pre")                    # bound 
 @functools.lru_cache(maxsize=None)
 def reference(name, dtype="float16"):
     """computed once per process and shared"""
-    c = build(name, dtype)
+    return reference_case(build(name, dtype))
+
+
+def reference_case(c):
+    name, dtype = c.name, c.dtype
     pre = _conv64(c.xs, c.w, c.layer) + c.b.double()
     out = finish(c, pre) + 0.0                                          # (-0.0 -> +0.0)
     assert out.dtype == torch.float64 and tuple(out.shape) == (c.N, c.Ho, c.Wo, c.layer.Cout)

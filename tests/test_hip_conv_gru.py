@@ -1,12 +1,14 @@
 """GPU parity of K17 (s2m2_conv_gru: one ConvGRU half, reference refinenet.py:7-36, in one launch) against the two launches it replaces -- K5 v5 on
 the stacked z | r layer with the r * h epilogue, K5 v5 on the candidate layer with the blend epilogue -- BIT FOR BIT on the same packed weights
-(same accumulation order, same rounding points; the kernel only keeps z and r * h on the CU)."""
+(same accumulation order, same rounding points; the kernel only keeps z and r * h on the CU).
+The K5 v5 kernel these bit-equalities rest on is itself held to a float64 reference on every patch form by tests/test_hip_k5_patch.py."""
 import ctypes
 import math
 
 import pytest
 import torch
 
+from k5_cases import in_nan
 from s2m2_amd import pack
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +84,22 @@ def test_conv_gru_on_a_channel_slice_and_without_biases(hip, taps):
     both = hip.conv2d([hc, x], w_zr, None, kh, kw, 2 * C, act=hip.ACT_SIGMOID, epi=hip.EPI_MUL, aux0=hc, korder=2, epi_cout0=C)
     ref = hip.conv2d([both[..., C:], x], w_q, None, kh, kw, C, act=hip.ACT_TANH, epi=hip.EPI_GRU, aux0=both[..., :C], aux1=hc, korder=2, tile=2)
     assert torch.equal(got, ref), float((got.float() - ref.float()).abs().max())
+
+
+@pytest.mark.parametrize("taps", [(3, 1), (1, 3)], ids=["3x1", "1x3"])
+def test_conv_gru_reads_nothing_around_its_inputs(hip, taps):
+    """h and x surrounded by NaN on every side, three images (the middle one has a neighbour above and below): a ring row fetched above the
+    first or below the last image, or a channel piece beside a slice, makes the output NaN"""
+    kh, kw = taps
+    hc, xc = _inputs(3, 9, 44, 33)
+    (hbig, h), (xbig, x) = in_nan(hc), in_nan(xc)
+    ref = _pair(hip, hc, xc, kh, kw)
+    w_zr, b_zr, w_q, b_q = _layers(kh, kw)
+    got = hip.conv_gru(h, x, w_zr, b_zr, w_q, b_q, kh, kw)
+    assert torch.isfinite(got).all()
+    assert torch.equal(got, ref), float((got.float() - ref.float()).abs().max())
+    assert torch.equal(h, hc) and torch.equal(x, xc)
+    assert int(torch.isnan(hbig).sum()) == hbig.numel() - h.numel() and int(torch.isnan(xbig).sum()) == xbig.numel() - x.numel()
 
 
 def test_conv_gru_replays_from_a_plan(hip):

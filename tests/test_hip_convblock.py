@@ -1,12 +1,14 @@
 """GPU parity of K14 (s2m2_conv_block: a whole ConvBlock2D, reference attentions.py:255-281, in one launch) against the three launches it
 replaces -- K9 two-stage chain (1x1 branch), K5 v5 (3x3 + GELU), K5 v5 with the residual epilogue -- BIT FOR BIT (same arithmetic in the same
-order; the kernel only keeps the intermediates on the CU), and against a plain PyTorch fp32 restatement with fp16 rounding points."""
+order; the kernel only keeps the intermediates on the CU), and against a plain PyTorch fp32 restatement with fp16 rounding points.
+The K5 v5 kernel these bit-equalities rest on is itself held to a float64 reference on every patch form by tests/test_hip_k5_patch.py."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from k5_cases import in_nan
 from s2m2_amd import pack
 
 pytestmark = pytest.mark.gpu
@@ -85,6 +87,23 @@ def test_conv_block_on_a_channel_slice_and_replayed_from_a_plan(hip, ph):
     y.zero_()
     plan.run([x])
     assert torch.equal(y, got)
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 33, 128), (3, 5, 7, 256)], ids=["n3-5x33-C128", "n3-5x7-C256"])
+def test_conv_block_reads_nothing_around_its_input(hip, shape):
+    """x as images 1 .. 3 of a five-image buffer and the middle third of a tensor three times as wide, NaN everywhere else: a halo row fetched
+    above the first or below the last image, or a channel piece beside the slice, makes the output NaN.  The middle image has a neighbour on
+    both sides."""
+    N, H, W, C = shape
+    k0, k2, p0, p2, bs = _layers(C, H + W)
+    big, x = in_nan((torch.randn(N, H, W, C, device="cuda", generator=torch.Generator(device="cuda").manual_seed(C + W)) * 1.3 + 0.2).half())
+    kept = x.clone()
+    ref, (w0, w2, a0, a2) = _triple(hip, x.contiguous(), k0, k2, p0, p2, bs)
+    for ph in ((0, 2, 4) if C == 128 else (0,)):                        # (C = 256 has one patch form)
+        got = hip.conv_block(x, w0, bs[0], w2, bs[1], a0, bs[2], a2, bs[3], patch_rows=ph)
+        assert torch.isfinite(got).all(), ph
+        assert torch.equal(got, ref), (ph, float((got.float() - ref.float()).abs().max()))
+    assert torch.equal(x, kept) and int(torch.isnan(big).sum()) == big.numel() - x.numel()
 
 
 def test_conv_block_vs_torch(hip):

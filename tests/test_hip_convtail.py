@@ -1,13 +1,15 @@
 """GPU parity of K19 (s2m2_conv_block_tail: the second half of a ConvBlock2D, reference attentions.py:255-281, in one launch) against the two
 launches it replaces -- the K9 two-stage chain on the 1x1 branch, K5 v5 on convs.2 with the residual epilogue -- BIT FOR BIT on the same packed
 weights (same accumulation order, same rounding points; the kernel only keeps the 1x1 branch's output on the CU), and the whole forward with the
-path switched on and off."""
+path switched on and off.
+The K5 v5 kernel these bit-equalities rest on is itself held to a float64 reference on every patch form by tests/test_hip_k5_patch.py."""
 import ctypes
 import math
 
 import pytest
 import torch
 
+from k5_cases import in_nan
 from s2m2_amd import pack
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +95,27 @@ def test_conv_block_tail_on_channel_slices_into_a_strided_output_without_biases(
     got = _tail(hip, t, z, bias=False, out=out)
     assert got.data_ptr() == out.data_ptr() and torch.equal(out, ref), float((out.float() - ref.float()).abs().max())
     assert bool((buf[..., :8] == 7.0).all()) and bool((buf[..., 8 + C:] == 7.0).all())          # nothing written beside the view
+
+
+@pytest.mark.parametrize("C,patch", [(128, (2, 32)), (128, (4, 32)), (128, (4, 40)), (256, None)],
+                         ids=["C128-p2x32", "C128-p4x32", "C128-p4x40", "C256-auto"])
+def test_conv_block_tail_reads_and_writes_nothing_around_its_operands(hip, C, patch):
+    """t and z surrounded by NaN on every side, three images (the middle one has a neighbour above and below), the output a channel slice of a
+    tensor of sentinels with a guard image behind it: a halo row fetched above the first or below the last image, or a channel piece beside a
+    slice, makes the output NaN; a store beside the slice or behind the last image loses a sentinel"""
+    N, H, W = 3, 5, 41
+    tc, zc = _inputs(N, H, W, C, 77 + C)
+    (tbig, t), (zbig, z) = in_nan(tc), in_nan(zc)
+    ref = _pair(hip, tc, zc)
+    sentinel = torch.tensor(-777.0, device="cuda", dtype=F16)
+    buf = torch.full((N + 1, H, W, C + 16), -777.0, device="cuda", dtype=F16)
+    out = buf[:N, :, :, 8:8 + C]
+    got = _tail(hip, t, z, out=out, patch=patch)
+    assert got.data_ptr() == out.data_ptr() and torch.isfinite(out).all()
+    assert torch.equal(out, ref), float((out.float() - ref.float()).abs().max())
+    assert bool((buf[:N, :, :, :8] == sentinel).all()) and bool((buf[:N, :, :, 8 + C:] == sentinel).all()) and bool((buf[N] == sentinel).all())
+    assert torch.equal(t, tc) and torch.equal(z, zc)
+    assert int(torch.isnan(tbig).sum()) == tbig.numel() - t.numel() and int(torch.isnan(zbig).sum()) == zbig.numel() - z.numel()
 
 
 def test_conv_block_tail_replays_from_a_plan(hip):

@@ -57,6 +57,14 @@ conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=14 fp16=1 -> E:conv2d: the pointwise kernel needs a 1x1 stride-1 layer
 conv N=1 H=256 W=304 Cin=512 Cout=128 KH=1 KW=1 stride=1 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=14 fp16=0 -> E:conv2d: pointwise kernel: Cin=512 needs 316416 bytes of LDS
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=3 korder=2 pool2=0 ln=0 shuffle2=0 tile=4 fp16=1 -> E:conv2d: K order 2 with 128-pixel blocks takes one-operand epilogues only (epi=3 has two)
+conv N=1 H=4 W=40 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=2 pool2=0 ln=0 shuffle2=0 tile=40 fp16=1 -> frag 128 128 4 40 0
+conv N=3 H=9 W=70 Cin=192 Cout=576 KH=3 KW=3 stride=1 epi=0 korder=2 pool2=0 ln=0 shuffle2=0 tile=40 fp16=1 -> frag 192 192 4 40 0
+conv N=1 H=5 W=41 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=2 korder=2 pool2=0 ln=0 shuffle2=0 tile=40 fp16=1 -> frag 128 128 4 40 1
+conv N=1 H=5 W=41 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=2 pool2=0 ln=0 shuffle2=0 tile=4 fp16=1 -> frag 128 128 4 32 0
+conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=2 pool2=0 ln=0 shuffle2=0 tile=2 fp16=1 -> frag 128 128 2 32 0
+conv N=1 H=5 W=41 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=2 pool2=0 ln=0 shuffle2=0 tile=0 fp16=1 -> frag 128 128 2 32 0
+conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=3 korder=2 pool2=0 ln=0 shuffle2=0 tile=40 fp16=1 -> E:conv2d: K order 2 with 160-pixel blocks takes one-operand epilogues only (epi=3 has two)
+conv N=1 H=256 W=304 Cin=128 Cout=128 KH=1 KW=3 stride=1 epi=4 korder=2 pool2=0 ln=0 shuffle2=0 tile=40 fp16=1 -> E:conv2d: K order 2 with 160-pixel blocks takes one-operand epilogues only (epi=4 has two)
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=1 KW=1 stride=1 epi=0 korder=0 pool2=0 ln=1 shuffle2=0 tile=7 fp16=1 -> E:conv2d: tile 7 has no pre-LayerNorm variant (2, 3, 6, 20 do)
 conv N=1 H=256 W=304 Cin=128 Cout=128 KH=3 KW=3 stride=1 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=28 fp16=1 -> E:conv2d: unknown tile id 28
 conv N=1 H=33 W=61 Cin=128 Cout=128 KH=3 KW=3 stride=2 epi=0 korder=0 pool2=0 ln=0 shuffle2=0 tile=0 fp16=1 -> igemm 64 64 2 8 1 4 0
