@@ -17,6 +17,18 @@
 //   * residuals: `res` (global rows) is added to the output of stage res_stage with coalesced loads issued before the stage's
 //     K loop; `carry` adds the output of stage 0 (still in the other LDS buffer) to the last stage of a 3-stage chain.
 // Every intermediate is rounded to the I/O dtype exactly where the separate launches round it (tile in LDS instead of HBM).
+//
+// Rounding points (T = the I/O dtype; everything between two of them is fp32; tests/k9_cases.py emulate() rounds at exactly these):
+//   R1  pooled tile load: T((a + b + c + d) * 0.25f), the four pixels summed in that order in fp32;
+//   R2  every stage tile: T(act(acc + b)), or with the fold T(act(rstd * (acc - mean * wsum) + b)) -- two fmas; acc is the MFMA's fp32 chain;
+//       statistics of the fold, per row, from the stage's INPUT tile (T values): fp16 -- s = sum x, q = sum x^2 as one fp32 chain per half-wave
+//       (lane half hi owns channels 16 f + 8 hi .. + 7 of every k16 step f, ascending, two channels per v_dot2 step), the halves added,
+//       mean = s / C, var = max(fma(-mean, mean, q / C), 0); fp32 -- the same sums of x - x[0], mean = s / C + x[0]; rstd = rsq(var + ln_eps);
+//   R3  residual on a stage that is not the last: T(tile + res);
+//   R4  last stage's store pass: T(tile + y_0) if carry, then T(. + res) if res_stage is the last stage, in that order; these are the `out` rows;
+//   R5  ln_out: T(fma((out - mean) * rstd, gamma, beta)) with two-pass fp32 statistics of the stored (R4) rows, biased variance;
+//   R6  every fan-out tile: as R2 without activation, on the stored (R4) rows -- or on the x / pooled rows when nstage = 0 -- with the
+//       statistics taken once, during the first fan-out layer, and reused by the others.
 #include "common.h"
 #include "chain_select.h"
 #include "launch.h"
@@ -649,6 +661,8 @@ static int mlp_chain_impl(const s2m2_chain_desc* d, void* stream) {
     if (d->nstage == 0 && d->weight_frag) {
         // fan-out only, direct form: the nfan layers read the x rows, their fragments straight from global memory (any row count)
         S2M2_REQUIRE(d->nfan >= 1 && d->nfan <= 4, "mlp_chain: nfan=%d (1..4)", d->nfan);
+        S2M2_REQUIRE(d->res_stage < 0 && !d->carry && !d->ln_out && d->xcd_group_rows == 0,
+                     "mlp_chain: a fan-out-only launch (nstage = 0) has no stage to take res_stage, carry, ln_out or xcd_group_rows");
         S2M2_REQUIRE(d->rows > 0 && d->rows < (1LL << 31) && d->x_stride >= d->C && d->x_stride % 8 == 0, "mlp_chain: bad rows / x_stride");
         S2M2_REQUIRE(d->fan_weight && d->fan_out && d->fan_out_stride >= (long long)d->nfan * d->C && d->fan_out_stride % 8 == 0,
                      "mlp_chain: fan-out stages need fan_weight, fan_out and a row stride of at least nfan * C (multiple of 8)");

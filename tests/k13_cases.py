@@ -510,21 +510,25 @@ _f32 = lambda t: t.float().double()                                             
 _HALF_ORDER = torch.tensor([[16 * s + 8 * u + 4 * hi + e for s in range(8) for u in range(2) for e in range(4)] for hi in range(2)])
 
 
-def ln_stats(x, eps, clamp=True):
+def ln_stats(x, eps, clamp=True, order=None):
     """mean and rstd of the last axis as ra_ln_stats takes them: each half-wave runs over its 64 channels in fragment order, two at a time
     (v_dot2: the two products and the running sum rounded once to fp32), the halves are added, the variance is fma(-mean, mean, q / C),
-    clamped at 0.  x: float64 holding fp16 (or fp32) values."""
-    o = _HALF_ORDER.to(x.device)
-    xs = x[..., o]                                                                   # (..., 2, 64)
+    clamped at 0.  x: float64 holding fp16 (or fp32) values.  order: (2, C / 2) channel indices, the order in which each half-wave of another
+    kernel takes a row of another width (tests/k9_cases.py); the width is that of x, and 1 / C is the fp32 constant the kernels multiply by."""
+    o = (_HALF_ORDER if order is None else order).to(x.device)
+    width = x.shape[-1]
+    assert o.numel() == width, (tuple(o.shape), width)
+    inv = float(np.float32(1.0) / np.float32(width))
+    xs = x[..., o]                                                                   # (..., 2, C / 2)
     s = torch.zeros(xs.shape[:-1], dtype=torch.float64, device=x.device)
     q = torch.zeros_like(s)
-    for p in range(32):
+    for p in range(o.shape[1] // 2):
         a, b = xs[..., 2 * p], xs[..., 2 * p + 1]
         s = _f32(s + (a + b))
         q = _f32(q + (a * a + b * b))
     s, q = _f32(s.sum(-1)), _f32(q.sum(-1))
-    mean = s / C
-    var = _f32(q / C - mean * mean)
+    mean = _f32(s * inv)
+    var = _f32(_f32(q * inv) - mean * mean)
     if clamp:
         var = var.clamp(min=0.0)
     rstd = _f32(1.0 / torch.sqrt(_f32(var + float(np.float32(eps)))))
@@ -654,7 +658,8 @@ def ln_fold_bound(x, wabs_x, acc, ws, eps=EPS):
                 exact (1.5 is; HOT is not: there dvar reaches eps and this bound is void -- the full regime judges such tokens, not this one).
       product   acc is an fp32 chain of C products in any order, (C + 2) u |W| |x|; mean ws, the subtraction, the two fmas: 3 u (|acc| + |m ws|)
       together  |dy| <= rstd [ rho |acc - m ws| + (C + 2) u |W||x| + dm |ws| + 3 u (|acc| + |m ws|) ] (1 + rho) + u |y|
-    A perturbation e of the accumulator is amplified by rstd: that is the factor in front."""
+    A perturbation e of the accumulator is amplified by rstd: that is the factor in front.  C is the width of x."""
+    C = x.shape[-1]
     m = x.mean(-1, keepdim=True)
     v = x.var(-1, unbiased=False, keepdim=True)
     M2 = m * m + v
@@ -667,18 +672,20 @@ def ln_fold_bound(x, wabs_x, acc, ws, eps=EPS):
     return e + U24 * (rstd * core).abs()
 
 
-def ln_out_bound(out, E, g, b, eps=LN_OUT_EPS):
+def ln_out_bound(out, E, g, b, eps=LN_OUT_EPS, half=None):
     """Bound of ln_out (the LayerNorm of the STORED rows, two passes in fp32) against LayerNorm(out) g + b of the reference's rows, when the
     stored rows are within E of out.  n = (o - mu) / sigma: a perturbation d of the row moves n_c by (d_c - mean d) / sigma - n_c dsigma / sigma
     with |dsigma| <= rms(d), so |dn_c| <= (E_c + mean E + |n_c| rms E) / sigma, to first order (second order: the factor 1.02, E << sigma);
     the kernel's own arithmetic is two fp32 chains of C terms and five operations per element, (C + 8) u (|n_c| + 1); the affine and one
-    rounding to fp16 follow."""
+    rounding to fp16 follow (half: half an ulp of another I/O dtype, tests/k9_cases.py).  C is the width of out."""
+    C = out.shape[-1]
+    half = half16 if half is None else half
     mu = out.mean(-1, keepdim=True)
     sig = torch.sqrt(out.var(-1, unbiased=False, keepdim=True) + eps)
     n = (out - mu) / sig
     dn = 1.02 * (E + E.mean(-1, keepdim=True) + n.abs() * torch.sqrt((E * E).mean(-1, keepdim=True))) / sig + (C + 8) * U24 * (n.abs() + 1)
     e = g.abs() * dn + 2 * U24 * (n * g + b).abs()
-    return e + half16(n * g + b, e)
+    return e + half(n * g + b, e)
 
 
 def route_bound(case, device="cpu"):
