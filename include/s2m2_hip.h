@@ -1432,6 +1432,54 @@ typedef struct s2m2_tsdf_track_desc {
 size_t s2m2_tsdf_track_workspace_bytes(int B, int H, int W);   /* 0: bad extents */
 int s2m2_tsdf_track(const s2m2_tsdf_track_desc* desc, void* stream);
 
+/*
+ * K28 -- the normal map of the disparity map: per kept pixel the unit normal of the surface through its neighbours `radius` pixels away, in the
+ *   CAMERA frame, in K26's layout (depth with 0 as the hole value, three fp32 planes, a uint8 image, a count), so that the maps of one frame can
+ *   stand where K27 takes K26's model maps (with identity model poses: frame-to-frame tracking without a volume) and can fill the normals of
+ *   K15's and K20's PLY files.  No counterpart in the reference: the semantics are defined here and pinned by the numpy oracle of
+ *   tests/normals_oracle.py.  Still S2M2_ABI_VERSION 800: the entry point is added, nothing changes in place.
+ *   `cloud` holds the INPUT fields of s2m2_cloud with the meaning they have in s2m2_tsdf_track_desc: the B padded maps, H, W, Hp, Wp (fused
+ *   crop), camera and filter parameters, unfiltered.  Its outputs are IGNORED and the image is not needed.
+ *   All in fp32, every operation ONE IEEE rounding, nothing fused into a multiply-add; division and sqrtf are correctly rounded.
+ *   gate = (float)max_jump * (float)radius is formed once on the host as fp32; min_cos is converted to fp32 once on the host.
+ *   Per pair b and pixel c = (v, u) of the UNPADDED image:
+ *     point       z, keep = K15's (the same device functions), d = the map's disparity;   x = ((float)u - cx) * z / fx;   y = ((float)v - cy) * z / fy;
+ *                 P = (x, y, z).  A pixel that is not kept is a hole.
+ *     neighbours  horizontal: plus = (v, u + radius), minus = (v, u - radius);   vertical: plus = (v + radius, u), minus = (v - radius, u).
+ *                 A neighbour q is USABLE iff it lies inside the H x W image, keep(q), and fabsf(d_q - d_c) <= gate (one exact subtraction; a NaN
+ *                 fails).  Padded map pixels outside the crop are outside the image, whatever memory holds there.
+ *     differences per pair: a = usable(plus) ? P_plus : P_c;   b = usable(minus) ? P_minus : P_c;   the pixel is a hole unless at least one of the
+ *                 two is usable;   difference = a - b per component (central, forward or backward).  This gives dx (horizontal), dy (vertical).
+ *     normal      n = dy x dx:   nx = dy.y*dx.z - dy.z*dx.y;   ny = dy.z*dx.x - dy.x*dx.z;   nz = dy.x*dx.y - dy.y*dx.x   (two products and one
+ *                 subtraction each);   s = (nx*nx + ny*ny) + nz*nz;   a hole unless s > 0 and s is finite;   q = sqrtf(s);   n = (nx/q, ny/q, nz/q).
+ *                 With x right, y down, z forward this points TOWARDS the camera: the side K24's and K26's gradients point to.
+ *     view gate   m = sqrtf((x*x + y*y) + z*z);   cosv = -(((nx*x + ny*y) + nz*z) / m);   a hole unless cosv >= min_cos (a NaN fails).
+ *   outputs, each optional (NULL), at least one; every pixel of every requested output is written:
+ *     depth    (B,1,H,W) fp32: keep ? z : 0 -- K15's bytes, whether or not the pixel has a normal
+ *     normals  (B,3,H,W) fp32: n, 0,0,0 at a hole
+ *     image    (B,3,H,W) uint8: per channel (int)rintf(n_a * 127.5f + 127.5f) (one product, one sum, half to even), 0,0,0 at a hole
+ *     count    (B) int32 pixels that have a normal: cleared on the stream by the entry point, then one atomic integer add per block.  The sum
+ *              does not depend on the order, so the stage stays bit-reproducible.
+ *   One launch plus the clear of count, no workspace, no host step.
+ *   Errors (before any device call): null descriptor; everything s2m2_tsdf_track checks of its maps and camera; no output requested; depth,
+ *   normals or count not 4-byte aligned; radius outside 1 .. 8; max_jump negative or NaN (+inf is allowed: it joins everything); min_cos not
+ *   finite or >= 1.
+ *   Non-finite maps never form an address: every index comes from integers.
+ *   Launch plans: s2m2_normals is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing.
+ *   Safe under stream capture (hipGraph).
+ */
+typedef struct s2m2_normals_desc {
+    s2m2_cloud_desc cloud;   /* the maps: K27's meaning; outputs ignored, image not needed */
+    float*   depth;          /* (B,1,H,W) fp32: K15's depth (z where keep, else 0); optional */
+    float*   normals;        /* (B,3,H,W) fp32: unit normal in the CAMERA frame, towards the camera; 0,0,0 at holes; optional */
+    uint8_t* image;          /* (B,3,H,W) uint8: the normal as a colour; 0,0,0 at holes; optional */
+    int32_t* count;          /* (B) pixels that have a normal; optional */
+    int      radius;         /* 1 .. 8: the neighbours lie `radius` pixels away */
+    double   max_jump;       /* px of disparity per pixel of distance, >= 0, +inf allowed (K20's gate) */
+    double   min_cos;        /* finite, < 1: smallest cosine between the normal and the direction to the camera */
+} s2m2_normals_desc;
+int s2m2_normals(const s2m2_normals_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,12 @@
 //   pair each, named as --ply names its files (OUT.<b>.f32, OUT.<b>.i32, OUT.<b>.ppm).  With --repeat: {"register_covered", "repeat", "register_us_per_pair"} on a line
 //   of its own.
 //
+// --normals OUT.f32 [--normals-image OUT.ppm] [--normals-radius R] [--normals-min-cos X]: the normal map of the disparity map (s2m2_normals),
+//   behind --calib: raw float32 (3,H,W) unit normals in the camera frame, towards the camera, 0,0,0 = no normal; --normals-image: the normals as
+//   colours in a binary PPM (P6), as --register-image writes one.  The neighbours lie R pixels away (1..8, default 1) and are used where their
+//   disparity differs by at most R times --max-jump (default 1) px; a normal is kept where its cosine with the direction to the camera is at
+//   least X (default 0).  Honours --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered, comes behind --min-size exactly as --ply
+//   does, and names its files like --ply for B > 1.  With --repeat: {"normals_count", "repeat", "normals_us_per_pair"} on a line of its own.
 // --min-size N [--max-jump X] [--labels OUT.i32] [--segment-mask OUT.u8]: the speckle filter (s2m2_segment) behind the forward and in front of
 //   every 3D output above: the 4-connected components of the kept pixels whose neighbouring disparities differ by at most X px (the --max-jump
 //   of --mesh, default 1), and the disparity map without the components of fewer than N pixels (N >= 1; 1 removes nothing).  Needs --calib;
@@ -382,6 +388,44 @@ static int stage_register(Context& c) {
     return 0;
 }
 
+// --normals (K28): the normal map of the run's own maps, and the normals as colours
+static int stage_normals(Context& c) {
+    const Options& o = c.o;
+    const s2m2_engine_info& m = c.m;
+    const size_t npix = (size_t)m.H * m.W;
+    DeviceBuffer dn, dcount, dc;
+    if (DeviceBuffer::make(dn, (size_t)m.B * 3 * npix * sizeof(float)) || DeviceBuffer::make(dcount, m.B * sizeof(int32_t))) return 1;
+    if (o.normals_image_path && DeviceBuffer::make(dc, (size_t)m.B * 3 * npix)) return 1;
+    s2m2_normals_desc nd;
+    memset(&nd, 0, sizeof nd);
+    fill_cloud_inputs(nd.cloud, m, c.disp3d, c.maps[1], c.maps[2], nullptr, 2, c.unfiltered3d, c.cal, o);
+    nd.normals = dn.as<float>(); nd.image = dc.as<unsigned char>(); nd.count = dcount.as<int32_t>();
+    nd.radius = o.normals_radius; nd.max_jump = o.max_jump; nd.min_cos = o.normals_min_cos;
+    const auto run = [&] { return s2m2_normals(&nd, c.s) == 0 ? 0 : fail_lib("s2m2_normals failed"); };
+    if (run()) return 1;
+    HIP_OK(hipStreamSynchronize(c.s), "s2m2_normals");
+    std::vector<int32_t> hcount(m.B);
+    HIP_OK(hipMemcpy(hcount.data(), dcount.h, m.B * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+    if (download_and_write(dn.h, (size_t)m.B * 3 * npix * sizeof(float), o.normals_path, "cannot write the normal map", m.B, ".f32")) return 1;
+    if (o.normals_image_path) {
+        std::vector<unsigned char> planar((size_t)m.B * 3 * npix), rgb(3 * npix);
+        HIP_OK(hipMemcpy(planar.data(), dc.h, planar.size(), hipMemcpyDeviceToHost), "download");
+        char head[64];
+        snprintf(head, sizeof head, "P6\n%d %d\n255\n", m.W, m.H);
+        for (int b = 0; b < m.B; ++b) {
+            for (size_t i = 0; i < npix; ++i)
+                for (int ch = 0; ch < 3; ++ch) rgb[3 * i + ch] = planar[((size_t)b * 3 + ch) * npix + i];
+            if (!write_bytes(pair_path(o.normals_image_path, m.B, b, ".ppm"), head, rgb.data(), rgb.size())) return fail("cannot write the normal image");
+        }
+    }
+    if (o.repeat > 0) {
+        float ms = 0.f;
+        if (time_calls(c.s, o.repeat, run, &ms, "timed normals runs")) return 1;
+        printf("{\"normals_count\": %d, \"repeat\": %d, \"normals_us_per_pair\": %.2f}\n", hcount[0], o.repeat, 1000.f * ms / o.repeat / m.B);
+    }
+    return 0;
+}
+
 // --gt (K18): the stat words of every pair and the numbers derived from them, as JSON
 static int stage_eval(Context& c, const GroundTruth& g) {
     const Options& o = c.o;
@@ -701,7 +745,7 @@ int main(int argc, char** argv) {
         printf("{\"B\": %d, \"H\": %d, \"W\": %d, \"repeat\": %d, \"ms_per_pair\": %.4f}\n", m.B, m.H, m.W, o.repeat, ms / o.repeat / m.B);
     }
     const bool cloud = o.calib_path && (o.ply_path || o.mesh_path);
-    if (o.min_size_arg || cloud || o.register_cam || o.voxel_arg) {                 // the calibration: once, in front of the first 3D stage
+    if (o.min_size_arg || cloud || o.register_cam || o.voxel_arg || o.normals_path) {              // the calibration: once, in front of the first 3D stage
         if (!read_calib(o.calib_path, c.cal)) return fail("--calib: cannot read cam0 and baseline from the file");
         if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
     }
@@ -709,6 +753,7 @@ int main(int argc, char** argv) {
     if (cloud && stage_cloud(c)) return 1;
     if (o.voxel_arg && stage_voxel(c)) return 1;
     if (o.register_cam && stage_register(c)) return 1;
+    if (o.normals_path && stage_normals(c)) return 1;
     if (o.gt_path && stage_eval(c, g)) return 1;
     return 0;
 }

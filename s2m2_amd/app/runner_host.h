@@ -17,7 +17,8 @@ inline const char* const USAGE =
     "usage: s2m2_run_engine ENGINE LEFT RIGHT [--out DIR] [--repeat N] [--calib FILE [--image LEFT.u8] [--depth-trunc M] [--depth-scale S] "
     "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
     "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]] "
-    "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]] "
+    "[--normals OUT.f32 [--normals-image OUT.ppm] [--normals-radius R] [--normals-min-cos X]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]"
     " | s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T] "
     "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply] [--tsdf-render POSE [--tsdf-render-depth OUT.f32] "
@@ -36,6 +37,7 @@ struct Options {
     const char *register_cam = nullptr, *reg_depth_path = nullptr, *reg_image_path = nullptr, *reg_index_path = nullptr, *splat_arg = nullptr;
     const char *min_size_arg = nullptr, *labels_path = nullptr, *segmask_path = nullptr;
     const char *voxel_arg = nullptr, *voxel_ply_path = nullptr, *voxel_max_arg = nullptr;
+    const char *normals_path = nullptr, *normals_image_path = nullptr, *normals_radius_arg = nullptr, *normals_min_cos_arg = nullptr;
     const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr, *gt_min_arg = nullptr;
     const char *tsdf_frames_path = nullptr, *tsdf_dims_arg = nullptr, *tsdf_voxel_arg = nullptr, *tsdf_origin_arg = nullptr;
     const char *tsdf_trunc_arg = nullptr, *tsdf_min_weight_arg = nullptr, *tsdf_carve_arg = nullptr, *tsdf_ply_path = nullptr;
@@ -54,6 +56,8 @@ struct Options {
     int repeat = 0, splat = 2, unfiltered = 0;
     long long min_size = 1, voxel_max = 0;               // voxel_max 0: a quarter of the image's pixels
     double max_jump = 1.0, voxel_size = 0.0;
+    int normals_radius = 1;                              // --normals (K28): the distance of the neighbours and the view gate
+    double normals_min_cos = 0.0;
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5, gt_min = 0.0;
 };
 
@@ -84,6 +88,10 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--voxel", true, &Options::voxel_arg},
     {"--voxel-ply", true, &Options::voxel_ply_path},
     {"--voxel-max", true, &Options::voxel_max_arg},
+    {"--normals", true, &Options::normals_path},
+    {"--normals-image", true, &Options::normals_image_path},
+    {"--normals-radius", true, &Options::normals_radius_arg},
+    {"--normals-min-cos", true, &Options::normals_min_cos_arg},
     {"--depth-trunc", true, &Options::depth_trunc_arg},
     {"--depth-scale", true, &Options::depth_scale_arg},
     {"--conf-min", true, &Options::conf_min_arg},
@@ -150,7 +158,7 @@ inline const char* check_tsdf_options(Options& o) {
     if (!o.tsdf_dims_arg || !o.tsdf_voxel_arg || !o.tsdf_origin_arg || !o.tsdf_ply_path || !o.calib_path)
         return "--tsdf-frames needs --tsdf-dims, --tsdf-voxel, --tsdf-origin, --calib and --tsdf-ply";
     if (o.out_dir || o.repeat_arg || o.image_path || o.ply_path || o.mesh_path || o.depth_path || o.register_cam || o.min_size_arg || o.voxel_arg ||
-        o.gt_path || o.max_jump_arg)
+        o.gt_path || o.max_jump_arg || o.normals_path || o.normals_image_path || o.normals_radius_arg || o.normals_min_cos_arg)
         return "--tsdf-frames comes without the options of a single pair";
     double d[3];
     if (!parse_triple(o.tsdf_dims_arg, d)) return "--tsdf-dims: three integers >= 1, NX,NY,NZ with NX*NY*NZ < 2^29";
@@ -259,9 +267,24 @@ inline const char* check_options(Options& o) {
         o.voxel_max = strtoll(o.voxel_max_arg, &end, 10);
         if (end == o.voxel_max_arg || *end || o.voxel_max < 1 || o.voxel_max > (1LL << 29)) return "--voxel-max: an integer >= 1 (at most 2^29)";
     }
-    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && !o.voxel_arg && (o.calib_path == nullptr) != (o.ply_path == nullptr)) return "--calib and --ply come together";
-    if ((o.register_cam || o.min_size_arg || o.voxel_arg) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
-    if (o.max_jump_arg && !o.mesh_path && !o.min_size_arg) return "--max-jump needs --mesh or --min-size";
+    if (o.normals_path && !o.calib_path) return "--normals needs --calib";
+    if (!o.normals_path && (o.normals_image_path || o.normals_radius_arg || o.normals_min_cos_arg))
+        return "--normals-image, --normals-radius and --normals-min-cos need --normals";
+    if (o.normals_radius_arg) {
+        char* end = nullptr;
+        const long long n = strtoll(o.normals_radius_arg, &end, 10);
+        if (end == o.normals_radius_arg || *end || n < 1 || n > 8) return "--normals-radius: an integer in 1..8";
+        o.normals_radius = (int)n;
+    }
+    if (o.normals_min_cos_arg) {
+        char* end = nullptr;
+        o.normals_min_cos = strtod(o.normals_min_cos_arg, &end);
+        if (end == o.normals_min_cos_arg || *end || !isfinite(o.normals_min_cos) || !(o.normals_min_cos < 1.0)) return "--normals-min-cos: a finite number < 1";
+    }
+    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && !o.voxel_arg && !o.normals_path && (o.calib_path == nullptr) != (o.ply_path == nullptr))
+        return "--calib and --ply come together";
+    if ((o.register_cam || o.min_size_arg || o.voxel_arg || o.normals_path) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
+    if (o.max_jump_arg && !o.mesh_path && !o.min_size_arg && !o.normals_path) return "--max-jump needs --mesh or --min-size";
     if (o.max_jump_arg) {
         char* end = nullptr;
         o.max_jump = strtod(o.max_jump_arg, &end);

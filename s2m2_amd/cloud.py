@@ -27,6 +27,11 @@ truncated signed distance volume on the device that ``integrate`` fuses the dept
 ``extract``, no synchronisation, capturable, bit-reproducible.  ``extract_mesh`` (K25, ``s2m2_tsdf_mesh``) returns that surface as a triangle
 mesh: ``extract``'s points as vertices and the marching-cubes faces between them (the rule: include/s2m2_hip.h, K25).  Three launches.
 
+``normals`` (K28, ``s2m2_normals``) gives the maps of ONE frame an orientation: the unit normal of every kept pixel in the camera frame, from
+the neighbours ``radius`` pixels away (the rule: include/s2m2_hip.h, K28), as a ``NormalMap`` -- a ``TsdfRender`` with identity poses.  It fills
+the normals of ``PointCloud.write_ply`` / ``Mesh.write_ply``, and ``track`` registers the next frame against it: K27 without a volume,
+frame-to-frame odometry.  One launch, no synchronisation, capturable.
+
 A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
@@ -165,8 +170,34 @@ class PointCloud:
         """(n,3) uint8 strided view (r, g, b) of the stored records of pair b"""
         return self.records[b, :self.size(b)].view(torch.uint8)[:, 12:15]
 
-    def write_ply(self, path: str, b: int = 0) -> int:
-        return write_ply_records(path, self.records[b, :self.size(b)].cpu().numpy())
+    def _normal_records(self, b: int, normals: "NormalMap", what: str) -> np.ndarray:
+        """the stored records of pair b with the normals of ``normals`` -- a ``NormalMap`` of the same maps, camera and filter keywords, whose
+        kept pixels (depth > 0) in raster order are this cloud's records in record order -- as a ``NORMAL_RECORD_DTYPE`` array; a kept pixel
+        without a normal gets 0,0,0"""
+        n = int(self.count[b].item())
+        if n > self.capacity:
+            raise ValueError(f"{what}: pair {b} has {n} points but a capacity of {self.capacity}: the normals of the unstored points have no record")
+        kept = normals.depth[b, 0] > 0
+        nrm = normals.gradients_buf[b][:, kept].t().cpu().numpy()
+        if len(nrm) != n:
+            raise ValueError(f"{what}: the normal map keeps {len(nrm)} pixels of pair {b}, the cloud {n}: not the same maps, camera or filter")
+        rec = self.records[b, :n].cpu().numpy().view(RECORD_DTYPE).ravel()
+        out = np.empty(n, dtype=NORMAL_RECORD_DTYPE)
+        for name in RECORD_DTYPE.names:
+            out[name] = rec[name]
+        out["nx"], out["ny"], out["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+        return out
+
+    def write_ply(self, path: str, b: int = 0, normals: Optional["NormalMap"] = None) -> int:
+        """the stored records of pair b as a binary PLY; ``normals``: a ``NormalMap`` computed with the same camera and filter keywords adds
+        nx, ny, nz per vertex between the position and the colour (raises when its kept pixels are not this cloud's points)"""
+        if normals is None:
+            return write_ply_records(path, self.records[b, :self.size(b)].cpu().numpy())
+        out = self._normal_records(b, normals, "PointCloud.write_ply")
+        with open(path, "wb") as f:
+            f.write((PLY_NORMALS_HEADER % len(out)).encode("ascii"))
+            f.write(out.tobytes())
+        return len(out)
 
 
 def _binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered) -> Dict[str, object]:
@@ -226,9 +257,12 @@ class Mesh(PointCloud):
             raise ValueError(f"Mesh.faces: pair {b} has {n} vertices but a capacity of {self.capacity}: the faces reference unstored vertices")
         return self.faces_buf[b, :self.face_size(b)]
 
-    def write_ply(self, path: str, b: int = 0) -> tuple:
+    def write_ply(self, path: str, b: int = 0, normals: Optional["NormalMap"] = None) -> tuple:
+        """vertices and faces of pair b in ``write_ply_mesh``'s layout; ``normals``: as for ``PointCloud.write_ply``"""
         faces = self.faces(b).cpu().numpy()
-        return write_ply_mesh(path, self.records[b, :self.size(b)].cpu().numpy(), faces)
+        if normals is None:
+            return write_ply_mesh(path, self.records[b, :self.size(b)].cpu().numpy(), faces)
+        return write_ply_mesh(path, self._normal_records(b, normals, "Mesh.write_ply"), faces, normals=True)
 
 
 def mesh(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, image: torch.Tensor, *, fx: float, cx: float, cy: float, baseline: float,
@@ -748,3 +782,83 @@ class TsdfVolume:
                        max_trans=4.0 * self.trunc if max_trans is None else max_trans, n_iters=n_iters, workspace=self._track_workspace,
                        systems=systems, residual=residual)
         return TsdfTrack(poses, systems, residual)
+
+
+class NormalMap(TsdfRender):
+    """What ``normals`` returns: a ``TsdfRender`` of the frame itself -- ``depth`` (B,1,H,W) fp32 K15's z (0: not kept), ``gradients_buf``
+    (B,3,H,W) fp32 the UNIT normals in the camera frame, towards the camera (0,0,0: no normal), ``image`` (B,3,H,W) uint8 or None (the normal
+    as a colour), ``count`` (B) int32 pixels with a normal or None, ``poses`` a device (B,12) identity and ``camera`` the frame's own.  So
+    ``normals()`` and ``holes()`` work, and it stands wherever K27 takes a render: ``track(..., model=this)``."""
+
+
+_TRACK_WORKSPACES: Dict[torch.device, torch.Tensor] = {}
+
+
+def normals(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: Optional[int] = None, W: Optional[int] = None, fx: float,
+            cx: float, cy: float, baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
+            depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True, radius: int = 1,
+            max_jump: float = 1.0, min_cos: float = 0.0, want_image: bool = False, want_count: bool = True) -> NormalMap:
+    """``reproject``'s maps and conventions (no image: ``H`` and ``W`` name the fused crop, default the maps' own size) -> NormalMap (K28,
+    ``s2m2_normals``; the rule: include/s2m2_hip.h, K28).  The normal of a kept pixel is the cross product of the vertical and the horizontal
+    difference of the points ``radius`` (1..8) pixels away -- central where both neighbours are kept and their disparities differ from the
+    pixel's by at most ``max_jump * radius`` (``mesh``'s gate; inf joins every kept neighbour), one-sided where one is --, normalised, and kept
+    where its cosine with the direction to the camera is at least ``min_cos``.  Only allocates: one launch, no synchronisation, capturable."""
+    B, _, Hp, Wp = disp.shape
+    H = Hp if H is None else int(H)
+    W = Wp if W is None else int(W)
+    dev = disp.device
+    depth = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    nrm = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+    image = torch.empty((B, 3, H, W), device=dev, dtype=torch.uint8) if want_image else None
+    count = torch.empty((B,), device=dev, dtype=torch.int32) if want_count else None
+    kw = _binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered)
+    hip.normals(disp, occ, conf, H=H, W=W, **kw, radius=radius, max_jump=max_jump, min_cos=min_cos, depth=depth, normals=nrm, image=image,
+                count=count)
+    poses = torch.eye(3, 4, device=dev, dtype=torch.float32).reshape(1, 12).repeat(B, 1)
+    return NormalMap(depth, nrm, image, count, poses.view(B, 3, 4)[:, :, :3], poses, Camera(W, H, kw["fx"], kw["fy"], cx, cy))
+
+
+def track(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, model: TsdfRender, *, R=None, t=None, poses: Optional[torch.Tensor] = None,
+          fx: float, cx: float, cy: float, baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
+          depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True, H: Optional[int] = None,
+          W: Optional[int] = None, max_dist: float, max_trans: float, n_iters: int = 10, min_count: int = 100, max_rot: float = 0.2,
+          want_systems: bool = True, want_residual: bool = False) -> TsdfTrack:
+    """K27 (``s2m2_tsdf_track``) without a volume: the live maps in ``reproject``'s conventions (``H``, ``W``: the fused crop, default the maps'
+    own size) are registered to ``model``, any ``TsdfRender`` with gradients, poses and a camera -- a ``NormalMap`` of the previous frame
+    makes this frame-to-frame odometry: the result is the pose of the live camera in the previous frame's.  The initial guess is ``R``, ``t``
+    in ``TsdfVolume.integrate``'s shapes, or ``poses``: a device (B,12) fp32 buffer that is refined IN PLACE; with none of them the identity.
+    ``max_dist`` (the correspondence gate) and ``max_trans`` (the longest step of an iteration), both in the unit of z, have no default: there
+    is no truncation distance to derive them from.  The workspace is kept per device from the first call on (make that call outside a
+    capture).  2 * n_iters launches, no synchronisation, capturable together with ``normals``."""
+    if model.gradients_buf is None or model.poses is None or model.camera is None:
+        raise ValueError("track: the model must carry gradients, poses and a camera (normals(...), or raycast(..., want_gradients=True))")
+    B = disp.shape[0]
+    dev = disp.device
+    if poses is not None and (R is not None or t is not None):
+        raise ValueError("track: pass the initial guess either as R and t or as poses")
+    if poses is None:
+        if (R is None) != (t is None):
+            raise ValueError("track: R and t come together")
+        if R is None:
+            poses = torch.eye(3, 4, device=dev, dtype=torch.float32).reshape(1, 12).repeat(B, 1)
+        else:
+            R = torch.as_tensor(R).to(device=dev, dtype=torch.float32)
+            t = torch.as_tensor(t).to(device=dev, dtype=torch.float32)
+            if tuple(R.shape) not in ((3, 3), (B, 3, 3)) or tuple(t.shape) not in ((3,), (B, 3)):
+                raise ValueError(f"track: R is (3,3) or ({B},3,3) and t is (3,) or ({B},3), got {tuple(R.shape)} and {tuple(t.shape)}")
+            poses = torch.cat([R.expand(B, 3, 3), t.expand(B, 3)[:, :, None]], dim=2).reshape(B, 12).contiguous()
+    Hl = disp.shape[2] if H is None else int(H)
+    Wl = disp.shape[3] if W is None else int(W)
+    need = hip.tsdf_track_workspace_bytes(B, Hl, Wl)
+    workspace = _TRACK_WORKSPACES.get(dev)
+    if workspace is None or workspace.nbytes < need:
+        workspace = _TRACK_WORKSPACES[dev] = torch.empty((need // 8,), device=dev, dtype=torch.float64)
+    n_iters = int(n_iters)
+    systems = torch.empty((B, n_iters, 32), device=dev, dtype=torch.float64) if want_systems else None
+    residual = torch.empty((B, 1, Hl, Wl), device=dev, dtype=torch.float32) if want_residual else None
+    kw = _binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered)
+    cam = model.camera
+    hip.tsdf_track(disp, occ, conf, poses, model.poses, model.depth, model.gradients_buf, H=Hl, W=Wl, **kw, mfx=cam.fx, mfy=cam.fy, mcx=cam.cx,
+                   mcy=cam.cy, max_dist=max_dist, min_count=min_count, max_rot=max_rot, max_trans=max_trans, n_iters=n_iters,
+                   workspace=workspace, systems=systems, residual=residual)
+    return TsdfTrack(poses, systems, residual)

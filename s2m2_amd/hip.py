@@ -181,6 +181,12 @@ class TsdfTrackDesc(ctypes.Structure):
                 ("max_rot", ctypes.c_double), ("max_trans", ctypes.c_double)]
 
 
+class NormalsDesc(ctypes.Structure):
+    """mirror of s2m2_normals_desc (include/s2m2_hip.h): K28, the normal map of the disparity map"""
+    _fields_ = [("cloud", CloudDesc), ("depth", _vp), ("normals", _vp), ("image", _vp), ("count", _vp), ("radius", _i),
+                ("max_jump", ctypes.c_double), ("min_cos", ctypes.c_double)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -311,6 +317,7 @@ SIGNATURES = {
     "s2m2_tsdf_raycast": (_i, [ctypes.POINTER(TsdfRaycastDesc), _vp]),
     "s2m2_tsdf_track_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_tsdf_track": (_i, [ctypes.POINTER(TsdfTrackDesc), _vp]),
+    "s2m2_normals": (_i, [ctypes.POINTER(NormalsDesc), _vp]),
 }
 
 
@@ -1422,3 +1429,5 @@ from .hip_voxel import voxel, voxel_home_slot, voxel_slots, voxel_tile_rows, vox
 # hip_tsdf.py
 from .hip_tsdf import (RAYCAST_MAX_STEPS, TRACK_MAX_ITERS, tsdf_extract, tsdf_integrate, tsdf_mesh, tsdf_mesh_workspace_bytes, tsdf_raycast,  # noqa: E402,F401
                        tsdf_raycast_steps, tsdf_tile_voxels, tsdf_track, tsdf_track_workspace_bytes, tsdf_workspace_bytes)
+# K28 (s2m2_normals): likewise, from hip_normals.py
+from .hip_normals import NORMALS_MAX_RADIUS, normals  # noqa: E402,F401

@@ -188,6 +188,22 @@ def get_mesh(rgb, disp, calib, depth_trunc=None, max_jump=1.0):
                           max_jump=max_jump)
 
 
+def get_normals(disp, calib, depth_trunc=None, radius=1, max_jump=1.0, min_cos=0.0):
+    """``get_pointcloud``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter: ``disp`` (H,W) arrives filtered, -1
+    where invalid) -> a ``cloud.NormalMap`` on the device: the depth map and the unit normal of every kept pixel in the camera frame, from the
+    neighbours ``radius`` pixels away whose disparities differ by at most ``max_jump * radius`` px, kept where the cosine with the direction to
+    the camera is at least ``min_cos``.  ``PointCloud.write_ply(..., normals=...)`` and ``Mesh.write_ply`` take it."""
+    from . import cloud
+    disp_t = torch.as_tensor(disp)
+    device = disp_t.device if disp_t.is_cuda else torch.device("cuda")
+    disp_t = disp_t.to(device=device, dtype=torch.float32).contiguous()[None, None]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(device):
+        return cloud.normals(disp_t, disp_t, disp_t, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
+                             baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
+                             radius=radius, max_jump=max_jump, min_cos=min_cos)
+
+
 def voxel_down_sample(rgb, disp, calib, voxel_size, depth_trunc=None):
     """``get_pointcloud``'s arguments and conventions (halved intrinsics, fx for both focal lengths, no confidence filter) -> a
     ``cloud.VoxelCloud`` on the device: one point per occupied cell of a grid of ``voxel_size`` (the unit of z: metres with a Middlebury
