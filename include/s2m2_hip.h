@@ -1480,6 +1480,65 @@ typedef struct s2m2_normals_desc {
 } s2m2_normals_desc;
 int s2m2_normals(const s2m2_normals_desc* desc, void* stream);
 
+/*
+ * K29 -- edge-preserving smoothing of the disparity map: a bilateral filter over the (2 radius + 1)^2 window of every kept pixel, in front of
+ *   K15 / K20 .. K28, which all take the map exactly as it leaves the forward.  Its output has the form K22 established: a PADDED disparity map
+ *   with -1 at dropped pixels, fed to any stage behind it with unfiltered = 1.  No counterpart in the reference: the semantics are defined here
+ *   and pinned by the numpy oracle of tests/smooth_oracle.py.  Still S2M2_ABI_VERSION 800: two entry points are added, nothing changes in place.
+ *   `cloud` holds the INPUT fields of s2m2_cloud with the meaning they have in s2m2_normals_desc: the B padded maps, H, W, Hp, Wp (fused crop),
+ *   camera and filter parameters, unfiltered.  Its outputs are IGNORED and the image is not needed.
+ *   The weights.  No exponential is evaluated on the device.  The host forms two tables in double and rounds each entry ONCE to fp32:
+ *     ws[k] = exp(-(k*k) / (2 sigma_s^2))                                       k = 0 .. radius   (entries behind radius are 0 and never read)
+ *     wr[i] = exp(-(e_i*e_i) / (2 sigma_r^2)),   e_i = i * (4 sigma_r / 256)    i = 0 .. 256
+ *     inv   = (float)(256 / (4 sigma_r))
+ *   s2m2_smooth_weights returns exactly the values a call of s2m2_smooth with these parameters uses; it touches no device.  The tables reach
+ *   the kernel as kernel arguments: no allocation, no workspace.  gate = (float)max_jump is formed once on the host.
+ *   All in fp32, every operation ONE IEEE rounding, nothing fused into a multiply-add; the division is correctly rounded.
+ *   Per pair b and pixel c = (v, u) of the UNPADDED image, keep = K15's (the same device functions), d = the map's disparity:
+ *     not keep(c): disp_out = -1, taps = 0.
+ *     num = 0;  den = 0;  n = 0
+ *     for dv = -radius .. radius:                   raster order of the window: dv outer, du inner, both ascending
+ *       for du = -radius .. radius:
+ *         q = (v + dv, u + du);  skipped unless q lies inside the H x W image and keep(q)
+ *         e = d_q - d_c;   a = fabsf(e);   skipped unless a <= gate                                  (a NaN fails)
+ *         t = fminf(a * inv, 256.f);   i = (int)t                                                   (truncation; t is in [0, 256])
+ *         w = (ws[|dv|] * ws[|du|]) * wr[i]                                                         (two products)
+ *         num = num + w * e;   den = den + w;   n += 1
+ *     disp_out = d_c + num / den;   taps = n
+ *   The centre always enters with w = 1 exactly (ws[0] = wr[0] = 1), so den >= 1.  (Two corners that only unusual parameters reach: a kept
+ *   d_c = -inf -- K15 keeps d <= 0 when depth_trunc admits 1e9 / depth_scale -- fails its own gate and gives a NaN; a sigma_r so small that inv
+ *   is +inf sends every tap to wr[256].)  Padded map pixels outside the crop are outside the image, whatever memory holds there.  max_jump is
+ *   NOT scaled by the radius, unlike K28's: it is the largest disparity difference between the centre and a neighbour anywhere in the window.
+ *   The order of the additions is part of the rule: the sum of a pixel is sequential.
+ *   Non-finite maps never form an address: the only index formed from a float is i, which is clamped first (fminf returns the number when one
+ *   operand is a NaN).
+ *   outputs, each optional (NULL), at least one; every element of every requested output is written:
+ *     disp_out (B,1,Hp,Wp) fp32, the PADDED map: the smoothed disparity where the pixel is kept, -1 everywhere else, the padding border
+ *              included (K22's disp_out convention).  It must not overlap an input map: blocks read each other's halo.
+ *     taps     (B,1,H,W) int32: n, the neighbours that entered the sum, the pixel itself included; 0 where the pixel is not kept
+ *     count    (B) int32 kept pixels: cleared on the stream by the entry point, then one atomic integer add per block.  The sum does not
+ *              depend on the order, so the stage stays bit-reproducible.
+ *   One launch plus the clear of count, no workspace, no host step.
+ *   Errors (before any device call): null descriptor; everything s2m2_normals checks of its maps and camera; no output requested; disp_out,
+ *   taps or count not 4-byte aligned; disp_out overlapping an input map; radius outside 1 .. 8; sigma_s or sigma_r not finite or <= 0;
+ *   max_jump negative or NaN (+inf is allowed: only keep decides).  s2m2_smooth_weights: a null pointer, or a bad radius or sigma.
+ *   Launch plans: s2m2_smooth is NOT recorded.  Called while the calling thread records a plan it fails with an error and launches nothing.
+ *   Safe under stream capture (hipGraph).
+ */
+typedef struct s2m2_smooth_desc {
+    s2m2_cloud_desc cloud;   /* the maps: K28's meaning; outputs ignored, image not needed */
+    float*   disp_out;       /* (B,1,Hp,Wp) fp32: the smoothed PADDED map, -1 where not kept and on the border; optional */
+    int32_t* taps;           /* (B,1,H,W) int32: neighbours in the pixel's sum, itself included; 0 where not kept; optional */
+    int32_t* count;          /* (B) kept pixels; optional */
+    int      radius;         /* 1 .. 8: the window is (2 radius + 1)^2 */
+    double   sigma_s;        /* pixels, finite, > 0 */
+    double   sigma_r;        /* px of disparity, finite, > 0 */
+    double   max_jump;       /* px of disparity, >= 0, +inf allowed; NOT scaled by the radius */
+} s2m2_smooth_desc;
+int s2m2_smooth(const s2m2_smooth_desc* desc, void* stream);
+/* ws9: 9 floats, wr257: 257 floats, inv: 1 float; host memory.  No device is touched. */
+int s2m2_smooth_weights(int radius, double sigma_s, double sigma_r, float* ws9, float* wr257, float* inv);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,13 @@
 //   disparity differs by at most R times --max-jump (default 1) px; a normal is kept where its cosine with the direction to the camera is at
 //   least X (default 0).  Honours --depth-trunc, --depth-scale, --conf-min, --occ-min and --unfiltered, comes behind --min-size exactly as --ply
 //   does, and names its files like --ply for B > 1.  With --repeat: {"normals_count", "repeat", "normals_us_per_pair"} on a line of its own.
+// --smooth R --smooth-sigma-r X --smooth-max-jump X [--smooth-sigma-s X] [--smooth-out OUT.f32]: edge-preserving smoothing of the disparity map
+//   (s2m2_smooth), behind --calib and --min-size and in front of every 3D output: --ply, --mesh, --depth, --voxel, --register and --normals
+//   read the smoothed map, and with --tsdf-frames every frame is fused and tracked from it.  A bilateral filter over the (2R + 1)^2 window
+//   (R in 1..8) with the widths --smooth-sigma-s pixels (default R / 2) and --smooth-sigma-r px of disparity; a neighbour enters where its
+//   disparity differs from the pixel's by at most --smooth-max-jump px (inf is allowed).  The last two have no default: they depend on the
+//   rig's disparity noise.  --smooth-out: the raw float32 (B,1,Hp,Wp) padded map, -1 = dropped.  With --repeat: {"smooth_kept", "repeat",
+//   "smooth_us_per_pair"} on a line of its own.
 // --min-size N [--max-jump X] [--labels OUT.i32] [--segment-mask OUT.u8]: the speckle filter (s2m2_segment) behind the forward and in front of
 //   every 3D output above: the 4-connected components of the kept pixels whose neighbouring disparities differ by at most X px (the --max-jump
 //   of --mesh, default 1), and the disparity map without the components of fewer than N pixels (N >= 1; 1 removes nothing).  Needs --calib;
@@ -169,6 +176,7 @@ struct Context {
     const float* disp3d = nullptr;
     int unfiltered3d = 0;
     DeviceBuffer filtered, image;                         // image: --image, uploaded on first use
+    DeviceBuffer smoothed;                                // --smooth: the map K29 leaves, behind --min-size's
     explicit Context(const Options& opt) : o(opt) {}
 };
 
@@ -224,6 +232,40 @@ static int stage_segment(Context& c) {
                hstats[0], hstats[1], hstats[2], o.repeat, 1000.f * ms / o.repeat / m.B);
     }
     c.disp3d = c.filtered.as<float>();
+    c.unfiltered3d = 1;
+    return 0;
+}
+
+// the descriptor of --smooth (K29) on the maps disp / occ / conf, into `out`
+static void fill_smooth(s2m2_smooth_desc& sd, const s2m2_engine_info& m, const float* disp, const float* occ, const float* conf, int unfiltered,
+                        const Calib& cal, const Options& o, float* out, int32_t* count) {
+    memset(&sd, 0, sizeof sd);
+    fill_cloud_inputs(sd.cloud, m, disp, occ, conf, nullptr, S2M2_F32, unfiltered, cal, o);
+    sd.disp_out = out; sd.count = count;
+    sd.radius = o.smooth_radius; sd.sigma_s = o.smooth_sigma_s; sd.sigma_r = o.smooth_sigma_r; sd.max_jump = o.smooth_max_jump;
+}
+
+// --smooth (K29): the smoothed map for the stages behind, which read it with the filter already applied
+static int stage_smooth(Context& c) {
+    const Options& o = c.o;
+    const s2m2_engine_info& m = c.m;
+    const size_t map = (size_t)m.B * m.out_h * m.out_w;
+    DeviceBuffer dcount;
+    if (DeviceBuffer::make(c.smoothed, map * sizeof(float)) || DeviceBuffer::make(dcount, m.B * sizeof(int32_t))) return 1;
+    s2m2_smooth_desc sd;
+    fill_smooth(sd, m, c.disp3d, c.maps[1], c.maps[2], c.unfiltered3d, c.cal, o, c.smoothed.as<float>(), dcount.as<int32_t>());
+    const auto run = [&] { return s2m2_smooth(&sd, c.s) == 0 ? 0 : fail_lib("s2m2_smooth failed"); };
+    if (run()) return 1;
+    HIP_OK(hipStreamSynchronize(c.s), "s2m2_smooth");
+    std::vector<int32_t> hcount(m.B);
+    HIP_OK(hipMemcpy(hcount.data(), dcount.h, m.B * sizeof(int32_t), hipMemcpyDeviceToHost), "download");
+    if (o.smooth_out_path && download_and_write(c.smoothed.h, map * sizeof(float), o.smooth_out_path, "cannot write the smoothed map")) return 1;
+    if (o.repeat > 0) {
+        float ms = 0.f;
+        if (time_calls(c.s, o.repeat, run, &ms, "timed smooth runs")) return 1;
+        printf("{\"smooth_kept\": %d, \"repeat\": %d, \"smooth_us_per_pair\": %.2f}\n", hcount[0], o.repeat, 1000.f * ms / o.repeat / m.B);
+    }
+    c.disp3d = c.smoothed.as<float>();
     c.unfiltered3d = 1;
     return 0;
 }
@@ -576,6 +618,14 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
     s2m2_tsdf_desc td;
     memset(&td, 0, sizeof td);
     fill_cloud_inputs(td.cloud, m, dout[0].as<float>(), dout[1].as<float>(), dout[2].as<float>(), dimage.h, 2, o.unfiltered, cal, o);
+    DeviceBuffer dsmooth;                                                    // --smooth (K29): every frame is fused, and tracked, from its smoothed map
+    s2m2_smooth_desc sm;
+    if (o.smooth_arg) {
+        if (DeviceBuffer::make(dsmooth, map * sizeof(float))) return 1;
+        fill_smooth(sm, m, dout[0].as<float>(), dout[1].as<float>(), dout[2].as<float>(), o.unfiltered, cal, o, dsmooth.as<float>(), nullptr);
+        td.cloud.disp = dsmooth.as<float>();
+        td.cloud.unfiltered = 1;
+    }
     td.volume = dvol.h; td.poses = dpose.as<float>();
     td.Nx = o.tsdf_dims[0]; td.Ny = o.tsdf_dims[1]; td.Nz = o.tsdf_dims[2];
     td.max_weight = 32767; td.carve = o.tsdf_carve;
@@ -600,6 +650,7 @@ static int run_tsdf(const Options& o, s2m2_engine* eng, const s2m2_engine_info& 
         HIP_OK(hipMemcpy(dimage.h, hi.data(), img, hipMemcpyHostToDevice), "upload");
         if (!o.tsdf_track || first) HIP_OK(hipMemcpy(dpose.h, fr.pose, sizeof fr.pose, hipMemcpyHostToDevice), "upload");
         if (s2m2_engine_run(eng, dl.h, dr.h, dout[0].as<float>(), dout[1].as<float>(), dout[2].as<float>(), s) != 0) return fail_lib("engine run failed");
+        if (o.smooth_arg && s2m2_smooth(&sm, s) != 0) return fail_lib("s2m2_smooth failed");
         int status = 0;
         if (o.tsdf_track && first) memcpy(pose, fr.pose, sizeof pose);
         if (o.tsdf_track && !first) {
@@ -745,11 +796,12 @@ int main(int argc, char** argv) {
         printf("{\"B\": %d, \"H\": %d, \"W\": %d, \"repeat\": %d, \"ms_per_pair\": %.4f}\n", m.B, m.H, m.W, o.repeat, ms / o.repeat / m.B);
     }
     const bool cloud = o.calib_path && (o.ply_path || o.mesh_path);
-    if (o.min_size_arg || cloud || o.register_cam || o.voxel_arg || o.normals_path) {              // the calibration: once, in front of the first 3D stage
+    if (o.min_size_arg || cloud || o.register_cam || o.voxel_arg || o.normals_path || o.smooth_arg) {   // the calibration: once, in front of the first 3D stage
         if (!read_calib(o.calib_path, c.cal)) return fail("--calib: cannot read cam0 and baseline from the file");
         if (m.out_h != m.H || m.out_w != m.W) return fail("the 3D outputs need maps of the image's size (an engine without output_upsample)");
     }
     if (o.min_size_arg && stage_segment(c)) return 1;
+    if (o.smooth_arg && stage_smooth(c)) return 1;
     if (cloud && stage_cloud(c)) return 1;
     if (o.voxel_arg && stage_voxel(c)) return 1;
     if (o.register_cam && stage_register(c)) return 1;

@@ -18,12 +18,13 @@ inline const char* const USAGE =
     "[--conf-min X] [--occ-min X] [--unfiltered] [--ply OUT.ply] [--mesh OUT.ply [--max-jump X]] [--depth OUT.f32] "
     "[--register CAM [--splat N] --register-depth OUT.f32 [--register-image OUT.ppm] [--register-index OUT.i32]] "
     "[--min-size N [--labels OUT.i32] [--segment-mask OUT.u8]] [--voxel SIZE --voxel-ply OUT.ply [--voxel-max N]] "
-    "[--normals OUT.f32 [--normals-image OUT.ppm] [--normals-radius R] [--normals-min-cos X]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
+    "[--normals OUT.f32 [--normals-image OUT.ppm] [--normals-radius R] [--normals-min-cos X]] "
+    "[--smooth R --smooth-sigma-r X --smooth-max-jump X [--smooth-sigma-s X] [--smooth-out OUT.f32]]] [--gt FILE.pfm [--gt-region FILE.u8] [--gt-min X] "
     "[--thresholds a,b,c] --metrics OUT.json]"
     " | s2m2_run_engine ENGINE --tsdf-frames LIST.txt --tsdf-dims NX,NY,NZ --tsdf-voxel VS --tsdf-origin X,Y,Z [--tsdf-trunc T] "
     "[--tsdf-min-weight N] [--tsdf-carve] --calib FILE --tsdf-ply OUT.ply [--tsdf-mesh OUT.ply] [--tsdf-render POSE [--tsdf-render-depth OUT.f32] "
     "[--tsdf-render-image OUT.u8] [--tsdf-render-step X] [--tsdf-render-min-weight N]] [--tsdf-track [--tsdf-track-iters N] [--tsdf-track-dist D] "
-    "[--tsdf-poses-out FILE]] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
+    "[--tsdf-poses-out FILE]] [--smooth R --smooth-sigma-r X --smooth-max-jump X [--smooth-sigma-s X]] [--depth-trunc M] [--depth-scale S] [--conf-min X] [--occ-min X] "
     "[--unfiltered]";
 
 // ---- options: every option as it stands on the command line (null: not given), then the numbers check_options parses from them
@@ -38,6 +39,8 @@ struct Options {
     const char *min_size_arg = nullptr, *labels_path = nullptr, *segmask_path = nullptr;
     const char *voxel_arg = nullptr, *voxel_ply_path = nullptr, *voxel_max_arg = nullptr;
     const char *normals_path = nullptr, *normals_image_path = nullptr, *normals_radius_arg = nullptr, *normals_min_cos_arg = nullptr;
+    const char *smooth_arg = nullptr, *smooth_sigma_r_arg = nullptr, *smooth_max_jump_arg = nullptr, *smooth_sigma_s_arg = nullptr;
+    const char* smooth_out_path = nullptr;
     const char *gt_path = nullptr, *region_path = nullptr, *metrics_path = nullptr, *thr_arg = nullptr, *gt_min_arg = nullptr;
     const char *tsdf_frames_path = nullptr, *tsdf_dims_arg = nullptr, *tsdf_voxel_arg = nullptr, *tsdf_origin_arg = nullptr;
     const char *tsdf_trunc_arg = nullptr, *tsdf_min_weight_arg = nullptr, *tsdf_carve_arg = nullptr, *tsdf_ply_path = nullptr;
@@ -58,6 +61,8 @@ struct Options {
     double max_jump = 1.0, voxel_size = 0.0;
     int normals_radius = 1;                              // --normals (K28): the distance of the neighbours and the view gate
     double normals_min_cos = 0.0;
+    int smooth_radius = 0;                               // --smooth (K29): the window, the two widths (sigma_s: radius / 2 unless given), the gate
+    double smooth_sigma_s = 0.0, smooth_sigma_r = 0.0, smooth_max_jump = 0.0;
     double depth_trunc = 0.0, depth_scale = 1000.0, conf_min = 0.1, occ_min = 0.5, gt_min = 0.0;
 };
 
@@ -92,6 +97,11 @@ inline const OptionRow OPTION_TABLE[] = {
     {"--normals-image", true, &Options::normals_image_path},
     {"--normals-radius", true, &Options::normals_radius_arg},
     {"--normals-min-cos", true, &Options::normals_min_cos_arg},
+    {"--smooth", true, &Options::smooth_arg},
+    {"--smooth-sigma-r", true, &Options::smooth_sigma_r_arg},
+    {"--smooth-max-jump", true, &Options::smooth_max_jump_arg},
+    {"--smooth-sigma-s", true, &Options::smooth_sigma_s_arg},
+    {"--smooth-out", true, &Options::smooth_out_path},
     {"--depth-trunc", true, &Options::depth_trunc_arg},
     {"--depth-scale", true, &Options::depth_scale_arg},
     {"--conf-min", true, &Options::conf_min_arg},
@@ -151,6 +161,28 @@ inline bool parse_pose(const char* arg, float* v) {
     return true;
 }
 
+// the rules of the --smooth* options (K29), which both modes take; null: complete
+inline const char* check_smooth_options(Options& o) {
+    if (!o.smooth_arg) {
+        if (o.smooth_sigma_r_arg || o.smooth_max_jump_arg || o.smooth_sigma_s_arg || o.smooth_out_path)
+            return "--smooth-sigma-r, --smooth-max-jump, --smooth-sigma-s and --smooth-out need --smooth";
+        return nullptr;
+    }
+    if (!o.smooth_sigma_r_arg || !o.smooth_max_jump_arg)
+        return "--smooth needs --smooth-sigma-r and --smooth-max-jump: they depend on the rig's disparity noise and have no default";
+    if (!o.calib_path) return "--smooth needs --calib";
+    char* end = nullptr;
+    const long long n = strtoll(o.smooth_arg, &end, 10);
+    if (end == o.smooth_arg || *end || n < 1 || n > 8) return "--smooth: the radius, an integer in 1..8";
+    o.smooth_radius = (int)n;
+    o.smooth_sigma_s = 0.5 * (double)n;
+    if (!parse_positive(o.smooth_sigma_r_arg, o.smooth_sigma_r)) return "--smooth-sigma-r: a finite number > 0";
+    if (o.smooth_sigma_s_arg && !parse_positive(o.smooth_sigma_s_arg, o.smooth_sigma_s)) return "--smooth-sigma-s: a finite number > 0";
+    o.smooth_max_jump = strtod(o.smooth_max_jump_arg, &end);
+    if (end == o.smooth_max_jump_arg || *end || !(o.smooth_max_jump >= 0.0)) return "--smooth-max-jump: a number >= 0 (inf is allowed)";
+    return nullptr;
+}
+
 // the rules of the --tsdf-* options (K24); null: complete.  The mode takes ENGINE alone: its pairs come from LIST
 inline const char* check_tsdf_options(Options& o) {
     if (!o.tsdf_frames_path) return "the --tsdf-* options need --tsdf-frames";
@@ -158,7 +190,7 @@ inline const char* check_tsdf_options(Options& o) {
     if (!o.tsdf_dims_arg || !o.tsdf_voxel_arg || !o.tsdf_origin_arg || !o.tsdf_ply_path || !o.calib_path)
         return "--tsdf-frames needs --tsdf-dims, --tsdf-voxel, --tsdf-origin, --calib and --tsdf-ply";
     if (o.out_dir || o.repeat_arg || o.image_path || o.ply_path || o.mesh_path || o.depth_path || o.register_cam || o.min_size_arg || o.voxel_arg ||
-        o.gt_path || o.max_jump_arg || o.normals_path || o.normals_image_path || o.normals_radius_arg || o.normals_min_cos_arg)
+        o.gt_path || o.max_jump_arg || o.normals_path || o.normals_image_path || o.normals_radius_arg || o.normals_min_cos_arg || o.smooth_out_path)
         return "--tsdf-frames comes without the options of a single pair";
     double d[3];
     if (!parse_triple(o.tsdf_dims_arg, d)) return "--tsdf-dims: three integers >= 1, NX,NY,NZ with NX*NY*NZ < 2^29";
@@ -235,6 +267,7 @@ inline const char* check_options(Options& o) {
     if (o.occ_min_arg) o.occ_min = atof(o.occ_min_arg);
     if (o.gt_min_arg) o.gt_min = atof(o.gt_min_arg);
     o.unfiltered = o.unfiltered_arg != nullptr;
+    if (const char* msg = check_smooth_options(o)) return msg;
     if (o.tsdf_frames_path || o.tsdf_dims_arg || o.tsdf_voxel_arg || o.tsdf_origin_arg || o.tsdf_trunc_arg || o.tsdf_min_weight_arg || o.tsdf_carve_arg ||
         o.tsdf_ply_path || o.tsdf_mesh_path || o.tsdf_render_arg || o.tsdf_render_depth_path || o.tsdf_render_image_path || o.tsdf_render_step_arg ||
         o.tsdf_render_min_weight_arg || o.tsdf_track_arg || o.tsdf_track_iters_arg || o.tsdf_track_dist_arg || o.tsdf_poses_out_path)
@@ -281,9 +314,10 @@ inline const char* check_options(Options& o) {
         o.normals_min_cos = strtod(o.normals_min_cos_arg, &end);
         if (end == o.normals_min_cos_arg || *end || !isfinite(o.normals_min_cos) || !(o.normals_min_cos < 1.0)) return "--normals-min-cos: a finite number < 1";
     }
-    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && !o.voxel_arg && !o.normals_path && (o.calib_path == nullptr) != (o.ply_path == nullptr))
+    if (!o.mesh_path && !o.register_cam && !o.min_size_arg && !o.voxel_arg && !o.normals_path && !o.smooth_arg &&
+        (o.calib_path == nullptr) != (o.ply_path == nullptr))
         return "--calib and --ply come together";
-    if ((o.register_cam || o.min_size_arg || o.voxel_arg || o.normals_path) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
+    if ((o.register_cam || o.min_size_arg || o.voxel_arg || o.normals_path || o.smooth_arg) && !o.mesh_path && !o.ply_path && o.depth_path) return "--depth needs --ply or --mesh";
     if (o.max_jump_arg && !o.mesh_path && !o.min_size_arg && !o.normals_path) return "--max-jump needs --mesh or --min-size";
     if (o.max_jump_arg) {
         char* end = nullptr;

@@ -32,6 +32,10 @@ the neighbours ``radius`` pixels away (the rule: include/s2m2_hip.h, K28), as a 
 the normals of ``PointCloud.write_ply`` / ``Mesh.write_ply``, and ``track`` registers the next frame against it: K27 without a volume,
 frame-to-frame odometry.  One launch, no synchronisation, capturable.
 
+``smooth`` (K29, ``s2m2_smooth``) comes in front of all of them: an edge-preserving (bilateral) filter of the disparity map with a jump gate,
+whose output has ``Segments.disp``'s form -- the padded map with -1 at dropped pixels, for any stage with ``filtered=False`` (the rule:
+include/s2m2_hip.h, K29).  One launch, no synchronisation, capturable, bit-reproducible.
+
 A record is 16 bytes --``float x, y, z; uint8 r, g, b, a`` (a = 255) -- which is the vertex of a binary little-endian PLY: ``write_ply_records``
 writes a record buffer as it is.
 """
@@ -816,6 +820,51 @@ def normals(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: Opt
                 count=count)
     poses = torch.eye(3, 4, device=dev, dtype=torch.float32).reshape(1, 12).repeat(B, 1)
     return NormalMap(depth, nrm, image, count, poses.view(B, 3, 4)[:, :, :3], poses, Camera(W, H, kw["fx"], kw["fy"], cx, cy))
+
+
+class Smoothed:
+    """What ``smooth`` returns, all on the device: ``disp`` (B,1,Hp,Wp) fp32, the PADDED smoothed disparity with -1 wherever the pixel is not
+    kept (border included: ``Segments.disp``'s convention); ``taps`` (B,1,H,W) int32 or None (neighbours in the pixel's sum, itself included;
+    0: not kept); ``count`` (B) int32 kept pixels or None."""
+
+    def __init__(self, disp: torch.Tensor, taps: Optional[torch.Tensor], count: Optional[torch.Tensor]):
+        self.disp, self.taps, self.count = disp, taps, count
+
+    def kept(self, b: int = 0) -> int:
+        """kept pixels of pair b -- reads ``count`` on the host (synchronises)"""
+        if self.count is None:
+            raise ValueError("Smoothed.kept: smooth was called with want_count=False")
+        return int(self.count[b].item())
+
+
+def smooth(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, *, H: Optional[int] = None, W: Optional[int] = None, fx: float,
+           cx: float, cy: float, baseline: float, doffs: float = 0.0, fy: Optional[float] = None, depth_scale: float = 1000.0,
+           depth_trunc: Optional[float] = None, conf_min: float = 0.1, occ_min: float = 0.5, filtered: bool = True, radius: int = 2,
+           sigma_s: Optional[float] = None, sigma_r: float, max_jump: float, want_taps: bool = False, want_count: bool = True) -> Smoothed:
+    """``reproject``'s maps and conventions (no image: ``H`` and ``W`` name the fused crop, default the maps' own size) -> Smoothed (K29,
+    ``s2m2_smooth``; the rule: include/s2m2_hip.h, K29).  A bilateral filter: every kept pixel becomes the weighted mean of the kept pixels of
+    its (2 ``radius`` + 1)^2 window (radius 1..8) whose disparities differ from its own by at most ``max_jump`` px -- NOT scaled by the radius
+    --, weighted by a Gaussian of the distance (``sigma_s`` pixels, None: ``radius / 2``) times a Gaussian of the disparity difference
+    (``sigma_r`` px).  ``sigma_r`` and ``max_jump`` have no default: they depend on the rig's disparity noise (a few sigma of it, and less
+    than the smallest step that must stay an edge).  Only allocates: one launch, no synchronisation, capturable.
+
+    Composition: ``s = smooth(...)`` then ``normals(s.disp, occ, conf, ..., filtered=False)`` (or ``reproject`` / ``mesh`` / ``register`` /
+    ``voxelize`` / ``TsdfVolume.integrate`` / ``track``) sees exactly the kept pixels with their smoothed disparities -- whenever K15 itself
+    drops d <= 0, that is whenever ``1e9 / depth_scale >= depth_trunc``.  With ``depth_trunc=None`` K15 keeps d <= 0 at z = 1e6 (depth_scale
+    1000) as the reference's formula does, the dropped pixels included: pass a real truncation distance to the stage behind.  After
+    ``segment``, pass ``segment(...).disp`` in with ``filtered=False``, so that speckles are removed before they are averaged into their
+    surroundings."""
+    B, _, Hp, Wp = disp.shape
+    H = Hp if H is None else int(H)
+    W = Wp if W is None else int(W)
+    dev = disp.device
+    out = torch.empty((B, 1, Hp, Wp), device=dev, dtype=torch.float32)
+    taps = torch.empty((B, 1, H, W), device=dev, dtype=torch.int32) if want_taps else None
+    count = torch.empty((B,), device=dev, dtype=torch.int32) if want_count else None
+    kw = _binding_kwargs(fx, fy, cx, cy, baseline, doffs, depth_scale, depth_trunc, conf_min, occ_min, filtered)
+    hip.smooth(disp, occ, conf, H=H, W=W, **kw, radius=radius, sigma_s=radius / 2.0 if sigma_s is None else sigma_s, sigma_r=sigma_r,
+               max_jump=max_jump, disp_out=out, taps=taps, count=count)
+    return Smoothed(out, taps, count)
 
 
 def track(disp: torch.Tensor, occ: torch.Tensor, conf: torch.Tensor, model: TsdfRender, *, R=None, t=None, poses: Optional[torch.Tensor] = None,

@@ -187,6 +187,12 @@ class NormalsDesc(ctypes.Structure):
                 ("max_jump", ctypes.c_double), ("min_cos", ctypes.c_double)]
 
 
+class SmoothDesc(ctypes.Structure):
+    """mirror of s2m2_smooth_desc (include/s2m2_hip.h): K29, edge-preserving smoothing of the disparity map"""
+    _fields_ = [("cloud", CloudDesc), ("disp_out", _vp), ("taps", _vp), ("count", _vp), ("radius", _i), ("sigma_s", ctypes.c_double),
+                ("sigma_r", ctypes.c_double), ("max_jump", ctypes.c_double)]
+
+
 class RectifyDesc(ctypes.Structure):
     """mirror of s2m2_rectify_desc (include/s2m2_hip.h): K16, the rectifier in front of the forward"""
     _fields_ = [("src", _vp * 2), ("records", _vp), ("out", _vp), ("maps", _vp), ("n_src", _i), ("n_img", _i), ("Hs", _i), ("Ws", _i),
@@ -318,6 +324,9 @@ SIGNATURES = {
     "s2m2_tsdf_track_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "s2m2_tsdf_track": (_i, [ctypes.POINTER(TsdfTrackDesc), _vp]),
     "s2m2_normals": (_i, [ctypes.POINTER(NormalsDesc), _vp]),
+    "s2m2_smooth": (_i, [ctypes.POINTER(SmoothDesc), _vp]),
+    "s2m2_smooth_weights": (_i, [_i, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                 ctypes.POINTER(ctypes.c_float)]),
 }
 
 
@@ -1431,3 +1440,5 @@ from .hip_tsdf import (RAYCAST_MAX_STEPS, TRACK_MAX_ITERS, tsdf_extract, tsdf_in
                        tsdf_raycast_steps, tsdf_tile_voxels, tsdf_track, tsdf_track_workspace_bytes, tsdf_workspace_bytes)
 # K28 (s2m2_normals): likewise, from hip_normals.py
 from .hip_normals import NORMALS_MAX_RADIUS, normals  # noqa: E402,F401
+# K29 (s2m2_smooth): likewise, from hip_smooth.py
+from .hip_smooth import smooth, smooth_weights  # noqa: E402,F401

@@ -204,6 +204,22 @@ def get_normals(disp, calib, depth_trunc=None, radius=1, max_jump=1.0, min_cos=0
                              radius=radius, max_jump=max_jump, min_cos=min_cos)
 
 
+def smooth_disparity(disp, calib, sigma_r, max_jump, depth_trunc=None, radius=2, sigma_s=None):
+    """``get_normals``'s conventions (halved intrinsics, fx for both focal lengths, no confidence filter: ``disp`` (H,W) arrives filtered, -1
+    where invalid) -> a ``cloud.Smoothed`` on the device: the disparity map after the edge-preserving filter of ``cloud.smooth`` (a window of
+    (2 ``radius`` + 1)^2 pixels, the widths ``sigma_s`` pixels -- None: ``radius / 2`` -- and ``sigma_r`` px of disparity, neighbours within
+    ``max_jump`` px of the centre), -1 where the pixel is not kept.  ``.disp[0, 0]`` stands wherever ``disp`` stood."""
+    from . import cloud
+    disp_t = torch.as_tensor(disp)
+    device = disp_t.device if disp_t.is_cuda else torch.device("cuda")
+    disp_t = disp_t.to(device=device, dtype=torch.float32).contiguous()[None, None]
+    cam0 = calib["cam0"]
+    with torch.cuda.device(device):
+        return cloud.smooth(disp_t, disp_t, disp_t, fx=float(cam0[0, 0]) / 2.0, cx=float(cam0[0, 2]) / 2.0, cy=float(cam0[1, 2]) / 2.0,
+                            baseline=float(calib["baseline"]), doffs=float(calib["doffs"]), depth_trunc=depth_trunc, filtered=False,
+                            radius=radius, sigma_s=sigma_s, sigma_r=sigma_r, max_jump=max_jump)
+
+
 def voxel_down_sample(rgb, disp, calib, voxel_size, depth_trunc=None):
     """``get_pointcloud``'s arguments and conventions (halved intrinsics, fx for both focal lengths, no confidence filter) -> a
     ``cloud.VoxelCloud`` on the device: one point per occupied cell of a grid of ``voxel_size`` (the unit of z: metres with a Middlebury
